@@ -10,15 +10,19 @@ pairs shard across ranks with no data-path dependency; each step ends with the R
 the fixed-stride match table.
 
 Prints ONE JSON line (rank 0).  `roofline` = attention kernel (the dominant kernel, 135 of 334
-GF/pair), algorithmic flops / HIP-event time measured live in the timed region; `cpu_baseline` =
-the torch-CPU oracle on a bounded sample of the same workload on this host's cores.
+GF/pair), algorithmic flops / HIP-event time measured live in the timed region.
 
-The plain invocation (what the driver runs) then times short legs of the OTHER BASELINE.json
+The plain invocation (`--gpus N --steps K --warmup W`) does only what its headline figure needs:
+set-up, W warm-up steps, K timed steps, the outputs of the last step when `--dump-outputs DIR` is
+given, the JSON line.  `--full` adds, after the timed region, everything else the benchmark
+measures or checks: `parity` (pairs of the timed batch against the CPU oracle), `cpu_baseline`
+(the torch-CPU oracle on a bounded sample of the same workload on this host's cores), the extra
+timed runs some workloads make beside their line, and short legs of the OTHER BASELINE.json
 configs in the same process -- configs[0] mutual-NN, configs[1] SuperPoint, configs[3] LoFTR
-1024x1024, configs[4] DUSt3R 512x512 in both arithmetics -- and attaches their lines (value,
-ms_per_step, roofline, cpu_baseline, parity) to the one JSON line as "workloads" (`--no-legs`:
-headline only; `--workload X`: that workload's line alone).  The library is built under a file
-lock first when it is missing or stale, so a clean checkout and an N-rank launch work.
+1024x1024, configs[4] DUSt3R 512x512 in both arithmetics -- attached to the one JSON line as
+"workloads" (`--no-legs`: headline only; `--workload X`: that workload's line alone).  The library
+is built under a file lock first when it is missing or stale, so a clean checkout and an N-rank
+launch work.
 """
 from __future__ import annotations
 
@@ -390,11 +394,12 @@ def bench_nn(args, dev, rank, world):
         from oracle.mutual_nn import mutual_nn
 
         nnc = {"ratio_threshold": None, "distance_threshold": None, "do_mutual_check": True}
-        ref = mutual_nn({"descriptors0": d0[:1].cpu(), "descriptors1": d1[:1].cpu()}, nnc)
-        ok = torch.equal(out["matches0"][:1].cpu().long(), ref["matches0"].long()) and (out["matching_scores0"][:1].cpu() - ref["matching_scores0"]).abs().max().item() < 1e-4
-        if not ok:
-            raise AssertionError("bench parity (nn): matches / scores differ from the oracle")
-        line["parity"] = {"status": "ok", "checked": "pair 0 vs oracle/mutual_nn.py (golden-pinned), matches bit-exact, scores within 1e-4"}
+        if args.full:
+            ref = mutual_nn({"descriptors0": d0[:1].cpu(), "descriptors1": d1[:1].cpu()}, nnc)
+            ok = torch.equal(out["matches0"][:1].cpu().long(), ref["matches0"].long()) and (out["matching_scores0"][:1].cpu() - ref["matching_scores0"]).abs().max().item() < 1e-4
+            if not ok:
+                raise AssertionError("bench parity (nn): matches / scores differ from the oracle")
+            line["parity"] = {"status": "ok", "checked": "pair 0 vs oracle/mutual_nn.py (golden-pinned), matches bit-exact, scores within 1e-4"}
         if not args.no_cpu_baseline and world == 1:
             torch.set_num_threads(min(os.cpu_count() or 1, 32))
             c0, c1 = d0.cpu(), d1.cpu()
@@ -574,6 +579,7 @@ def bench_loftr(args, dev, rank, world):
                           "note": "data dependent: the synthetic pair of this leg yields few matches; the dense evaluation is what `--fine-dense` (option 0) times"}  # fmt: skip
             if mode == 1:
                 tf_pair += win_tf - dense_tf
+            if mode == 1 and args.full:
                 # the same step with the dense maps (option 0), timed right here: what this leg reported until round 5 and what a pair with
                 # thousands of matches costs (break-even ~3000 matches per 1024^2 pair: profiles/r06_lab_loftr_fine.txt)
                 with backend.option(dev, loftr_fine_sparse=0):
@@ -587,7 +593,7 @@ def bench_loftr(args, dev, rank, world):
                     td = (time.perf_counter() - td) / max(2, args.steps // 2)
                 fine_stage["dense_maps_pairs_per_s"] = B / td
                 fine_stage["dense_maps_ms_per_step"] = td * 1e3
-            if (Hh, Ww) == (1024, 1024) and "IMCUI_BENCH_LOFTR_THR" not in os.environ:
+            if (Hh, Ww) == (1024, 1024) and "IMCUI_BENCH_LOFTR_THR" not in os.environ and args.full:
                 # The synthetic pair with seeded weights yields 17 matches per pair at the zoo's threshold; a real outdoor pair yields thousands, and
                 # both the fine transformer and the window evaluation scale with that.  The same step with the coarse threshold lowered until the
                 # synthetic pair gives ~2000 matches per pair (3e-5), default routing and dense maps: the load a user is more likely to see.
@@ -764,7 +770,7 @@ def bench_dust3r(args, dev, rank, world):
     cls_ms = {k: backend.profile_read(dev, k) for k in ("gemm", "conv3x3", "attention")}
     backend.profile_enable(dev, False)
     net_ms = None
-    if mast:  # the network alone, same batch (the matching step = the rest of a step)
+    if mast and args.full:  # the network alone, same batch (the matching step = the rest of a step)
         torch.cuda.synchronize()
         t1 = time.perf_counter()
         for _ in range(3):
@@ -802,7 +808,7 @@ def bench_dust3r(args, dev, rank, world):
                        "pairs_per_step_per_gpu": B, "weights": "seeded random (imcui_hip/synth_weights.py), AsymmetricCroCo3DStereo architecture, 578 M parameters",
                        "mean_confidence": float(out["conf"].mean()),
                        **({"head": "catmlp+dpt, 24-d descriptors; matching: fast_reciprocal_NNs(subsample 2, dot, 10 rounds) on the device, 2000 matches kept",
-                           "matcher_arithmetic": args.nn_arith, "matches_per_pair": nmatch[0] / B, "network_ms_per_step": net_ms, "matching_ms_per_step": dt / args.steps * 1e3 - net_ms} if mast else {})},
+                           "matcher_arithmetic": args.nn_arith, "matches_per_pair": nmatch[0] / B, "network_ms_per_step": net_ms, "matching_ms_per_step": dt / args.steps * 1e3 - net_ms if net_ms is not None else None} if mast else {})},
             "roofline": {"kernel": "gemm_split_kernel + conv3x3_split_kernel + attn_split_kernel (matrix class)", "bound": "mfma", "achieved": ach,
                          "peak": PEAK_F16_MFMA_TF, "unit": "TFLOP/s", "frac": ach / PEAK_F16_MFMA_TF, "traffic": traffic, "traffic_source": traffic_source,
                          "class_ms_per_step": {k: v[0] / args.steps for k, v in cls_ms.items()}, "launches_per_step": mat_n / args.steps,
@@ -895,12 +901,14 @@ def bench_superglue(args, dev, rank, world):
     conv_ms, _ = backend.profile_read(dev, "conv3x3")
     gemm_ms, _ = backend.profile_read(dev, "gemm")
     backend.profile_enable(dev, False)
-    # the optimal transport alone: the same step without Sinkhorn rounds (outside the timed region)
-    pipe.matcher.conf["runtime_match_threshold"] = True  # the plugin freezes its conf at _init like the reference; this leg re-reads it
-    pipe.matcher.conf["sinkhorn_iterations"] = 0
-    pipe(img0, img1)
-    dt0, _ = timed(max(2, args.steps // 2))
-    dt0 *= args.steps / max(2, args.steps // 2)
+    dt0 = None
+    if args.full:
+        # the optimal transport alone: the same step without Sinkhorn rounds (outside the timed region)
+        pipe.matcher.conf["runtime_match_threshold"] = True  # the plugin freezes its conf at _init like the reference; this leg re-reads it
+        pipe.matcher.conf["sinkhorn_iterations"] = 0
+        pipe(img0, img1)
+        dt0, _ = timed(max(2, args.steps // 2))
+        dt0 *= args.steps / max(2, args.steps // 2)
     if dist_on(world):
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -911,7 +919,7 @@ def bench_superglue(args, dev, rank, world):
         peak = PEAK_F16_MFMA_TF if split else PEAK_F32_MFMA_TF
         attn_flops = B * 8.59e9 * (nk0 * nk1 / (MAXK * MAXK))  # one launch: 2 images x 4 heads x (QK^T + PV) at 2048 x 2048 x 64
         achieved = attn_flops / (attn_ms / max(attn_n, 1) * 1e-3) / 1e12 if attn_n else 0.0
-        sk_ms = max(dt - dt0, 0.0) / args.steps * 1e3
+        sk_ms = max(dt - dt0, 0.0) / args.steps * 1e3 if dt0 is not None else None
         sk_bytes = args.sinkhorn * 4.0 * nk0 * nk1 * B  # the fused round reads the score matrix once (row pass + column statistics)
         line = {
             "metric": "image-pairs/sec @640x480 SuperPoint+SuperGlue", "value": world * B * args.steps / dt, "unit": "pairs/s", "n_gpus": world,
@@ -925,7 +933,7 @@ def bench_superglue(args, dev, rank, world):
                          "achieved": achieved, "peak": peak, "unit": "TFLOP/s", "frac": achieved / peak, "traffic": None,
                          "avg_launch_ms": attn_ms / max(attn_n, 1), "launches": attn_n},
             "sinkhorn": {"bound": "hbm", "ms_per_step": sk_ms, "algorithmic_bytes_per_step": sk_bytes,
-                         "achieved": sk_bytes / (sk_ms * 1e-3) / 1e9 if sk_ms > 0 else None, "peak": 8000.0, "unit": "GB/s",
+                         "achieved": sk_bytes / (sk_ms * 1e-3) / 1e9 if sk_ms else None, "peak": 8000.0, "unit": "GB/s",
                          "note": "step time minus the same step with 0 Sinkhorn rounds; rounds * 4 * n0 * n1 bytes per pair (one matrix read per round; "
                                  "the band partials add 12 %)"},
             "kernel_time_ms_per_step": {"attention": attn_ms / args.steps, "conv3x3": conv_ms / args.steps, "gemm": gemm_ms / args.steps},
@@ -1006,10 +1014,10 @@ LEGS = {
 
 
 def legs_enabled(args) -> bool:
-    """The default invocation (`python bench.py --gpus N --steps K --warmup W`, what the driver runs) carries the legs; any switch that
-    turns the run into a profiler pass or an A/B leg (--no-parity, --no-cpu-baseline, --adaptive, --graph, --h2d, --precision 0, --batch,
-    another --workload, --gpus > 1) does not, and --no-legs / --legs select explicitly."""
-    if args.no_legs:
+    """The full headline invocation (`python bench.py --gpus N --steps K --warmup W --full`) carries the legs; a plain run (no --full) never
+    does, nor does any switch that turns the run into a profiler pass or an A/B leg (--no-parity, --no-cpu-baseline, --adaptive, --graph,
+    --h2d, --precision 0, --batch, another --workload, --gpus > 1), and --no-legs / --legs select explicitly."""
+    if args.no_legs or not args.full:
         return False
     if args.legs is not None:
         return True
@@ -1036,7 +1044,8 @@ def run_legs(args, dev, rank, world) -> dict:
             out[name] = {"status": "unknown leg", "known": list(LEGS)}
             continue
         workload, over = LEGS[name]
-        a = argparse.Namespace(**{**vars(args), **over, "workload": workload, "steps": min(args.steps, 10), "warmup": min(args.warmup, 3), "nn_arith": "auto"})
+        a = argparse.Namespace(**{**vars(args), **over, "workload": workload, "steps": min(args.steps, 10), "warmup": min(args.warmup, 3), "nn_arith": "auto",
+                                  "dump_outputs": None})
         gc.collect()
         torch.cuda.empty_cache()
         t0 = time.perf_counter()
@@ -1178,11 +1187,22 @@ def main():
                     help="dust3r: fp32 = 3 x f16 split products (default, the parity mode), fp16 = one f16 product per element pair (bf16-class)")
     ap.add_argument("--precision", type=int, default=1, choices=[0, 1],
                     help="0 = exact f32 MFMA, 1 = 3 x f16 split MFMA with f32 accumulate (default, parity-tested)")
-    ap.add_argument("--legs", default=None, help="comma-separated legs to run after the workload and attach as \"workloads\" (" + ", ".join(LEGS) + "; `all`); default: all of "
-                                                 "them on the plain headline invocation, none otherwise")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run the oracle parity checks, the CPU baselines, the extra timed runs of the loftr / mast3r / superglue "
+                         "lines and (headline invocation) the legs; off: set-up, warm-up, timed steps and the JSON line only")
+    ap.add_argument("--legs", default=None, help="with --full: comma-separated legs to run after the workload and attach as \"workloads\" (" + ", ".join(LEGS) + "; `all`); "
+                                                 "default: all of them on the headline invocation, none otherwise")
     ap.add_argument("--no-legs", action="store_true", help="headline line only")
     ap.add_argument("--fine-dense", action="store_true", help="loftr: the last FPN stage as dense maps whatever the match count (option loftr_fine_sparse = 0; A/B)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="splg: write what the last timed step returned (rank 0's pairs) as DIR/<name>.npy, float32 / float64 (dump_outputs)")
     args = ap.parse_args()
+    if args.legs is not None and not args.full:
+        ap.error("--legs needs --full")
+    if args.dump_outputs and args.workload != "splg":
+        ap.error("--dump-outputs is implemented for the headline workload (splg) only")
+    if not args.full:  # a plain run: no oracle check, no CPU baseline (legs_enabled and the extra timed runs read args.full themselves)
+        args.no_parity = args.no_cpu_baseline = True
     args.batch_given = args.batch
     if args.batch is None:
         args.batch = 16 if args.workload == "loftr" else 32 if args.workload == "eloftr" else 32 if args.workload == "dust3r" else 16 if args.workload == "mast3r" else 64  # pairs per step and GPU (64: +2.5 % over 32, same kernels; dust3r 8 / 16 / 32: 86.5 / 90.5 / 92.7 pairs/s)
@@ -1368,6 +1388,44 @@ def bench_seam(args, dev, rank, world):
             "seam": {k: {kk: round(vv, 3) for kk, vv in v.items()} for k, v in res.items()}}  # fmt: skip
 
 
+def splg_outputs(out: dict) -> dict:
+    """What a caller of the pair pipeline receives, per side: key-points, scores, descriptors, counts, matches, matching scores, pruning
+    counters, and the stop layer.  The rows past an image's key-point count are padding of the fixed-stride buffers, not results: they
+    are zeroed so that two runs compare on what they computed."""
+    res = {"stop": out["stop"]}
+    for s in "01":
+        n = out["num_keypoints" + s]
+        valid = torch.arange(out["keypoints" + s].shape[1], device=n.device)[None, :] < n[:, None].long()
+        res["num_keypoints" + s] = n
+        for k in ("keypoints", "scores", "descriptors", "matches", "matching_scores", "prune"):
+            t = out[k + s]
+            res[k + s] = torch.where(valid.reshape(valid.shape + (1,) * (t.dim() - 2)), t, torch.zeros((), dtype=t.dtype, device=t.device))
+    return res
+
+
+def dump_outputs(path: str, arrays: dict, budget: int = 56 << 20) -> None:
+    """Write every tensor of `arrays` as <path>/<name>.npy: float64 stays float64, other floating types become float32, integers float64
+    (exact).  The files hold at most `budget` bytes of data: arrays are taken smallest first and kept whole while they fit an equal share
+    of what is left; a larger one is reduced to a fixed sample of its flattened elements (ascending indices drawn with seed 0), the same
+    sample in every run of the same shapes."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    host = {}
+    for name, t in arrays.items():
+        t = t.detach().cpu()
+        host[name] = (t.double() if t.dtype == torch.float64 or not t.is_floating_point() else t.float()).numpy()
+    left = budget
+    order = sorted(host, key=lambda k: host[k].nbytes)
+    for i, name in enumerate(order):
+        a = host[name]
+        share = left // (len(order) - i)
+        if a.nbytes > share:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, size=share // a.itemsize, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
+        left -= a.nbytes
+
+
 def bench_splg(args, dev, rank, world):
     """configs[2], the BASELINE metric: SuperPoint + LightGlue on 640x480 pair batches (module docstring)."""
     from imcui_hip import backend
@@ -1513,6 +1571,8 @@ def bench_splg(args, dev, rank, world):
         dt = float(t.item())
 
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, splg_outputs(out))
         nk0 = out["num_keypoints0"].float().mean().item()
         nk1 = out["num_keypoints1"].float().mean().item()
         stop = out["stop"].float().mean().item()

@@ -1,5 +1,5 @@
 """Host logic of bench.py that needs no GPU: which invocations carry the legs of the other BASELINE configs, the leg table, the
-locked self-build, the rank-agreement guard on one rank."""
+locked self-build, the rank-agreement guard on one rank, the output dump of `--dump-outputs`."""
 import argparse
 import os
 import sys
@@ -13,13 +13,14 @@ import bench  # noqa: E402
 
 def _args(**kw):
     base = dict(workload="splg", no_parity=False, no_cpu_baseline=False, adaptive=False, graph=False, h2d=None, precision=1, batch_given=None, gpus=1, legs=None,
-                no_legs=False)  # fmt: skip
+                no_legs=False, full=True)  # fmt: skip
     base.update(kw)
     return argparse.Namespace(**base)
 
 
 def test_which_invocations_carry_the_legs():
-    assert bench.legs_enabled(_args())  # the driver's plain command line
+    assert bench.legs_enabled(_args())  # the full headline command line
+    assert not bench.legs_enabled(_args(full=False)) and not bench.legs_enabled(_args(full=False, legs="all"))  # a plain run: the headline alone
     assert not bench.legs_enabled(_args(no_legs=True))
     for kw in (dict(no_parity=True), dict(no_cpu_baseline=True), dict(adaptive=True), dict(graph=True), dict(h2d="raw"), dict(h2d="jpeg"), dict(precision=0),
                dict(batch_given=32), dict(workload="loftr"), dict(gpus=8)):  # fmt: skip
@@ -66,3 +67,35 @@ def test_ensure_built_is_a_no_op_on_a_fresh_library_and_guard_on_one_rank():
     bench.ensure_built()
     assert not b.needs_build() and os.path.exists(b.LIB_PATH)
     assert bench.ranks_agree(True, 1, torch.device("cpu")) and not bench.ranks_agree(False, 1, torch.device("cpu"))
+
+
+def test_dump_outputs_zeroes_padding_keeps_dtypes_and_fits_the_budget(tmp_path):
+    """`--dump-outputs`: the rows past a key-point count are zeroed (padding, not results), integers are written exactly as float64, floats
+    as float32, and an array larger than its share of the budget becomes the same seeded sample of its elements in every run."""
+    import numpy as np
+
+    B, K = 2, 8
+    g = torch.Generator().manual_seed(0)
+    out = {"stop": torch.tensor([3, 9], dtype=torch.int32)}
+    for s in "01":
+        out.update({f"keypoints{s}": torch.rand(B, K, 2, generator=g), f"scores{s}": torch.rand(B, K, generator=g),
+                    f"descriptors{s}": torch.rand(B, K, 256, generator=g), f"num_keypoints{s}": torch.tensor([5, K], dtype=torch.int32),
+                    f"matches{s}": torch.randint(-1, K, (B, K), generator=g, dtype=torch.int32), f"matching_scores{s}": torch.rand(B, K, generator=g),
+                    f"prune{s}": torch.randint(0, 9, (B, K), generator=g, dtype=torch.int32)})  # fmt: skip
+    out["descriptors0"][0, 5:] = float("nan")  # what unwritten padding may hold
+    arr = bench.splg_outputs(out)
+    assert set(arr) == set(out)
+    assert torch.equal(arr["descriptors0"][0, 5:], torch.zeros(3, 256)) and torch.equal(arr["descriptors0"][0, :5], out["descriptors0"][0, :5])
+    assert torch.equal(arr["matches0"][0, 5:], torch.zeros(3, dtype=torch.int32)) and torch.equal(arr["matches0"][1], out["matches0"][1])
+    budget = 20_000
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arr, budget=budget)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(k + ".npy" for k in out)
+    loaded = {f: np.load(tmp_path / "a" / f) for f in files}
+    assert sum(a.nbytes for a in loaded.values()) <= budget
+    assert loaded["matches0.npy"].dtype == np.float64 and np.array_equal(loaded["matches0.npy"], arr["matches0"].double().numpy())
+    assert loaded["keypoints1.npy"].dtype == np.float32 and np.array_equal(loaded["keypoints1.npy"], arr["keypoints1"].numpy())
+    d1 = loaded["descriptors1.npy"]  # 16 KB of float32 > its share: a sample, identical in both runs
+    assert d1.dtype == np.float32 and d1.ndim == 1 and d1.size < B * K * 256 and np.array_equal(d1, np.load(tmp_path / "b" / "descriptors1.npy"))
+    assert not np.isnan(loaded["descriptors0.npy"]).any()

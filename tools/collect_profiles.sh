@@ -12,7 +12,7 @@ mkdir -p $O
 echo "${HEAD:-unknown}" > $O/HEAD
 P=${PART:-123}
 cd /tmp && export TMPDIR=/tmp
-b() { ( cd $R && timeout ${T:-300} python bench.py "${@:2}" > $O/$1.json.log 2>$O/$1.err; tail -1 $O/$1.json.log | cut -c1-150 ); }
+b() { ( cd $R && timeout ${T:-300} python bench.py --full "${@:2}" > $O/$1.json.log 2>$O/$1.err; tail -1 $O/$1.json.log | cut -c1-150 ); }
 stats() { timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_$1 -o $1 -- python $R/bench.py "${@:2}" --no-cpu-baseline --no-parity --no-legs > $O/rocprof_$1.log 2>&1 < /dev/null; echo "stats $1 rc $?"; }
 pmc() { timeout 300 rocprofv3 --kernel-trace --pmc ${@:3} --output-format csv -d $O/pmc_$1 -o $2 -- python $R/bench.py ${WL} --steps 2 --warmup 1 --no-cpu-baseline --no-parity --no-legs > $O/pmc_$1.log 2>&1 < /dev/null; echo "pmc $1 rc $?"; }
 SQ="SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_LDS_BANK_CONFLICT"
