@@ -2,10 +2,12 @@
 
 PyTorch-ROCm tensors in, tensors out.  Everything is enqueued on
 ``torch.cuda.current_stream()``; nothing here synchronises except where the reference's
-ragged list outputs force a device->host read of the key-point counts.
+ragged list outputs force a device->host read of the key-point counts, and LoFTR's default
+windowed fine stage (`LoFTRHIP.forward`), which reads its match count back.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import threading
 
@@ -35,6 +37,15 @@ class Handle:
             msg = self.lib.imcui_hip_last_error(self.h)
             raise ImcuiHipError(f"{what} failed ({rc}): {msg.decode() if msg else ''}")
 
+    def call(self, fn, *args):
+        """`fn(h, *args)` for an ABI function of this handle; a non-zero status raises, naming the C symbol."""
+        self.check(fn(self.h, *args), fn.__name__)
+
+    def launch(self, fn, *args):
+        """The one path of every stream-ordered ABI call: `fn(h, *args, stream)` on this handle's device and its current stream."""
+        with torch.cuda.device(self.device_index):
+            self.call(fn, *args, _stream_ptr())
+
 
 def get_handle(device: torch.device) -> Handle:
     if device.type != "cuda":
@@ -60,37 +71,69 @@ def _as_f32_host(t) -> np.ndarray:
     return np.ascontiguousarray(t, dtype=np.float32)
 
 
-class _Workspace:
-    """Caller-provided scratch of the C ABI: one grow-only byte buffer per (device, stream).
+def _pad_rows(t: torch.Tensor, n: int, device: torch.device) -> torch.Tensor:
+    """[B, m, ...] -> float32 [B, n, ...] on `device`, rows m.. zero (the tensor itself, made contiguous, when m == n)."""
+    if t.shape[1] == n:
+        return t.contiguous().float()
+    shape = list(t.shape)
+    shape[1] = n
+    o = torch.zeros(shape, dtype=torch.float32, device=device)
+    o[:, : t.shape[1]] = t
+    return o
 
-    Kernels of one stream execute in order, so a buffer is only ever shared by launches that are ordered
-    anyway; two streams (two Gradio worker threads, a side stream) get separate buffers and cannot overwrite
-    each other's scratch while kernels are in flight.  A buffer that was handed out during a HIP-graph capture
-    is baked into that graph: it is pinned, and a later request that would have to re-allocate it raises
-    instead of freeing memory the graph still replays on."""
+
+_owner = threading.local()
+
+
+@contextlib.contextmanager
+def workspace_owner(table: dict):
+    """Inside the block, scratch handed out on this thread comes from `table` (one buffer per (`_Workspace`, device)) instead of the
+    per-stream buffers.  A captured graph enters it around its warm-up and capture and keeps `table` as an attribute: the graph owns its
+    scratch, no stream or other graph can grow or re-use it, and it is freed together with the graph."""
+    prev = getattr(_owner, "table", None)
+    _owner.table = table
+    try:
+        yield
+    finally:
+        _owner.table = prev
+
+
+class _Workspace:
+    """Caller-provided scratch of the C ABI: one grow-only byte buffer per (device, stream), or per device in the table of the active
+    `workspace_owner`.
+
+    Kernels of one stream execute in order, so a buffer is only ever shared by launches that are ordered anyway; two streams (two Gradio
+    worker threads, a side stream) get separate buffers and cannot overwrite each other's scratch while kernels are in flight.  A HIP-graph
+    capture must run inside a `workspace_owner`: a buffer handed out during the capture is baked into the graph, and a later request that
+    would have to re-allocate it raises instead of freeing memory the graph still replays on."""
 
     def __init__(self):
-        self._bufs: dict[tuple[int, int], torch.Tensor] = {}
-        self._pinned: set[tuple[int, int]] = set()
+        self._bufs: dict[tuple[int, int], tuple[torch.Tensor, bool]] = {}  # (device, stream) -> (buffer, pinned)
+        self._lock = threading.Lock()
 
-    def get(self, nbytes: int, device: torch.device) -> torch.Tensor:
+    @contextlib.contextmanager
+    def use(self, nbytes: int, device: torch.device):
+        """A buffer of at least `nbytes` bytes, the lock held until the block (the launch that reads it) ends."""
         idx = device.index if device.index is not None else torch.cuda.current_device()
-        key = (idx, torch.cuda.current_stream(device).cuda_stream)
         capturing = torch.cuda.is_current_stream_capturing()
-        buf = self._bufs.get(key)
-        if buf is None or buf.numel() < nbytes:
-            if key in self._pinned:
-                raise ImcuiHipError(
-                    f"workspace of stream {key[1]:#x} is referenced by a captured HIP graph ({buf.numel()} B) and cannot grow to "
-                    f"{int(nbytes)} B: capture the graph after a warm-up at the largest shape, or run the larger call on another stream"
-                )
-            buf = None
-            self._bufs.pop(key, None)
-            buf = torch.empty(int(nbytes), dtype=torch.uint8, device=device)
-            self._bufs[key] = buf
-        if capturing:
-            self._pinned.add(key)
-        return buf
+        table = getattr(_owner, "table", None)
+        if table is not None:
+            key = (self, idx)
+        elif capturing:
+            raise ImcuiHipError("HIP-graph capture outside backend.workspace_owner: the graph's scratch would be a stream's buffer that later calls may free")
+        else:
+            table, key = self._bufs, (idx, torch.cuda.current_stream(device).cuda_stream)
+        with self._lock:
+            buf, pinned = table.get(key, (None, False))
+            if buf is None or buf.numel() < nbytes:
+                if pinned:
+                    raise ImcuiHipError(f"workspace of a captured HIP graph ({buf.numel()} B) cannot grow to {int(nbytes)} B: "
+                                        "capture the graph after a warm-up at the largest shape")
+                buf = None
+                table.pop(key, None)
+                buf = torch.empty(int(nbytes), dtype=torch.uint8, device=device)
+            table[key] = (buf, pinned or capturing)
+            yield buf
 
 
 # ------------------------------------------------------------------ SuperPoint
@@ -118,7 +161,6 @@ SP_TOPK_MAX = 16384  # on-chip top-k sorter of sp_topk_kernel (csrc/superpoint.h
 class SuperPointHIP:
     def __init__(self):
         self._ws = _Workspace()
-        self._lock = threading.Lock()
 
     def forward(self, packed: torch.Tensor, image: torch.Tensor, conf: dict, want_score_map: bool = False, kcap: int | None = None):
         """image [B,1,H,W] float32 on the GPU.  Returns dict of fixed-stride tensors + counts.
@@ -147,15 +189,12 @@ class SuperPointHIP:
         nk = torch.empty((B,), dtype=torch.int32, device=dev)
         status = torch.empty((1,), dtype=torch.int32, device=dev)
         smap = torch.empty((B, H, W), dtype=torch.float32, device=dev) if want_score_map else None
-        with self._lock:
-            ws = self._ws.get(lib.imcui_hip_superpoint_workspace_bytes(B, H, W, nms), dev)
-            with torch.cuda.device(dev):
-                rc = lib.imcui_hip_superpoint_forward(
-                    hd.h, _ptr(packed), _ptr(image), B, H, W, nms, float(conf["keypoint_threshold"]),
-                    int(conf["remove_borders"]), maxk, int(bool(conf.get("fix_sampling", False))), kcap,
-                    _ptr(kpts), _ptr(scores), _ptr(desc), _ptr(nk), _ptr(status), _ptr(smap), _ptr(ws), ws.numel(), _stream_ptr(),
-                )  # fmt: skip
-                hd.check(rc, "imcui_hip_superpoint_forward")
+        with self._ws.use(lib.imcui_hip_superpoint_workspace_bytes(B, H, W, nms), dev) as ws:
+            hd.launch(
+                lib.imcui_hip_superpoint_forward, _ptr(packed), _ptr(image), B, H, W, nms, float(conf["keypoint_threshold"]),
+                int(conf["remove_borders"]), maxk, int(bool(conf.get("fix_sampling", False))), kcap,
+                _ptr(kpts), _ptr(scores), _ptr(desc), _ptr(nk), _ptr(status), _ptr(smap), _ptr(ws), ws.numel(),
+            )  # fmt: skip
         out = {"keypoints": kpts, "scores": scores, "descriptors": desc, "num_keypoints": nk, "status": status}
         if want_score_map:
             out["score_map"] = smap
@@ -221,7 +260,6 @@ def pack_lightglue(state_dict: dict) -> torch.Tensor:
 class LightGlueHIP:
     def __init__(self):
         self._ws = _Workspace()
-        self._lock = threading.Lock()
 
     def forward(self, packed, kpts0, kpts1, desc0, desc1, n0, n1, size0, size1, depth_confidence, width_confidence,
                 filter_threshold, pruning_threshold: int = -1, layer_dump: bool = False, scales_oris=None):  # fmt: skip
@@ -235,19 +273,9 @@ class LightGlueHIP:
         B, ncap0 = kpts0.shape[0], kpts0.shape[1]
         ncap1 = kpts1.shape[1]
         ncap = max(ncap0, ncap1, 1)
-
-        def pad(t, n):
-            if t.shape[1] == n:
-                return t.contiguous().float()
-            shape = list(t.shape)
-            shape[1] = n
-            o = torch.zeros(shape, dtype=torch.float32, device=dev)
-            o[:, : t.shape[1]] = t
-            return o
-
-        kpts0, kpts1, desc0, desc1 = pad(kpts0, ncap), pad(kpts1, ncap), pad(desc0, ncap), pad(desc1, ncap)
+        kpts0, kpts1, desc0, desc1 = (_pad_rows(t, ncap, dev) for t in (kpts0, kpts1, desc0, desc1))
         input_dim = desc0.shape[2]
-        so = [None] * 4 if scales_oris is None else [pad(t, ncap) for t in scales_oris]
+        so = [None] * 4 if scales_oris is None else [_pad_rows(t, ncap, dev) for t in scales_oris]
         n0 = n0.to(device=dev, dtype=torch.int32).contiguous()
         n1 = n1.to(device=dev, dtype=torch.int32).contiguous()
         m0 = torch.empty((B, ncap), dtype=torch.int32, device=dev)
@@ -258,25 +286,22 @@ class LightGlueHIP:
         p0 = torch.empty((B, ncap), dtype=torch.int32, device=dev)
         p1 = torch.empty((B, ncap), dtype=torch.int32, device=dev)
         dump = None
-        with self._lock:
-            ws = self._ws.get(lib.imcui_hip_lightglue_workspace_bytes(B, ncap), dev)
-            with torch.cuda.device(dev):
+        with self._ws.use(lib.imcui_hip_lightglue_workspace_bytes(B, ncap), dev) as ws:
+            if layer_dump:
+                R = (ncap + 127) // 128 * 128
+                dump = torch.zeros((9, 2 * B, R, 256), dtype=torch.float32, device=dev)
+                hd.call(lib.imcui_hip_lightglue_set_layer_dump, _ptr(dump), dump.numel())
+            try:
+                hd.launch(
+                    lib.imcui_hip_lightglue_forward, _ptr(packed), B, ncap, input_dim, _ptr(kpts0), _ptr(kpts1), _ptr(desc0), _ptr(desc1),
+                    _ptr(so[0]), _ptr(so[1]), _ptr(so[2]), _ptr(so[3]), _ptr(n0), _ptr(n1),
+                    float(size0[0]), float(size0[1]), float(size1[0]), float(size1[1]),
+                    float(depth_confidence), float(width_confidence), int(pruning_threshold), float(filter_threshold),
+                    _ptr(m0), _ptr(m1), _ptr(s0), _ptr(s1), _ptr(stop), _ptr(p0), _ptr(p1), _ptr(ws), ws.numel(),
+                )  # fmt: skip
+            finally:
                 if layer_dump:
-                    R = (ncap + 127) // 128 * 128
-                    dump = torch.zeros((9, 2 * B, R, 256), dtype=torch.float32, device=dev)
-                    hd.check(lib.imcui_hip_lightglue_set_layer_dump(hd.h, _ptr(dump), dump.numel()), "set_layer_dump")
-                try:
-                    rc = lib.imcui_hip_lightglue_forward(
-                        hd.h, _ptr(packed), B, ncap, input_dim, _ptr(kpts0), _ptr(kpts1), _ptr(desc0), _ptr(desc1),
-                        _ptr(so[0]), _ptr(so[1]), _ptr(so[2]), _ptr(so[3]), _ptr(n0), _ptr(n1),
-                        float(size0[0]), float(size0[1]), float(size1[0]), float(size1[1]),
-                        float(depth_confidence), float(width_confidence), int(pruning_threshold), float(filter_threshold),
-                        _ptr(m0), _ptr(m1), _ptr(s0), _ptr(s1), _ptr(stop), _ptr(p0), _ptr(p1), _ptr(ws), ws.numel(), _stream_ptr(),
-                    )  # fmt: skip
-                finally:
-                    if layer_dump:
-                        lib.imcui_hip_lightglue_set_layer_dump(hd.h, None, 0)
-                hd.check(rc, "imcui_hip_lightglue_forward")
+                    lib.imcui_hip_lightglue_set_layer_dump(hd.h, None, 0)
         out = {
             "matches0": m0[:, :ncap0], "matches1": m1[:, :ncap1], "matching_scores0": s0[:, :ncap0],
             "matching_scores1": s1[:, :ncap1], "stop": stop, "prune0": p0[:, :ncap0], "prune1": p1[:, :ncap1],
@@ -314,7 +339,6 @@ def pack_superglue(state_dict: dict) -> torch.Tensor:
 class SuperGlueHIP:
     def __init__(self):
         self._ws = _Workspace()
-        self._lock = threading.Lock()
 
     def forward(self, packed, kpts0, kpts1, scores0, scores1, desc0, desc1, n0, n1, size0, size1, sinkhorn_iterations,
                 match_threshold):  # fmt: skip
@@ -325,34 +349,20 @@ class SuperGlueHIP:
         B, ncap0 = kpts0.shape[0], kpts0.shape[1]
         ncap1 = kpts1.shape[1]
         ncap = max(ncap0, ncap1, 1)
-
-        def pad(t, n):
-            if t.shape[1] == n:
-                return t.contiguous().float()
-            shape = list(t.shape)
-            shape[1] = n
-            o = torch.zeros(shape, dtype=torch.float32, device=dev)
-            o[:, : t.shape[1]] = t
-            return o
-
-        kpts0, kpts1, desc0, desc1 = pad(kpts0, ncap), pad(kpts1, ncap), pad(desc0, ncap), pad(desc1, ncap)
-        scores0, scores1 = pad(scores0, ncap), pad(scores1, ncap)
+        kpts0, kpts1, desc0, desc1, scores0, scores1 = (_pad_rows(t, ncap, dev) for t in (kpts0, kpts1, desc0, desc1, scores0, scores1))
         n0 = n0.to(device=dev, dtype=torch.int32).contiguous()
         n1 = n1.to(device=dev, dtype=torch.int32).contiguous()
         m0 = torch.empty((B, ncap), dtype=torch.int32, device=dev)
         m1 = torch.empty((B, ncap), dtype=torch.int32, device=dev)
         s0 = torch.empty((B, ncap), dtype=torch.float32, device=dev)
         s1 = torch.empty((B, ncap), dtype=torch.float32, device=dev)
-        with self._lock:
-            ws = self._ws.get(lib.imcui_hip_superglue_workspace_bytes(B, ncap), dev)
-            with torch.cuda.device(dev):
-                rc = lib.imcui_hip_superglue_forward(
-                    hd.h, _ptr(packed), B, ncap, _ptr(kpts0), _ptr(kpts1), _ptr(scores0), _ptr(scores1), _ptr(desc0), _ptr(desc1),
-                    _ptr(n0), _ptr(n1), float(size0[0]), float(size0[1]), float(size1[0]), float(size1[1]),
-                    int(sinkhorn_iterations), float(match_threshold),
-                    _ptr(m0), _ptr(m1), _ptr(s0), _ptr(s1), _ptr(ws), ws.numel(), _stream_ptr(),
-                )  # fmt: skip
-                hd.check(rc, "imcui_hip_superglue_forward")
+        with self._ws.use(lib.imcui_hip_superglue_workspace_bytes(B, ncap), dev) as ws:
+            hd.launch(
+                lib.imcui_hip_superglue_forward, _ptr(packed), B, ncap, _ptr(kpts0), _ptr(kpts1), _ptr(scores0), _ptr(scores1), _ptr(desc0), _ptr(desc1),
+                _ptr(n0), _ptr(n1), float(size0[0]), float(size0[1]), float(size1[0]), float(size1[1]),
+                int(sinkhorn_iterations), float(match_threshold),
+                _ptr(m0), _ptr(m1), _ptr(s0), _ptr(s1), _ptr(ws), ws.numel(),
+            )  # fmt: skip
         return {
             "matches0": m0[:, :ncap0], "matches1": m1[:, :ncap1], "matching_scores0": s0[:, :ncap0],
             "matching_scores1": s1[:, :ncap1],
@@ -442,40 +452,56 @@ def pack_loftr(state_dict: dict) -> torch.Tensor:
     return torch.from_numpy(packed)
 
 
-class LoFTRHIP:
+class _DenseMatcherHIP:
+    """What LoFTR and EfficientLoFTR share: the input checks, the fixed-capacity outputs and `debug_buffer`, which reads intermediate maps
+    out of the last forward's workspace (`last_ws`, `last_dims`)."""
+
+    _debug_offset = ""  # the library's imcui_hip_*_debug_offset of the network
+
     def __init__(self):
         self._ws = _Workspace()
-        self._lock = threading.Lock()
         self.last_ws = None
 
-    def forward(self, packed, image0, image1, match_threshold, temp_bug_fix=False):
-        """kornia LoFTR.forward on image0 [B,1,H0,W0] / image1 [B,1,H1,W1] (sizes may differ between the two sides);
-        fixed-capacity outputs + device match count."""
+    def _inputs(self, name: str, image0: torch.Tensor, image1: torch.Tensor):
+        """-> (handle, image0, image1, dims (B, H0, W0, H1, W1), outputs in the order of the ABI's output pointers)."""
         dev = image0.device
         hd = get_handle(dev)
-        lib = hd.lib
         image0, image1 = image0.contiguous().float(), image1.contiguous().float()
         B, Cc, H0, W0 = image0.shape
         B1, C1, H1, W1 = image1.shape
         if Cc != 1 or C1 != 1 or B1 != B:
-            raise ImcuiHipError("LoFTR expects two batches of 1-channel images of equal batch size")
+            raise ImcuiHipError(f"{name} expects two batches of 1-channel images of equal batch size")
         cap = B * (H0 // 8) * (W0 // 8)
-        kp0 = torch.empty((cap, 2), dtype=torch.float32, device=dev)
-        kp1 = torch.empty((cap, 2), dtype=torch.float32, device=dev)
-        conf = torch.empty((cap,), dtype=torch.float32, device=dev)
-        bidx = torch.empty((cap,), dtype=torch.int32, device=dev)
-        nm = torch.zeros((1,), dtype=torch.int32, device=dev)
-        with self._lock:
-            ws = self._ws.get(lib.imcui_hip_loftr_workspace_bytes(B, H0, W0, H1, W1), dev)
-            self.last_ws = ws
-            self.last_dims = (B, H0, W0, H1, W1)
-            with torch.cuda.device(dev):
-                rc = lib.imcui_hip_loftr_forward(
-                    hd.h, _ptr(packed), _ptr(image0), _ptr(image1), B, H0, W0, H1, W1, float(match_threshold), int(bool(temp_bug_fix)),
-                    _ptr(kp0), _ptr(kp1), _ptr(conf), _ptr(bidx), _ptr(nm), _ptr(ws), ws.numel(), _stream_ptr(),
-                )  # fmt: skip
-                hd.check(rc, "imcui_hip_loftr_forward")
-        return {"keypoints0": kp0, "keypoints1": kp1, "confidence": conf, "batch_indexes": bidx, "num_matches": nm}
+        out = {
+            "keypoints0": torch.empty((cap, 2), dtype=torch.float32, device=dev), "keypoints1": torch.empty((cap, 2), dtype=torch.float32, device=dev),
+            "confidence": torch.empty((cap,), dtype=torch.float32, device=dev), "batch_indexes": torch.empty((cap,), dtype=torch.int32, device=dev),
+            "num_matches": torch.zeros((1,), dtype=torch.int32, device=dev),
+        }  # fmt: skip
+        return hd, image0, image1, (B, H0, W0, H1, W1), out
+
+    def debug_buffer(self, which: int, shape) -> torch.Tensor:
+        """Workspace buffer `which` of the last forward (`_debug_offset`) viewed as float32 `shape`."""
+        off = getattr(load_library(), self._debug_offset)(which, *self.last_dims)
+        n = int(np.prod(shape))
+        return self.last_ws[off : off + 4 * n].view(torch.float32).view(*shape)
+
+
+class LoFTRHIP(_DenseMatcherHIP):
+    _debug_offset = "imcui_hip_loftr_debug_offset"
+
+    def forward(self, packed, image0, image1, match_threshold, temp_bug_fix=False):
+        """kornia LoFTR.forward on image0 [B,1,H0,W0] / image1 [B,1,H1,W1] (sizes may differ between the two sides);
+        fixed-capacity outputs + device match count.
+
+        With the routing switch loftr_fine_sparse = 1 (the default) the call reads the coarse match count back to the host -- one
+        synchronisation -- to choose between the dense last FPN stage and the 5x5 windows of the matches (`last_fine_mode`).  On a stream
+        that is being captured into a HIP graph it takes the dense path and does not synchronise; loftr_fine_sparse = 0 never does."""
+        hd, image0, image1, dims, out = self._inputs("LoFTR", image0, image1)
+        with self._ws.use(hd.lib.imcui_hip_loftr_workspace_bytes(*dims), image0.device) as ws:
+            self.last_ws, self.last_dims = ws, dims
+            hd.launch(hd.lib.imcui_hip_loftr_forward, _ptr(packed), _ptr(image0), _ptr(image1), *dims, float(match_threshold), int(bool(temp_bug_fix)),
+                      *map(_ptr, out.values()), _ptr(ws), ws.numel())  # fmt: skip
+        return out
 
     @staticmethod
     def last_fine_mode(dev) -> tuple:
@@ -484,13 +510,6 @@ class LoFTRHIP:
         hd = get_handle(dev)
         m = C.c_int(-1)
         return int(hd.lib.imcui_hip_loftr_last_fine_mode(hd.h, C.byref(m))), m.value
-
-    def debug_buffer(self, which: int, shape) -> torch.Tensor:
-        """Workspace buffer `which` of the last forward (imcui_hip_loftr_debug_offset) viewed as float32 `shape`."""
-        lib = load_library()
-        off = lib.imcui_hip_loftr_debug_offset(which, *self.last_dims)
-        n = int(np.prod(shape))
-        return self.last_ws[off : off + 4 * n].view(torch.float32).view(*shape)
 
 
 # ------------------------------------------------------------------ EfficientLoFTR
@@ -577,48 +596,19 @@ def pack_eloftr(state_dict: dict) -> torch.Tensor:
     return torch.from_numpy(packed)
 
 
-class ELoFTRHIP:
-    def __init__(self):
-        self._ws = _Workspace()
-        self._lock = threading.Lock()
-        self.last_ws = None
+class ELoFTRHIP(_DenseMatcherHIP):
+    _debug_offset = "imcui_hip_eloftr_debug_offset"
 
     def forward(self, packed, image0, image1, match_threshold, debug_windows=False, arith=0):
         """Upstream EfficientLoFTR forward on image0 [B,1,H0,W0] / image1 [B,1,H1,W1] (multiples of 32; the two sizes may
         differ); fixed-capacity outputs + device match count.  arith 1 = the wrapper's precision "fp16" / "mp" (one f16
         product per element pair in the convolutions)."""
-        dev = image0.device
-        hd = get_handle(dev)
-        lib = hd.lib
-        image0, image1 = image0.contiguous().float(), image1.contiguous().float()
-        B, Cc, H0, W0 = image0.shape
-        B1, C1, H1, W1 = image1.shape
-        if Cc != 1 or C1 != 1 or B1 != B:
-            raise ImcuiHipError("EfficientLoFTR expects two batches of 1-channel images of equal batch size")
-        cap = B * (H0 // 8) * (W0 // 8)
-        kp0 = torch.empty((cap, 2), dtype=torch.float32, device=dev)
-        kp1 = torch.empty((cap, 2), dtype=torch.float32, device=dev)
-        conf = torch.empty((cap,), dtype=torch.float32, device=dev)
-        bidx = torch.empty((cap,), dtype=torch.int32, device=dev)
-        nm = torch.zeros((1,), dtype=torch.int32, device=dev)
-        with self._lock:
-            ws = self._ws.get(lib.imcui_hip_eloftr_workspace_bytes(B, H0, W0, H1, W1, int(bool(debug_windows))), dev)
-            self.last_ws = ws
-            self.last_dims = (B, H0, W0, H1, W1)
-            with torch.cuda.device(dev):
-                rc = lib.imcui_hip_eloftr_forward_ex(
-                    hd.h, _ptr(packed), _ptr(image0), _ptr(image1), B, H0, W0, H1, W1, float(match_threshold), int(arith), _ptr(kp0), _ptr(kp1),
-                    _ptr(conf), _ptr(bidx), _ptr(nm), int(bool(debug_windows)), _ptr(ws), ws.numel(), _stream_ptr(),
-                )  # fmt: skip
-                hd.check(rc, "imcui_hip_eloftr_forward")
-        return {"keypoints0": kp0, "keypoints1": kp1, "confidence": conf, "batch_indexes": bidx, "num_matches": nm}
-
-    def debug_buffer(self, which: int, shape) -> torch.Tensor:
-        """Workspace buffer `which` of the last forward (imcui_hip_eloftr_debug_offset) viewed as float32 `shape`."""
-        lib = load_library()
-        off = lib.imcui_hip_eloftr_debug_offset(which, *self.last_dims)
-        n = int(np.prod(shape))
-        return self.last_ws[off : off + 4 * n].view(torch.float32).view(*shape)
+        hd, image0, image1, dims, out = self._inputs("EfficientLoFTR", image0, image1)
+        with self._ws.use(hd.lib.imcui_hip_eloftr_workspace_bytes(*dims, int(bool(debug_windows))), image0.device) as ws:
+            self.last_ws, self.last_dims = ws, dims
+            hd.launch(hd.lib.imcui_hip_eloftr_forward_ex, _ptr(packed), _ptr(image0), _ptr(image1), *dims, float(match_threshold), int(arith),
+                      *map(_ptr, out.values()), int(bool(debug_windows)), _ptr(ws), ws.numel())  # fmt: skip
+        return out
 
 
 DUST3R_CFG = {"enc_dim": 1024, "enc_depth": 24, "dec_dim": 768, "dec_depth": 12, "desc_dim": 0}  # DUSt3R_ViTLarge_BaseDecoder_512_dpt
@@ -802,8 +792,20 @@ def check_dust3r_packed(packed: torch.Tensor, cfg: dict) -> None:
 class DUSt3RHIP:
     def __init__(self):
         self._ws = _Workspace()
-        self._lock = threading.Lock()
         self.last_dump = None
+
+    @staticmethod
+    def _check_inputs(hd: Handle, channels, pairs, NI: int) -> torch.Tensor:
+        """The arithmetic mode, 3-channel images and a pair table inside [0, NI) -> the pair table as int32 [P,2]."""
+        if hd.lib.imcui_hip_get_precision(hd.h) != 1:  # imcui_hip_dust3r_forward exists in the 3 x f16 split arithmetic only
+            raise ImcuiHipError("DUSt3R / MASt3R run in the library's default arithmetic (imcui_hip_set_precision(h, 1)): the exact-f32 matrix "
+                                "mode has no ViT kernels (for an exact-f32 nearest-neighbour search set conf['matcher_arithmetic'] = 'fp32')")
+        if any(c != 3 for c in channels):
+            raise ImcuiHipError("DUSt3R expects 3-channel images")
+        pairs = torch.as_tensor(pairs, dtype=torch.int32).reshape(-1, 2)
+        if int(pairs.min()) < 0 or int(pairs.max()) >= NI:
+            raise ImcuiHipError(f"DUSt3R pair table refers to images outside [0, {NI})")
+        return pairs
 
     def forward(self, packed, cfg, images, pairs, dump=False, arith=0):
         """images [NI,3,H,W] in [0,1] (H, W multiples of 16), pairs [P,2] int (view-1 image, view-2 image) ->
@@ -813,17 +815,9 @@ class DUSt3RHIP:
         dev = images.device
         hd = get_handle(dev)
         lib = hd.lib
-        if lib.imcui_hip_get_precision(hd.h) != 1:  # imcui_hip_dust3r_forward exists in the 3 x f16 split arithmetic only
-            raise ImcuiHipError("DUSt3R / MASt3R run in the library's default arithmetic (imcui_hip_set_precision(h, 1)): the exact-f32 matrix "
-                                "mode has no ViT kernels (for an exact-f32 nearest-neighbour search set conf['matcher_arithmetic'] = 'fp32')")
         images = images.contiguous().float()
         NI, Cc, H, W = images.shape
-        if Cc != 3:
-            raise ImcuiHipError("DUSt3R expects 3-channel images")
-        pairs = torch.as_tensor(pairs, dtype=torch.int32).reshape(-1, 2)
-        if int(pairs.min()) < 0 or int(pairs.max()) >= NI:
-            raise ImcuiHipError(f"DUSt3R pair table refers to images outside [0, {NI})")
-        pairs = pairs.to(dev).contiguous()
+        pairs = self._check_inputs(hd, [Cc], pairs, NI).to(dev).contiguous()
         P = pairs.shape[0]
         c4 = _dust3r_c5(cfg)
         dd = c4[4]
@@ -833,15 +827,12 @@ class DUSt3RHIP:
         dconf = torch.empty((2, P, H, W), dtype=torch.float32, device=dev) if dd else None
         nd = lib.imcui_hip_dust3r_dump_floats(*c4, NI, P, H, W) if dump else 0
         dbuf = torch.zeros((nd,), dtype=torch.float32, device=dev) if dump else None
-        with self._lock:
-            nbytes = lib.imcui_hip_dust3r_workspace_bytes(*c4, NI, P, H, W)
-            if nbytes == 0:
-                raise ImcuiHipError(f"DUSt3R: unsupported sizes ({NI} images of {W}x{H}, {P} pairs; multiples of 16)")
-            ws = self._ws.get(nbytes, dev)
-            with torch.cuda.device(dev):
-                rc = lib.imcui_hip_dust3r_forward(hd.h, *c4, _ptr(packed), packed.numel(), _ptr(images), NI, H, W, _ptr(pairs), P, int(arith), _ptr(pts), _ptr(conf),
-                                                  _ptr(desc), _ptr(dconf), _ptr(dbuf), nd, _ptr(ws), ws.numel(), _stream_ptr())  # fmt: skip
-                hd.check(rc, "imcui_hip_dust3r_forward")
+        nbytes = lib.imcui_hip_dust3r_workspace_bytes(*c4, NI, P, H, W)
+        if nbytes == 0:
+            raise ImcuiHipError(f"DUSt3R: unsupported sizes ({NI} images of {W}x{H}, {P} pairs; multiples of 16)")
+        with self._ws.use(nbytes, dev) as ws:
+            hd.launch(lib.imcui_hip_dust3r_forward, *c4, _ptr(packed), packed.numel(), _ptr(images), NI, H, W, _ptr(pairs), P, int(arith), _ptr(pts), _ptr(conf),
+                      _ptr(desc), _ptr(dconf), _ptr(dbuf), nd, _ptr(ws), ws.numel())  # fmt: skip
         self.last_dump = dbuf
         out = {"pts3d": pts, "conf": conf}
         if dd:
@@ -853,21 +844,13 @@ class DUSt3RHIP:
         [1,3,H_i,W_i]) tensors in [0,1], every size a multiple of 16, at most 4 distinct sizes; pairs [P,2] ->
         {"pts3d": [view][pair] -> [H,W,3], "conf": [view][pair] -> [H,W]} (+ "desc" / "desc_conf" for a MASt3R network) as nested
         lists of views into ONE ragged device buffer per output: the map of (view v, pair p) has the size of image pairs[p][v]."""
-        import ctypes as C
-
         imgs = [im.reshape(im.shape[-3:]).contiguous().float() for im in images]
         dev = imgs[0].device
         hd = get_handle(dev)
         lib = hd.lib
-        if lib.imcui_hip_get_precision(hd.h) != 1:
-            raise ImcuiHipError("DUSt3R / MASt3R run in the library's default arithmetic (imcui_hip_set_precision(h, 1))")
         NI = len(imgs)
-        if any(im.shape[0] != 3 for im in imgs):
-            raise ImcuiHipError("DUSt3R expects 3-channel images")
+        ptab = self._check_inputs(hd, [im.shape[0] for im in imgs], pairs, NI).cpu().contiguous()
         sizes = [(int(im.shape[1]), int(im.shape[2])) for im in imgs]
-        ptab = torch.as_tensor(pairs, dtype=torch.int32).reshape(-1, 2).cpu().contiguous()
-        if int(ptab.min()) < 0 or int(ptab.max()) >= NI:
-            raise ImcuiHipError(f"DUSt3R pair table refers to images outside [0, {NI})")
         P = ptab.shape[0]
         flat = torch.cat([im.reshape(-1) for im in imgs])
         pairs_dev = ptab.to(dev)
@@ -885,15 +868,12 @@ class DUSt3RHIP:
         one_size = len(set(sizes)) == 1
         nd = (lib.imcui_hip_dust3r_dump_floats(*c4, NI, P, *sizes[0]) if one_size else lib.imcui_hip_dust3r_token_dump_floats(*c4, NI, sz, P)) if dump else 0
         dbuf = torch.zeros((nd,), dtype=torch.float32, device=dev) if dump else None
-        with self._lock:
-            nbytes = lib.imcui_hip_dust3r_workspace_bytes_sizes(*c4, NI, sz, P)
-            if nbytes == 0:
-                raise ImcuiHipError(f"DUSt3R: unsupported sizes {sizes} (multiples of 16, 32 .. 4096)")
-            ws = self._ws.get(nbytes, dev)
-            with torch.cuda.device(dev):
-                rc = lib.imcui_hip_dust3r_forward_sizes(hd.h, *c4, _ptr(packed), packed.numel(), _ptr(flat), NI, sz, ph, _ptr(pairs_dev), P, int(arith), _ptr(pts), _ptr(conf),
-                                                        _ptr(desc), _ptr(dconf), offs, _ptr(dbuf), nd, _ptr(ws), ws.numel(), _stream_ptr())  # fmt: skip
-                hd.check(rc, "imcui_hip_dust3r_forward_sizes")
+        nbytes = lib.imcui_hip_dust3r_workspace_bytes_sizes(*c4, NI, sz, P)
+        if nbytes == 0:
+            raise ImcuiHipError(f"DUSt3R: unsupported sizes {sizes} (multiples of 16, 32 .. 4096)")
+        with self._ws.use(nbytes, dev) as ws:
+            hd.launch(lib.imcui_hip_dust3r_forward_sizes, *c4, _ptr(packed), packed.numel(), _ptr(flat), NI, sz, ph, _ptr(pairs_dev), P, int(arith), _ptr(pts),
+                      _ptr(conf), _ptr(desc), _ptr(dconf), offs, _ptr(dbuf), nd, _ptr(ws), ws.numel())  # fmt: skip
         assert offs[2 * P] == total
         self.last_dump = dbuf
 
@@ -927,17 +907,12 @@ def conv_gemm_f32(x_nhwc, w_oihw, bias, resid=None, stride=1, act=0):
     x_nhwc = x_nhwc.contiguous().float()
     if resid is not None:
         resid = resid.contiguous().float()
-    with torch.cuda.device(x_nhwc.device):
-        hd.check(
-            hd.lib.imcui_hip_conv_gemm_f32(hd.h, _ptr(x_nhwc), _ptr(wd), _ptr(bd), _ptr(resid), _ptr(out), B, H, W, Cin, Cout, ks, stride, act, _stream_ptr()),
-            "conv_gemm",
-        )
+    hd.launch(hd.lib.imcui_hip_conv_gemm_f32, _ptr(x_nhwc), _ptr(wd), _ptr(bd), _ptr(resid), _ptr(out), B, H, W, Cin, Cout, ks, stride, act)
     return out
 
 
 # ------------------------------------------------------------------ mutual NN
 _nn_ws = _Workspace()
-_nn_lock = threading.Lock()
 
 
 def mutual_nn(desc0_nd: torch.Tensor, desc1_md: torch.Tensor, ratio_threshold=None, distance_threshold=None,
@@ -953,15 +928,10 @@ def mutual_nn(desc0_nd: torch.Tensor, desc1_md: torch.Tensor, ratio_threshold=No
     s0 = torch.empty((B, N), dtype=torch.float32, device=dev)
     if D % 32:
         raise ImcuiHipError(f"descriptor dim {D} must be a multiple of 32")
-    with _nn_lock:
-        ws = _nn_ws.get(lib.imcui_hip_mutual_nn_workspace_bytes_d(hd.h, B, N, M, D), dev)  # (no similarity matrix for D = 64 / 128 / 256 or the split arithmetic)
-        with torch.cuda.device(dev):
-            rc = lib.imcui_hip_mutual_nn(
-                hd.h, _ptr(desc0_nd), _ptr(desc1_md), B, N, M, D, float(ratio_threshold or 0.0),
-                float(distance_threshold or 0.0), int(bool(do_mutual_check)), _ptr(m0), _ptr(s0), _ptr(ws), ws.numel(),
-                _stream_ptr(),
-            )  # fmt: skip
-            hd.check(rc, "imcui_hip_mutual_nn")
+    # (no similarity matrix for D = 64 / 128 / 256 or the split arithmetic)
+    with _nn_ws.use(lib.imcui_hip_mutual_nn_workspace_bytes_d(hd.h, B, N, M, D), dev) as ws:
+        hd.launch(lib.imcui_hip_mutual_nn, _ptr(desc0_nd), _ptr(desc1_md), B, N, M, D, float(ratio_threshold or 0.0),
+                  float(distance_threshold or 0.0), int(bool(do_mutual_check)), _ptr(m0), _ptr(s0), _ptr(ws), ws.numel())  # fmt: skip
     return m0, s0
 
 
@@ -978,14 +948,9 @@ def mutual_nn_dn(desc0_dn: torch.Tensor, desc1_dm: torch.Tensor, ratio_threshold
     s0 = torch.empty((B, N), dtype=torch.float32, device=dev)
     if D % 32:
         raise ImcuiHipError(f"descriptor dim {D} must be a multiple of 32")
-    with _nn_lock:
-        ws = _nn_ws.get(lib.imcui_hip_mutual_nn_dn_workspace_bytes_for(hd.h, B, N, M, D), dev)
-        with torch.cuda.device(dev):
-            rc = lib.imcui_hip_mutual_nn_dn(
-                hd.h, _ptr(desc0_dn), _ptr(desc1_dm), B, N, M, D, float(ratio_threshold or 0.0), float(distance_threshold or 0.0),
-                int(bool(do_mutual_check)), _ptr(m0), _ptr(s0), _ptr(ws), ws.numel(), _stream_ptr(),
-            )  # fmt: skip
-            hd.check(rc, "imcui_hip_mutual_nn_dn")
+    with _nn_ws.use(lib.imcui_hip_mutual_nn_dn_workspace_bytes_for(hd.h, B, N, M, D), dev) as ws:
+        hd.launch(lib.imcui_hip_mutual_nn_dn, _ptr(desc0_dn), _ptr(desc1_dm), B, N, M, D, float(ratio_threshold or 0.0), float(distance_threshold or 0.0),
+                  int(bool(do_mutual_check)), _ptr(m0), _ptr(s0), _ptr(ws), ws.numel())  # fmt: skip
     return m0, s0
 
 
@@ -1003,13 +968,10 @@ def nn_argmax(queries: torch.Tensor, db: torch.Tensor, return_best: bool = False
     best = torch.empty((Q,), dtype=torch.float32, device=dev) if return_best else None
     if Q == 0:
         return (idx.long(), best) if return_best else idx.long()
-    with _nn_lock:
-        fn_ws, fn = ((lib.imcui_hip_nn_argmax_split_workspace_bytes, lib.imcui_hip_nn_argmax_split_f32) if split else
-                     (lib.imcui_hip_nn_argmax_workspace_bytes, lib.imcui_hip_nn_argmax_f32))
-        ws = _nn_ws.get(fn_ws(Q, N), dev)
-        with torch.cuda.device(dev):
-            rc = fn(hd.h, _ptr(queries), _ptr(db), Q, N, D, _ptr(idx), _ptr(best), _ptr(ws), ws.numel(), _stream_ptr())
-            hd.check(rc, "imcui_hip_nn_argmax_f32")
+    fn_ws, fn = ((lib.imcui_hip_nn_argmax_split_workspace_bytes, lib.imcui_hip_nn_argmax_split_f32) if split else
+                 (lib.imcui_hip_nn_argmax_workspace_bytes, lib.imcui_hip_nn_argmax_f32))
+    with _nn_ws.use(fn_ws(Q, N), dev) as ws:
+        hd.launch(fn, _ptr(queries), _ptr(db), Q, N, D, _ptr(idx), _ptr(best), _ptr(ws), ws.numel())
     return (idx.long(), best) if return_best else idx.long()
 
 
@@ -1023,12 +985,9 @@ def dual_softmax(desc0: torch.Tensor, desc1: torch.Tensor, threshold: float = 0.
     M = desc1.shape[2]
     m0 = torch.empty((B, N), dtype=torch.int32, device=dev)
     s0 = torch.empty((B, N), dtype=torch.float32, device=dev)
-    with _nn_lock:
-        ws = _nn_ws.get(lib.imcui_hip_dual_softmax_workspace_bytes(B, C, N, M), dev)
-        with torch.cuda.device(dev):
-            rc = lib.imcui_hip_dual_softmax(hd.h, _ptr(desc0), _ptr(desc1), B, C, N, M, float(threshold), float(inv_temperature),
-                                            int(bool(normalize)), _ptr(m0), _ptr(s0), _ptr(ws), ws.numel(), _stream_ptr())  # fmt: skip
-            hd.check(rc, "imcui_hip_dual_softmax")
+    with _nn_ws.use(lib.imcui_hip_dual_softmax_workspace_bytes(B, C, N, M), dev) as ws:
+        hd.launch(lib.imcui_hip_dual_softmax, _ptr(desc0), _ptr(desc1), B, C, N, M, float(threshold), float(inv_temperature),
+                  int(bool(normalize)), _ptr(m0), _ptr(s0), _ptr(ws), ws.numel())  # fmt: skip
     return m0, s0
 
 
@@ -1036,7 +995,7 @@ def dual_softmax(desc0: torch.Tensor, desc1: torch.Tensor, threshold: float = 0.
 def set_precision(device: torch.device, mode: int):
     """0 = exact f32 MFMA, 1 = 3 x f16 split MFMA (default; ~fp32 accuracy at ~5x the matrix rate)."""
     hd = get_handle(device)
-    hd.check(hd.lib.imcui_hip_set_precision(hd.h, int(mode)), "set_precision")
+    hd.call(hd.lib.imcui_hip_set_precision, int(mode))
 
 
 def get_precision(device: torch.device) -> int:
@@ -1054,8 +1013,8 @@ def set_option(device: torch.device, name: str, value: int) -> int:
     the previous value.  The IMCUI_* environment variables of the same names are only read when the handle is created."""
     hd = get_handle(device)
     old = C.c_int(0)
-    hd.check(hd.lib.imcui_hip_get_option(hd.h, name.encode(), C.byref(old)), "get_option")
-    hd.check(hd.lib.imcui_hip_set_option(hd.h, name.encode(), int(value)), "set_option")
+    hd.call(hd.lib.imcui_hip_get_option, name.encode(), C.byref(old))
+    hd.call(hd.lib.imcui_hip_set_option, name.encode(), int(value))
     return old.value
 
 
@@ -1063,7 +1022,7 @@ def get_option(device: torch.device, name: str) -> int:
     """Current value of a routing switch (imcui_hip_get_option)."""
     hd = get_handle(device)
     val = C.c_int(0)
-    hd.check(hd.lib.imcui_hip_get_option(hd.h, name.encode(), C.byref(val)), "get_option")
+    hd.call(hd.lib.imcui_hip_get_option, name.encode(), C.byref(val))
     return val.value
 
 
@@ -1089,14 +1048,14 @@ KERNEL_CLASSES = {"attention": 0, "conv3x3": 1, "gemm": 2}
 
 def profile_enable(device: torch.device, on: bool = True):
     hd = get_handle(device)
-    hd.check(hd.lib.imcui_hip_profile_enable(hd.h, int(on)), "profile_enable")
+    hd.call(hd.lib.imcui_hip_profile_enable, int(on))
 
 
 def profile_read(device: torch.device, kernel_class: str):
     """(total kernel ms, launches) of one class since the last read; HIP events on the launch stream."""
     hd = get_handle(device)
     tot, cnt = C.c_double(0.0), C.c_int(0)
-    hd.check(hd.lib.imcui_hip_profile_read(hd.h, KERNEL_CLASSES[kernel_class], C.byref(tot), C.byref(cnt)), "profile_read")
+    hd.call(hd.lib.imcui_hip_profile_read, KERNEL_CLASSES[kernel_class], C.byref(tot), C.byref(cnt))
     return tot.value, cnt.value
 
 
@@ -1107,8 +1066,7 @@ def linear_f32(a: torch.Tensor, w: torch.Tensor, bias: torch.Tensor | None, relu
     M, K = a.shape
     N = w.shape[0]
     c = torch.empty((M, N), dtype=torch.float32, device=a.device)
-    with torch.cuda.device(a.device):
-        hd.check(hd.lib.imcui_hip_linear_f32(hd.h, _ptr(a), _ptr(w), _ptr(bias), _ptr(c), M, N, K, int(relu), _stream_ptr()), "linear")
+    hd.launch(hd.lib.imcui_hip_linear_f32, _ptr(a), _ptr(w), _ptr(bias), _ptr(c), M, N, K, int(relu))
     return c
 
 
@@ -1121,8 +1079,7 @@ def rgb_to_gray(rgb_u8: torch.Tensor) -> torch.Tensor:
     rgb_u8 = rgb_u8.contiguous()
     B, H, W, _ = rgb_u8.shape
     out = torch.empty((B, 1, H, W), dtype=torch.float32, device=rgb_u8.device)
-    with torch.cuda.device(rgb_u8.device):
-        hd.check(hd.lib.imcui_hip_rgb_to_gray_f32(hd.h, _ptr(rgb_u8), _ptr(out), B, H, W, _stream_ptr()), "rgb_to_gray")
+    hd.launch(hd.lib.imcui_hip_rgb_to_gray_f32, _ptr(rgb_u8), _ptr(out), B, H, W)
     return out
 
 
@@ -1160,9 +1117,7 @@ def preprocess_area(img_u8: torch.Tensor, size) -> torch.Tensor:
     tabs = [None] * 6
     if not (W % ow == 0 and H % oh == 0) and ow <= W and oh <= H:
         tabs = [*_area_table(W, ow, img_u8.device), *_area_table(H, oh, img_u8.device)]
-    with torch.cuda.device(img_u8.device):
-        hd.check(hd.lib.imcui_hip_preprocess_area_f32(hd.h, _ptr(img_u8), B, H, W, Cc, *[_ptr(t) for t in tabs], _ptr(out), oh, ow, _stream_ptr()),
-                 "preprocess_area")
+    hd.launch(hd.lib.imcui_hip_preprocess_area_f32, _ptr(img_u8), B, H, W, Cc, *[_ptr(t) for t in tabs], _ptr(out), oh, ow)
     return out
 
 
@@ -1209,9 +1164,7 @@ def preprocess_linear(img_u8: torch.Tensor, size) -> torch.Tensor:
         _linear_tables[key] = tuple(torch.from_numpy(a).to(img_u8.device) for a in (*linear_table_host(W, ow, True), *linear_table_host(H, oh, False)))
     tabs = _linear_tables[key]
     out = torch.empty((B, 1, oh, ow), dtype=torch.float32, device=img_u8.device)
-    with torch.cuda.device(img_u8.device):
-        hd.check(hd.lib.imcui_hip_preprocess_linear_f32(hd.h, _ptr(img_u8), B, H, W, Cc, *[_ptr(t) for t in tabs], _ptr(out), oh, ow, _stream_ptr()),
-                 "preprocess_linear")
+    hd.launch(hd.lib.imcui_hip_preprocess_linear_f32, _ptr(img_u8), B, H, W, Cc, *[_ptr(t) for t in tabs], _ptr(out), oh, ow)
     return out
 
 
@@ -1232,16 +1185,13 @@ def resize_aa(image: torch.Tensor, size_hw) -> torch.Tensor:
         _aa_tables[key] = (tuple(torch.from_numpy(a).to(image.device) for a in xt), xt[2].shape[1], tuple(torch.from_numpy(a).to(image.device) for a in yt), yt[2].shape[1])
     xt, kx, yt, ky = _aa_tables[key]
     out = torch.empty((*src.shape[:-2], oh, ow), dtype=torch.float32, device=image.device)
-    with torch.cuda.device(image.device):
-        hd.check(hd.lib.imcui_hip_resize_aa_f32(hd.h, _ptr(src), planes, H, W, _ptr(xt[0]), _ptr(xt[1]), _ptr(xt[2]), kx, _ptr(yt[0]), _ptr(yt[1]),
-                                                _ptr(yt[2]), ky, _ptr(out), oh, ow, _stream_ptr()), "resize_aa")
+    hd.launch(hd.lib.imcui_hip_resize_aa_f32, _ptr(src), planes, H, W, _ptr(xt[0]), _ptr(xt[1]), _ptr(xt[2]), kx, _ptr(yt[0]), _ptr(yt[1]),
+              _ptr(yt[2]), ky, _ptr(out), oh, ow)  # fmt: skip
     return out
 
 
 def pack_linear_split(w: torch.Tensor):
     """Host: nn.Linear weight [N, K] -> (hi, lo) uint16 fragment-major planes and the inverse scale 2^-e."""
-    from .lib_loader import load_library
-
     lib = load_library()
     wh = _as_f32_host(w)
     N, K = wh.shape
@@ -1266,9 +1216,7 @@ def linear_split_f32(a: torch.Tensor, w: torch.Tensor, bias: torch.Tensor | None
     dl = torch.from_numpy(lo.view(np.int16)).to(a.device)
     ds = torch.tensor([sc], dtype=torch.float32, device=a.device)
     c = torch.empty((M, N), dtype=torch.float32, device=a.device)
-    with torch.cuda.device(a.device):
-        hd.check(hd.lib.imcui_hip_linear_split_f32(hd.h, _ptr(a), _ptr(dh), _ptr(dl), _ptr(ds), _ptr(bias), _ptr(c), M, N, K, int(relu), _stream_ptr()),
-                 "linear_split")
+    hd.launch(hd.lib.imcui_hip_linear_split_f32, _ptr(a), _ptr(dh), _ptr(dl), _ptr(ds), _ptr(bias), _ptr(c), M, N, K, int(relu))
     return c
 
 
@@ -1276,14 +1224,14 @@ def set_range_check(device, enable: bool = True) -> None:
     """Debugging aid: scan the f32 activation operand of every split-mode GEMM / convolution / FFN launch for values the f16
     split cannot carry (imcui_hip_set_range_check)."""
     hd = get_handle(torch.device(device))
-    hd.check(hd.lib.imcui_hip_set_range_check(hd.h, int(bool(enable))), "set_range_check")
+    hd.call(hd.lib.imcui_hip_set_range_check, int(bool(enable)))
 
 
 def range_status(device) -> int:
     """Accumulated range-check word since the last read (synchronises): bit 0 = |x| > 65504 seen, bit 1 = NaN / Inf seen."""
     hd = get_handle(torch.device(device))
     st = C.c_int(0)
-    hd.check(hd.lib.imcui_hip_get_range_status(hd.h, C.byref(st)), "get_range_status")
+    hd.call(hd.lib.imcui_hip_get_range_status, C.byref(st))
     return int(st.value)
 
 
@@ -1303,16 +1251,13 @@ def qkv_split_f32(x: torch.Tensor, w: torch.Tensor, bias, cos, sin, cnt: torch.T
     k = torch.zeros((2, nseq, 4, R, 64), dtype=torch.int16, device=dev)
     v = torch.zeros((2, nseq, 4, 64, R), dtype=torch.int16, device=dev)
     cnt = cnt.to(torch.int32).contiguous()
-    with torch.cuda.device(dev):
-        hd.check(hd.lib.imcui_hip_qkv_split_f32(hd.h, _ptr(x), _ptr(dh), _ptr(dl), _ptr(ds), _ptr(bias), _ptr(cos), _ptr(sin), _ptr(cnt), nseq, R,
-                                                float(alpha), int(cross), _ptr(q), _ptr(k), _ptr(v), _stream_ptr()), "qkv_split")
+    hd.launch(hd.lib.imcui_hip_qkv_split_f32, _ptr(x), _ptr(dh), _ptr(dl), _ptr(ds), _ptr(bias), _ptr(cos), _ptr(sin), _ptr(cnt), nseq, R,
+              float(alpha), int(cross), _ptr(q), _ptr(k), _ptr(v))  # fmt: skip
     return q, k, v
 
 
 def pack_ffn_w2(w2: torch.Tensor):
     """Host: ffn.3 weight [256, 512] -> planes in the K order of the fused FFN kernel, and the inverse scale."""
-    from .lib_loader import load_library
-
     lib = load_library()
     wh = _as_f32_host(w2)
     assert wh.shape == (256, 512)
@@ -1348,12 +1293,8 @@ class FusedFFN:
         x, ctx = x.contiguous().float(), ctx.contiguous().float()
         M = x.shape[0]
         out = torch.empty_like(x) if out is None else out
-        with torch.cuda.device(x.device):
-            hd.check(
-                hd.lib.imcui_hip_ffn_split_f32(hd.h, _ptr(x), _ptr(ctx), _ptr(self.w1h), _ptr(self.w1l), _ptr(self.s1), _ptr(self.b1), _ptr(self.gamma),
-                                               _ptr(self.beta), _ptr(self.w2h), _ptr(self.w2l), _ptr(self.s2), _ptr(self.b2), _ptr(out), M, self.act, _stream_ptr()),
-                "ffn_split",
-            )
+        hd.launch(hd.lib.imcui_hip_ffn_split_f32, _ptr(x), _ptr(ctx), _ptr(self.w1h), _ptr(self.w1l), _ptr(self.s1), _ptr(self.b1), _ptr(self.gamma),
+                  _ptr(self.beta), _ptr(self.w2h), _ptr(self.w2l), _ptr(self.s2), _ptr(self.b2), _ptr(out), M, self.act)  # fmt: skip
         return out
 
 
@@ -1375,21 +1316,13 @@ def conv3x3_f32(x_nhwc: torch.Tensor, w_oihw: torch.Tensor, bias: torch.Tensor, 
         dh = torch.from_numpy(hi.view(np.int16)).to(x_nhwc.device)
         dl = torch.from_numpy(lo.view(np.int16)).to(x_nhwc.device)
         ds = torch.tensor([sc], dtype=torch.float32, device=x_nhwc.device)
-        with torch.cuda.device(x_nhwc.device):
-            hd.check(
-                lib.imcui_hip_conv3x3_split_f32(hd.h, _ptr(x_nhwc), _ptr(dh), _ptr(dl), _ptr(ds), _ptr(bias), _ptr(out), B, H, W, Cin, Cout, int(relu), int(pool), _stream_ptr()),
-                "conv3x3_split",
-            )
+        hd.launch(lib.imcui_hip_conv3x3_split_f32, _ptr(x_nhwc), _ptr(dh), _ptr(dl), _ptr(ds), _ptr(bias), _ptr(out), B, H, W, Cin, Cout, int(relu), int(pool))
         return out
     packed = np.zeros(Cout * Cin * 9, dtype=np.float32)
     if lib.imcui_hip_conv3x3_pack(wh.ctypes.data, Cout, Cin, packed.ctypes.data) != 0:
         raise ImcuiHipError("conv3x3_pack failed")
     wp = torch.from_numpy(packed).to(x_nhwc.device)
-    with torch.cuda.device(x_nhwc.device):
-        hd.check(
-            lib.imcui_hip_conv3x3_f32(hd.h, _ptr(x_nhwc), _ptr(wp), _ptr(bias), _ptr(out), B, H, W, Cin, Cout, int(relu), int(pool), _stream_ptr()),
-            "conv3x3",
-        )
+    hd.launch(lib.imcui_hip_conv3x3_f32, _ptr(x_nhwc), _ptr(wp), _ptr(bias), _ptr(out), B, H, W, Cin, Cout, int(relu), int(pool))
     return out
 
 
@@ -1415,11 +1348,7 @@ def attention_f32(q, k, v, cnt, cross=False, log2_domain=False):
         q, k, v = q.contiguous().float(), k.contiguous().float(), v.contiguous().float()
     o = torch.zeros((S * R, Hh * 64), dtype=torch.float32, device=q.device)
     cnt = cnt.to(torch.int32).contiguous()
-    with torch.cuda.device(q.device):
-        hd.check(
-            hd.lib.imcui_hip_attention_f32(hd.h, _ptr(q), _ptr(k), _ptr(v), _ptr(o), _ptr(cnt), S, Hh, R, int(cross), int(bool(log2_domain)), _stream_ptr()),
-            "attention",
-        )
+    hd.launch(hd.lib.imcui_hip_attention_f32, _ptr(q), _ptr(k), _ptr(v), _ptr(o), _ptr(cnt), S, Hh, R, int(cross), int(bool(log2_domain)))
     return o
 
 
@@ -1435,8 +1364,7 @@ def attention_mx_f32(q, k, v, cnt, cross=False):
     cnt = cnt.to(torch.int32).contiguous()
     nbytes = hd.lib.imcui_hip_attention_mx_scratch_bytes(S, Hh, R)
     scratch = torch.empty(nbytes, dtype=torch.uint8, device=q.device)
-    with torch.cuda.device(q.device):
-        hd.check(hd.lib.imcui_hip_attention_mx_f32(hd.h, _ptr(q), _ptr(k), _ptr(v), _ptr(o), _ptr(cnt), S, Hh, R, int(cross), _ptr(scratch), nbytes, _stream_ptr()), "attention (variant 9)")
+    hd.launch(hd.lib.imcui_hip_attention_mx_f32, _ptr(q), _ptr(k), _ptr(v), _ptr(o), _ptr(cnt), S, Hh, R, int(cross), _ptr(scratch), nbytes)
     return o
 
 
@@ -1445,6 +1373,5 @@ def simple_nms(scores: torch.Tensor, radius: int) -> torch.Tensor:
     scores = scores.contiguous().float()
     B, H, W = scores.shape
     out = torch.empty_like(scores)
-    with torch.cuda.device(scores.device):
-        hd.check(hd.lib.imcui_hip_simple_nms(hd.h, _ptr(scores), _ptr(out), B, H, W, int(radius), _stream_ptr()), "simple_nms")
+    hd.launch(hd.lib.imcui_hip_simple_nms, _ptr(scores), _ptr(out), B, H, W, int(radius))
     return out

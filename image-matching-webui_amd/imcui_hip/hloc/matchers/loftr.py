@@ -85,7 +85,9 @@ class LoFTR(BaseModel):
         self._impl = backend.LoFTRHIP()
 
     def forward_batched(self, image0: torch.Tensor, image1: torch.Tensor) -> dict:
-        """kornia LoFTR.forward(image0, image1) on a batch: fixed-capacity outputs, no host sync."""
+        """kornia LoFTR.forward(image0, image1) on a batch: fixed-capacity outputs.  Reads the coarse match count back to the host (one
+        synchronisation) to choose the fine stage's path, unless the routing switch loftr_fine_sparse is 0; under a HIP-graph capture it
+        takes the dense path and does not synchronise (backend.LoFTRHIP.forward)."""
         return self._impl.forward(self.packed, image0, image1, self.match_threshold(), self.temp_bug_fix)
 
     def match_threshold(self) -> float:

@@ -69,10 +69,7 @@ def reconstruct(info, coef: torch.Tensor, qt: torch.Tensor, gray: bool, device) 
     out = torch.empty((H, W) if gray else (H, W, 3), dtype=torch.uint8, device=device)
     nbytes = lib.imcui_hip_jpeg_workspace_bytes(info, int(gray))
     ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
-    with torch.cuda.device(device):
-        rc = lib.imcui_hip_jpeg_reconstruct(hd.h, backend._ptr(coef_d), backend._ptr(qt_d), info, int(gray), backend._ptr(out), backend._ptr(ws), nbytes,
-                                            backend._stream_ptr())  # fmt: skip
-        hd.check(rc, "imcui_hip_jpeg_reconstruct")
+    hd.launch(lib.imcui_hip_jpeg_reconstruct, backend._ptr(coef_d), backend._ptr(qt_d), info, int(gray), backend._ptr(out), backend._ptr(ws), nbytes)
     return out
 
 
@@ -85,8 +82,7 @@ def apply_orientation(img: torch.Tensor, orientation: int) -> torch.Tensor:
     Cc = img.shape[2] if img.dim() == 3 else 1
     shape = ((W, H) if orientation >= 5 else (H, W)) + ((Cc,) if img.dim() == 3 else ())
     out = torch.empty(shape, dtype=torch.uint8, device=img.device)
-    with torch.cuda.device(img.device):
-        hd.check(hd.lib.imcui_hip_orient_u8(hd.h, backend._ptr(img.contiguous()), H, W, Cc, int(orientation), backend._ptr(out), backend._stream_ptr()), "imcui_hip_orient_u8")
+    hd.launch(hd.lib.imcui_hip_orient_u8, backend._ptr(img.contiguous()), H, W, Cc, int(orientation), backend._ptr(out))
     return out
 
 
@@ -182,10 +178,8 @@ class JpegDecoder:
             cy = coef_d.data_ptr()
             ccb = cy + 2 * m * ny if chroma else None
             ccr = cy + 2 * m * (ny + ncb) if chroma else None
-            with torch.cuda.device(dev):
-                rc = lib.imcui_hip_jpeg_reconstruct_batch(hd.h, cy, ccb, ccr, backend._ptr(qsel.contiguous()), info, m, int(gray), backend._ptr(out), backend._ptr(ws),
-                                                          nbytes, backend._stream_ptr())  # fmt: skip
-                hd.check(rc, "imcui_hip_jpeg_reconstruct_batch")
+            hd.launch(lib.imcui_hip_jpeg_reconstruct_batch, cy, ccb, ccr, backend._ptr(qsel.contiguous()), info, m, int(gray), backend._ptr(out), backend._ptr(ws),
+                      nbytes)  # fmt: skip
             for k, i in enumerate(idx):
                 results[i] = apply_orientation(out[k], info_of[i]) if status[i] == 0 else JpegUnsupported(
                     f"imcui_hip_jpeg_entropy_decode: status {status[i]} ({'unsupported JPEG variant' if status[i] == -4 else 'damaged bit stream'})")

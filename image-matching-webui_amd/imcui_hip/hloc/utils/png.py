@@ -118,10 +118,8 @@ class PngDecoder:
         if g != m:
             pal = staged[pal_off : pal_off + 768 * m].view(m, 768)[torch.tensor(good, device=dev)].contiguous()
             pal_ptr = pal.data_ptr()
-        with torch.cuda.device(dev):
-            rc = lib.imcui_hip_png_reconstruct_batch(hd.h, backend._ptr(staged), (C.c_size_t * g)(*[raw_off[k] for k in good]), info_flat, pal_ptr, g, backend._ptr(out),
-                                                     (C.c_size_t * g)(*out_off), backend._ptr(ws), nbytes, backend._stream_ptr())  # fmt: skip
-            hd.check(rc, "imcui_hip_png_reconstruct_batch")
+        hd.launch(lib.imcui_hip_png_reconstruct_batch, backend._ptr(staged), (C.c_size_t * g)(*[raw_off[k] for k in good]), info_flat, pal_ptr, g,
+                  backend._ptr(out), (C.c_size_t * g)(*out_off), backend._ptr(ws), nbytes)  # fmt: skip
         for q, k in enumerate(good):
             i = live[k]
             W, H, ch = infos[i][0], infos[i][1], infos[i][4]

@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import torch
 
+from . import backend
 from .hloc.extractors.superpoint import SuperPoint
 from .hloc.matchers.lightglue import LightGlue
 
@@ -88,16 +89,18 @@ class GraphedPipeline:
     def __init__(self, pipe: torch.nn.Module, image0: torch.Tensor, image1: torch.Tensor, warmup: int = 3):
         self.pipe = pipe
         self.image0, self.image1 = image0.clone(), image1.clone()
+        self.workspaces = {}  # the graph's own scratch (backend.workspace_owner), freed with it
         side = torch.cuda.Stream(device=image0.device)
         side.wait_stream(torch.cuda.current_stream(image0.device))
-        with torch.cuda.stream(side):  # warm-up off the capture: workspaces reach their final size
-            for _ in range(warmup):
-                pipe(self.image0, self.image1)
-        torch.cuda.current_stream(image0.device).wait_stream(side)
-        torch.cuda.synchronize(image0.device)
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
-            self.out = pipe(self.image0, self.image1)
+        with backend.workspace_owner(self.workspaces):
+            with torch.cuda.stream(side):  # warm-up off the capture: workspaces reach their final size
+                for _ in range(warmup):
+                    pipe(self.image0, self.image1)
+            torch.cuda.current_stream(image0.device).wait_stream(side)
+            torch.cuda.synchronize(image0.device)
+            self.graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.graph):
+                self.out = pipe(self.image0, self.image1)
 
     @torch.no_grad()
     def __call__(self, image0: torch.Tensor, image1: torch.Tensor) -> dict:
@@ -120,21 +123,18 @@ class GraphedCall:
         dev = inputs[0].device
         self.fn = fn
         self.static_in = [t.clone() for t in inputs]
-        # The graph's OWN stream, for the warm-up and for the capture: the C ABI's scratch is one buffer per (device, stream)
-        # (`backend._Workspace`) and a buffer handed out during a capture is pinned, so every graph pins a workspace of its own, sized by its
-        # own warm-up -- a later graph of a larger capacity (LightGlue 2048 key-points after 1024, a bigger SuperPoint image) no longer asks
-        # a pinned buffer to grow (torch.cuda.graph's default capture stream is shared by all graphs of the process), and the warm-up leaves no
-        # second buffer behind under a throw-away stream's key.  ADVICE round 5.
+        self.workspaces = {}  # warm-up and capture share scratch owned by this graph (backend.workspace_owner), freed with it
         self.stream = torch.cuda.Stream(device=dev)
         self.stream.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(self.stream):  # warm-up off the capture: workspaces reach their final size
-            for _ in range(warmup):
-                fn(*self.static_in)
-        torch.cuda.current_stream(dev).wait_stream(self.stream)
-        torch.cuda.synchronize(dev)
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph, stream=self.stream):
-            self.out = fn(*self.static_in)
+        with backend.workspace_owner(self.workspaces):
+            with torch.cuda.stream(self.stream):  # warm-up off the capture: workspaces reach their final size
+                for _ in range(warmup):
+                    fn(*self.static_in)
+            torch.cuda.current_stream(dev).wait_stream(self.stream)
+            torch.cuda.synchronize(dev)
+            self.graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.graph, stream=self.stream):
+                self.out = fn(*self.static_in)
 
     @torch.no_grad()
     def __call__(self, *inputs: torch.Tensor) -> dict:
