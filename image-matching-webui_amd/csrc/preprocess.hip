@@ -52,7 +52,7 @@ extern "C" int imcui_hip_area_table(int ssize, int dsize, int* start, int* index
 }
 
 __device__ __forceinline__ float pp_pixel(const unsigned char* p, int C) {
-    if (C == 1) return (float)p[0];
+    if (C == 1 || C == -3) return (float)p[0];
     // cv2.cvtColor(RGB2GRAY) on 8-bit pixels: (9798 R + 19235 G + 3735 B + 16384) >> 15
     return (float)((9798u * p[0] + 19235u * p[1] + 3735u * p[2] + 16384u) >> 15);
 }
@@ -61,31 +61,35 @@ __global__ __launch_bounds__(256) void pp_area_kernel(const unsigned char* __res
                                                       const int* __restrict__ xs, const int* __restrict__ xi,
                                                       const float* __restrict__ xw, const int* __restrict__ ys,
                                                       const int* __restrict__ yi, const float* __restrict__ yw,
-                                                      float* __restrict__ out, int h, int w, int fast_fx, int fast_fy) {
+                                                      float* __restrict__ out, int h, int w, int fast_fx, int fast_fy, int rgb) {
     const int dx = blockIdx.x * 64 + (threadIdx.x & 63);
     const int dy = blockIdx.y * 4 + (threadIdx.x >> 6);
-    const int b = blockIdx.z;
+    // rgb: blockIdx.z = image * 3 + channel, every pixel contributes that channel's byte and the output is planar [B, 3, h, w];
+    // otherwise blockIdx.z = image and the pixel is its gray value (pp_pixel)
+    const int b = rgb ? blockIdx.z / 3 : blockIdx.z;
     if (dx >= w || dy >= h) return;
-    const unsigned char* img = src + (size_t)b * H * W * C;
+    const unsigned char* img = src + (size_t)b * H * W * C + (rgb ? blockIdx.z % 3 : 0);
+    if (rgb) C = -3;  // pp_pixel: one byte of a 3-byte pixel
+    const int Cs = rgb ? 3 : C;  // bytes per pixel
     float acc = 0.0f;
     if (fast_fx > 0) {
         // integer factors: OpenCV's resizeAreaFast -- plain sum of the block, row-major, times float(1 / area)
         for (int ky = 0; ky < fast_fy; ++ky)
             for (int kx = 0; kx < fast_fx; ++kx)
-                acc = __fadd_rn(acc, pp_pixel(img + ((size_t)(dy * fast_fy + ky) * W + dx * fast_fx + kx) * C, C));
+                acc = __fadd_rn(acc, pp_pixel(img + ((size_t)(dy * fast_fy + ky) * W + dx * fast_fx + kx) * Cs, C));
         acc = __fmul_rn(acc, 1.0f / (float)(fast_fx * fast_fy));
     } else {
         const int x0 = xs[dx], x1 = xs[dx + 1];
         const int y0 = ys[dy], y1 = ys[dy + 1];
         for (int j = y0; j < y1; ++j) {
-            const unsigned char* row = img + (size_t)yi[j] * W * C;
-            float buf = __fmul_rn(pp_pixel(row + (size_t)xi[x0] * C, C), xw[x0]);
-            for (int k = x0 + 1; k < x1; ++k) buf = __fadd_rn(buf, __fmul_rn(pp_pixel(row + (size_t)xi[k] * C, C), xw[k]));
+            const unsigned char* row = img + (size_t)yi[j] * W * Cs;
+            float buf = __fmul_rn(pp_pixel(row + (size_t)xi[x0] * Cs, C), xw[x0]);
+            for (int k = x0 + 1; k < x1; ++k) buf = __fadd_rn(buf, __fmul_rn(pp_pixel(row + (size_t)xi[k] * Cs, C), xw[k]));
             const float t = __fmul_rn(buf, yw[j]);
             acc = (j == y0) ? t : __fadd_rn(acc, t);
         }
     }
-    out[((size_t)b * h + dy) * w + dx] = __fdiv_rn(acc, 255.0f);
+    out[((size_t)blockIdx.z * h + dy) * w + dx] = __fdiv_rn(acc, 255.0f);
 }
 
 extern "C" int imcui_hip_preprocess_area_f32(imcui_hip_t* h, const unsigned char* src, int B, int H, int W, int C,
@@ -100,7 +104,27 @@ extern "C" int imcui_hip_preprocess_area_f32(imcui_hip_t* h, const unsigned char
     if (!fast && (!xstart || !xindex || !xweight || !ystart || !yindex || !yweight))
         return imcui_set_err(h, IMCUI_ERR_ARG, "preprocess_area: decimation tables missing (imcui_hip_area_table)");
     hipLaunchKernelGGL(pp_area_kernel, dim3(cdiv(ow, 64), cdiv(oh, 4), B), dim3(256), 0, (hipStream_t)stream, src, H, W, C, xstart, xindex,
-                       xweight, ystart, yindex, yweight, out, oh, ow, fast ? W / ow : 0, fast ? H / oh : 0);
+                       xweight, ystart, yindex, yweight, out, oh, ow, fast ? W / ow : 0, fast ? H / oh : 0, 0);
+    IMCUI_CHECK_LAUNCH(h);
+    return IMCUI_OK;
+}
+
+// RGB mode (extractors that take colour, e.g. DISK: `grayscale: False`): uint8 [B,H,W,3] -> float32 -> INTER_AREA per channel -> / 255
+// -> planar [B,3,oh,ow] (imcui/hloc/extract_features.py:80-99: astype(float32), resize_image, transpose to CxHxW, / 255).  Same tables
+// and arithmetic as the gray path, applied to each channel's bytes; oh = H, ow = W is the plain conversion (a 1 x 1 block).
+extern "C" int imcui_hip_preprocess_area_rgb_f32(imcui_hip_t* h, const unsigned char* src, int B, int H, int W, const int* xstart, const int* xindex,
+                                                 const float* xweight, const int* ystart, const int* yindex, const float* yweight, float* out, int oh,
+                                                 int ow, void* stream) {
+    if (!h || !src || !out || B < 0 || H <= 0 || W <= 0 || oh <= 0 || ow <= 0)
+        return imcui_set_err(h, IMCUI_ERR_ARG, "preprocess_area_rgb: bad argument");
+    if (oh > H || ow > W)
+        return imcui_set_err(h, IMCUI_ERR_UNSUPPORTED, "preprocess_area_rgb: %dx%d -> %dx%d grows a side (the reference uses INTER_LINEAR there)", W, H, ow, oh);
+    if (B == 0) return IMCUI_OK;
+    const bool fast = (W % ow == 0) && (H % oh == 0);
+    if (!fast && (!xstart || !xindex || !xweight || !ystart || !yindex || !yweight))
+        return imcui_set_err(h, IMCUI_ERR_ARG, "preprocess_area_rgb: decimation tables missing (imcui_hip_area_table)");
+    hipLaunchKernelGGL(pp_area_kernel, dim3(cdiv(ow, 64), cdiv(oh, 4), B * 3), dim3(256), 0, (hipStream_t)stream, src, H, W, 3, xstart, xindex,
+                       xweight, ystart, yindex, yweight, out, oh, ow, fast ? W / ow : 0, fast ? H / oh : 0, 1);
     IMCUI_CHECK_LAUNCH(h);
     return IMCUI_OK;
 }

@@ -201,6 +201,100 @@ class SuperPointHIP:
         return out
 
 
+# ------------------------------------------------------------------ DISK
+def disk_tensor_names() -> list[str]:
+    lib = load_library()
+    return [lib.imcui_hip_disk_tensor_name(i).decode() for i in range(lib.imcui_hip_disk_num_tensors())]
+
+
+def disk_tensor_shapes() -> dict:
+    """kornia DISK's state-dict shapes (Unet(in_features=3, size=5, down=[16, 32, 64, 64, 64], up=[64, 64, 64, 129]))."""
+    blocks = [("unet.path_down.0.1", 3, 16), ("unet.path_down.1.1", 16, 32), ("unet.path_down.2.1", 32, 64), ("unet.path_down.3.1", 64, 64),
+              ("unet.path_down.4.1", 64, 64), ("unet.path_up.0.conv", 128, 64), ("unet.path_up.1.conv", 128, 64), ("unet.path_up.2.conv", 96, 64),
+              ("unet.path_up.3.conv", 80, 129)]  # fmt: skip
+    shapes = {}
+    for i, (name, cin, cout) in enumerate(blocks):
+        if i > 0:
+            shapes[f"{name}.1.weight"] = (cin,)
+        shapes[f"{name}.3.weight"] = (cout, cin, 5, 5)
+        shapes[f"{name}.3.bias"] = (cout,)
+    return shapes
+
+
+def pack_disk(state_dict: dict) -> torch.Tensor:
+    """kornia DISK state dict (the `["extractor"]` entry of a cvlab-epfl/disk checkpoint) -> packed float32 buffer (host).
+    Strict: every key consumed exactly once, every shape checked."""
+    lib = load_library()
+    names = disk_tensor_names()
+    shapes = disk_tensor_shapes()
+    missing = [n for n in names if n not in state_dict]
+    extra = sorted(set(state_dict) - set(names))
+    if missing or extra:
+        raise ImcuiHipError(f"DISK state dict does not match kornia's layout: missing {missing[:4]}, unexpected {extra[:4]}")
+    arrs = []
+    for n in names:
+        a = _as_f32_host(state_dict[n])
+        if a.shape != shapes[n]:
+            raise ImcuiHipError(f"DISK state dict: '{n}' has shape {a.shape}, expected {shapes[n]}")
+        arrs.append(a)
+    packed = np.zeros(lib.imcui_hip_disk_packed_floats(), dtype=np.float32)
+    tp = (C.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
+    rc = lib.imcui_hip_disk_pack_weights(tp, packed.ctypes.data)
+    if rc != 0:
+        raise ImcuiHipError(f"imcui_hip_disk_pack_weights failed ({rc})")
+    return torch.from_numpy(packed)
+
+
+def disk_check_args(image_shape, window: int, pad_if_not_divisible: bool) -> None:
+    """The refusals of kornia's DISK.forward / nms, raised before anything is launched."""
+    if len(image_shape) != 4 or image_shape[1] != 3:
+        raise ValueError(f"DISK expects an RGB image [B,3,H,W], got shape {tuple(image_shape)}")
+    if int(window) % 2 != 1:
+        raise ValueError(f"window_size has to be odd, got {window}")
+    H, W = image_shape[2:]
+    if not pad_if_not_divisible and (H % 16 or W % 16):
+        raise ValueError(f"Input image shape must be divisible by 16 (got {tuple(image_shape)}); set pad_if_not_divisible")
+
+
+class DiskHIP:
+    def __init__(self):
+        self._ws = _Workspace()
+
+    def forward(self, packed: torch.Tensor, image: torch.Tensor, conf: dict, want_heatmap: bool = False, kcap: int | None = None):
+        """image [B,3,H,W] float32 on the GPU -> fixed-stride outputs, no host synchronisation: keypoints [B,K,2] (row-major order),
+        scores [B,K], descriptors [B,K,128], num_keypoints [B] int32, status [1] int32 (bit 1: `kcap` too small), heatmap [B,H,W]
+        when asked.  K = max_keypoints, or the exact NMS bound when max_keypoints is None."""
+        window, pad = int(conf["nms_window_size"]), bool(conf["pad_if_not_divisible"])
+        disk_check_args(tuple(image.shape), window, pad)
+        hd = get_handle(image.device)
+        if packed.device != image.device:
+            raise ImcuiHipError("packed weights and image live on different devices")
+        lib = hd.lib
+        image = image.contiguous().float()
+        B, _, H, W = image.shape
+        maxk = conf.get("max_keypoints")
+        maxk = -1 if maxk is None or int(maxk) < 0 else int(maxk)
+        bound = lib.imcui_hip_disk_max_keypoints_bound(H, W, window)
+        if kcap is None:
+            kcap = bound if maxk < 0 else max(1, min(maxk, bound))
+        dev = image.device
+        kpts = torch.empty((B, kcap, 2), dtype=torch.float32, device=dev)
+        scores = torch.empty((B, kcap), dtype=torch.float32, device=dev)
+        desc = torch.empty((B, kcap, 128), dtype=torch.float32, device=dev)
+        nk = torch.empty((B,), dtype=torch.int32, device=dev)
+        status = torch.empty((1,), dtype=torch.int32, device=dev)
+        heat = torch.empty((B, H, W), dtype=torch.float32, device=dev) if want_heatmap else None
+        with self._ws.use(lib.imcui_hip_disk_workspace_bytes(B, H, W), dev) as ws:
+            hd.launch(
+                lib.imcui_hip_disk_forward, _ptr(packed), _ptr(image), B, H, W, int(pad), window, float(conf["detection_threshold"]), maxk, kcap,
+                _ptr(kpts), _ptr(scores), _ptr(desc), _ptr(nk), _ptr(status), _ptr(heat), _ptr(ws), ws.numel(),
+            )  # fmt: skip
+        out = {"keypoints": kpts, "scores": scores, "descriptors": desc, "num_keypoints": nk, "status": status}
+        if want_heatmap:
+            out["heatmap"] = heat
+        return out
+
+
 # ------------------------------------------------------------------ LightGlue
 def lightglue_tensor_names() -> list[str]:
     lib = load_library()
@@ -1118,6 +1212,24 @@ def preprocess_area(img_u8: torch.Tensor, size) -> torch.Tensor:
     if not (W % ow == 0 and H % oh == 0) and ow <= W and oh <= H:
         tabs = [*_area_table(W, ow, img_u8.device), *_area_table(H, oh, img_u8.device)]
     hd.launch(hd.lib.imcui_hip_preprocess_area_f32, _ptr(img_u8), B, H, W, Cc, *[_ptr(t) for t in tabs], _ptr(out), oh, ow)
+    return out
+
+
+def preprocess_area_rgb(img_u8: torch.Tensor, size) -> torch.Tensor:
+    """The RGB branch of `extract.preprocess` (extract_features.py:80-99, `grayscale: False`): uint8 [B,H,W,3] on the device ->
+    float32 -> cv2.INTER_AREA per channel to `size` = (w, h) -> / 255 -> float32 planar [B,3,h,w].  `size` equal to the input
+    converts without resizing; shrinking resizes only."""
+    if img_u8.dtype != torch.uint8 or img_u8.dim() != 4 or img_u8.shape[-1] != 3:
+        raise ImcuiHipError("preprocess_area_rgb expects uint8 [B,H,W,3]")
+    hd = get_handle(img_u8.device)
+    img_u8 = img_u8.contiguous()
+    B, H, W, _ = img_u8.shape
+    ow, oh = int(size[0]), int(size[1])
+    out = torch.empty((B, 3, oh, ow), dtype=torch.float32, device=img_u8.device)
+    tabs = [None] * 6
+    if not (W % ow == 0 and H % oh == 0) and ow <= W and oh <= H:
+        tabs = [*_area_table(W, ow, img_u8.device), *_area_table(H, oh, img_u8.device)]
+    hd.launch(hd.lib.imcui_hip_preprocess_area_rgb_f32, _ptr(img_u8), B, H, W, *[_ptr(t) for t in tabs], _ptr(out), oh, ow)
     return out
 
 

@@ -231,10 +231,13 @@ def target_size(size, conf: SimpleNamespace):
     return None
 
 
-def preprocess_on_device(img_u8, conf: SimpleNamespace, device) -> torch.Tensor:
-    """uint8 [H,W] / [H,W,3] (host array or device tensor) -> float32 [1,1,h,w] in [0,1] on the device, following :79-99."""
-    if not conf.grayscale:
-        raise NotImplementedError("the HIP extractors take gray images (SuperPoint conf `grayscale: True`)")
+def preprocess_on_device(img_u8, conf: SimpleNamespace, device, rgb: bool = False) -> torch.Tensor:
+    """uint8 [H,W] / [H,W,3] (host array or device tensor) -> float32 [1,1,h,w] in [0,1] on the device, following :79-99.
+    `rgb` (the model declares `takes_rgb`, e.g. DISK) with `grayscale: False`: [H,W,3] -> float32 [1,3,h,w] (astype(float32),
+    INTER_AREA per channel, CxHxW, / 255)."""
+    if not conf.grayscale and not rgb:
+        raise NotImplementedError("this HIP extractor takes gray images (SuperPoint conf `grayscale: True`); "
+                                  "`grayscale: False` runs only with an extractor that declares `takes_rgb` (DISK)")  # fmt: skip
     if conf.interpolation != "cv2_area":
         raise NotImplementedError(f"interpolation {conf.interpolation!r}: only cv2_area runs on the device")
     t = (img_u8 if torch.is_tensor(img_u8) else torch.from_numpy(img_u8)).to(device)[None]
@@ -242,6 +245,12 @@ def preprocess_on_device(img_u8, conf: SimpleNamespace, device) -> torch.Tensor:
     new = target_size((w, h), conf)
     if new is None:
         new = (w, h)
+    if not conf.grayscale:
+        if t.dim() != 4 or t.shape[-1] != 3:
+            raise ValueError(f"`grayscale: False` needs an [H,W,3] image, got shape {tuple(t.shape[1:])}")
+        if new[0] > w or new[1] > h:  # the `disk` conf (resize_max, no force_resize) never grows an image
+            raise NotImplementedError(f"a growing RGB resize ({w}x{h} -> {new[0]}x{new[1]}, INTER_LINEAR) does not run on the device")
+        return backend.preprocess_area_rgb(t, new)
     if new[0] > w or new[1] > h:
         return backend.preprocess_linear(t, new)  # resize_image :29-31: INTER_AREA becomes INTER_LINEAR as soon as a side grows
     if new == (w, h) and t.dim() == 4:
@@ -274,6 +283,7 @@ def main(conf: Dict, image_dir: Path, export_dir: Optional[Path] = None, as_half
         model = dynamic_load(extractors, conf["model"]["name"])(conf["model"]).eval().to(device)
     device = next(model.buffers()).device
     noise = getattr(model, "detection_noise", 1)
+    rgb = bool(getattr(model, "takes_rgb", False))  # extractors that take colour (DISK) get [B,3,h,w] with `grayscale: False`
 
     pending: Dict[tuple, list] = {}  # preprocessed (h, w) -> [(name, image tensor, original size)]
 
@@ -296,7 +306,7 @@ def main(conf: Dict, image_dir: Path, export_dir: Optional[Path] = None, as_half
                 pred = {
                     "keypoints": (kp[b, :n] + 0.5) * scales[None] - 0.5,
                     "scores": sc[b, :n],
-                    "descriptors": np.ascontiguousarray(de[b, :n].T),  # [256, N] like the reference plugin
+                    "descriptors": np.ascontiguousarray(de[b, :n].T),  # [D, N] like the reference plugin
                     "image_size": original_size,
                 }
                 uncertainty = noise * scales.mean()
@@ -319,7 +329,7 @@ def main(conf: Dict, image_dir: Path, export_dir: Optional[Path] = None, as_half
         part = names[c0 : c0 + chunk]
         for name, img_u8 in zip(part, read_images_device([image_dir / n for n in part], pconf.grayscale, device, decode, decoder)):
             original_size = np.array(tuple(img_u8.shape[:2][::-1]))
-            img = preprocess_on_device(img_u8, pconf, device)
+            img = preprocess_on_device(img_u8, pconf, device, rgb=rgb)
             key = tuple(img.shape[-2:])
             pending.setdefault(key, []).append((name, img, original_size))
             if len(pending[key]) >= batch_size:

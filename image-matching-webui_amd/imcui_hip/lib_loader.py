@@ -35,6 +35,7 @@ SIGNATURES = {
     "imcui_hip_rgb_to_gray_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "imcui_hip_area_table": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "imcui_hip_preprocess_area_f32": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 7 + [C.c_int, C.c_int, C.c_void_p]),
+    "imcui_hip_preprocess_area_rgb_f32": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] * 7 + [C.c_int, C.c_int, C.c_void_p]),
     "imcui_hip_linear_table": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "imcui_hip_preprocess_linear_f32": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 7 + [C.c_int, C.c_int, C.c_void_p]),
     "imcui_hip_aa_table": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
@@ -50,6 +51,16 @@ SIGNATURES = {
     "imcui_hip_conv3x3_split_f32": (C.c_int, [C.c_void_p] * 7 + [C.c_int] * 7 + [C.c_void_p]),
     "imcui_hip_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "imcui_hip_profile_read": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int)]),
+    "imcui_hip_disk_packed_floats": (C.c_size_t, []),
+    "imcui_hip_disk_num_tensors": (C.c_int, []),
+    "imcui_hip_disk_tensor_name": (C.c_char_p, [C.c_int]),
+    "imcui_hip_disk_pack_weights": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p]),
+    "imcui_hip_disk_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
+    "imcui_hip_disk_max_keypoints_bound": (C.c_int, [C.c_int] * 3),
+    "imcui_hip_disk_forward": (
+        C.c_int,
+        [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_float, C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_void_p, C.c_size_t, C.c_void_p],
+    ),
     "imcui_hip_superpoint_packed_floats": (C.c_size_t, []),
     "imcui_hip_superpoint_pack_weights": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p]),
     "imcui_hip_superpoint_workspace_bytes": (C.c_size_t, [C.c_int] * 4),

@@ -519,3 +519,37 @@ def dust3r_state_dict(seed: int = 0, cfg: dict | None = None, gain: float = 1.0)
             lin(q + "fc1", 4 * (E + D), E + D)
             lin(q + "fc2", (dd + 1) * 256, 4 * (E + D), 1.5)
     return sd
+
+
+# DISK (kornia.feature.DISK, U-Net of 5x5 convolutions): (state-dict block, input channels, output channels, has norm / gate)
+DISK_LAYERS = [
+    ("unet.path_down.0.1", 3, 16, False),
+    ("unet.path_down.1.1", 16, 32, True),
+    ("unet.path_down.2.1", 32, 64, True),
+    ("unet.path_down.3.1", 64, 64, True),
+    ("unet.path_down.4.1", 64, 64, True),
+    ("unet.path_up.0.conv", 128, 64, True),
+    ("unet.path_up.1.conv", 128, 64, True),
+    ("unet.path_up.2.conv", 96, 64, True),
+    ("unet.path_up.3.conv", 80, 129, True),
+]
+
+
+def disk_state_dict(seed: int = 0, heat_gain: float = 4.0) -> dict:
+    """Kaiming-scaled random DISK weights (26 tensors, 1 092 369 params, kornia's key names).  PReLU slopes scatter around
+    PyTorch's 0.25 initial value.  The heatmap row (output channel 128 of the last convolution) is scaled by `heat_gain` so the
+    logits spread over several units: many well separated NMS maxima above a 0.0 threshold, and a selection cut-off that
+    falls inside a dense range of values."""
+    g = torch.Generator().manual_seed(seed)
+    sd = {}
+    for name, cin, cout, gated in DISK_LAYERS:
+        if gated:
+            sd[f"{name}.1.weight"] = 0.25 + 0.1 * torch.randn(cin, generator=g)
+        w = torch.randn(cout, cin, 5, 5, generator=g) * math.sqrt(2.0 / (cin * 25))
+        b = 0.05 * torch.randn(cout, generator=g)
+        if cout == 129:
+            w[128] *= heat_gain
+            b[128] = 0.0
+        sd[f"{name}.3.weight"] = w
+        sd[f"{name}.3.bias"] = b
+    return sd

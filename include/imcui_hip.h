@@ -124,6 +124,32 @@ int imcui_hip_superpoint_status(imcui_hip_t* h, int B, int H, int W, int nms_rad
 int imcui_hip_simple_nms(imcui_hip_t* h, const float* scores, float* out, int B, int H, int W, int nms_radius,
                          void* stream);
 
+/* ---- DISK (zoo entries disk, disk+lightglue, disk+dualsoftmax; imcui/hloc/extractors/disk.py:18-36) ------------------ */
+/* Weight packing runs on the HOST (imcui/hloc/extractors/disk.py:18-36 -> kornia DISK.from_pretrained): tensor i is the kornia
+ * state-dict entry named imcui_hip_disk_tensor_name(i) (unet.path_down.*, unet.path_up.*: 26 tensors); `packed` receives
+ * imcui_hip_disk_packed_floats() floats which the caller uploads once. */
+size_t imcui_hip_disk_packed_floats(void);
+int imcui_hip_disk_num_tensors(void);
+const char* imcui_hip_disk_tensor_name(int i);
+int imcui_hip_disk_pack_weights(const float* const* tensors, float* packed);
+/* Scratch of imcui_hip_disk_forward for B images of H x W (independent of the window, the threshold and kcap). */
+size_t imcui_hip_disk_workspace_bytes(int B, int H, int W);
+/* Exact bound on the key-points of an H x W image: NMS survivors are pairwise >= window / 2 + 1 apart (Chebyshev). */
+int imcui_hip_disk_max_keypoints_bound(int H, int W, int window);
+/* imcui/hloc/extractors/disk.py:18-36 `self.model(image, n=max_keypoints, window_size=nms_window_size,
+ * score_threshold=detection_threshold, pad_if_not_divisible=...)`.
+ * image [dev, B,3,H,W] RGB in [0,1].  pad_if_not_divisible: zero-pad right / bottom to multiples of 16 (else H, W must be
+ * multiples of 16); window: odd NMS window; threshold: strict; max_keypoints -1 = None.
+ * Outputs, fixed stride `kcap` per image, first num_keypoints[b] entries valid, the rest zero:
+ *   keypoints [dev, B,kcap,2] (x, y) integer pixels as float, ROW-MAJOR order (not sorted by score)
+ *   scores [dev, B,kcap] raw heatmap values;  descriptors [dev, B,kcap,128] L2-normalised rows;  num_keypoints [dev, B] int32
+ *   status [dev, 1] int32 optional: 0 = fine, bit 1 = more key-points than kcap (the first kcap are returned)
+ *   heatmap [dev, B,H,W] optional: the dense detection logits (cropped)
+ * One intended divergence: zero candidates give zero key-points (kornia raises inside kthvalue).  No host synchronisation. */
+int imcui_hip_disk_forward(imcui_hip_t* h, const float* packed, const float* image, int B, int H, int W, int pad_if_not_divisible, int window,
+                           float threshold, int max_keypoints, int kcap, float* keypoints, float* scores, float* descriptors, int* num_keypoints,
+                           int* status, float* heatmap, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- LightGlue --------------------------------------------- */
 /* Host-side packing of the upstream state dict (9 layers, dim 256, 4 heads).  `tensors` holds the
  * host pointers of imcui_hip_lightglue_num_tensors() tensors; tensor i is the upstream state-dict
@@ -508,6 +534,12 @@ int imcui_hip_area_table(int ssize, int dsize, int* start, int* index, float* we
 int imcui_hip_preprocess_area_f32(imcui_hip_t* h, const unsigned char* src, int B, int H, int W, int C, const int* xstart,
                                   const int* xindex, const float* xweight, const int* ystart, const int* yindex,
                                   const float* yweight, float* out, int oh, int ow, void* stream);
+/* RGB mode of the same resize for extractors that take colour (DISK, `grayscale: False`): src uint8 [dev, B,H,W,3] -> float32 ->
+ * INTER_AREA per channel -> / 255 -> out float32 planar [dev, B,3,oh,ow] (imcui/hloc/extract_features.py:80-99).  Tables as above;
+ * oh = H, ow = W converts without resizing.  Shrinking only. */
+int imcui_hip_preprocess_area_rgb_f32(imcui_hip_t* h, const unsigned char* src, int B, int H, int W, const int* xstart, const int* xindex,
+                                      const float* xweight, const int* ystart, const int* yindex, const float* yweight, float* out, int oh,
+                                      int ow, void* stream);
 
 /* Growing resize of the same preprocessing step: `resize_image(image, size, "cv2_area")` runs cv2.INTER_LINEAR as soon as a
  * side grows (imcui/hloc/extract_features.py:29-31; `superpoint_max` force-resizes every image to 640 x 480).  Host table of
