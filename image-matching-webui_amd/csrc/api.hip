@@ -211,6 +211,87 @@ extern "C" int imcui_hip_linear_f32(imcui_hip_t* h, const float* A, const float*
     return gemm_launch(h, g, (hipStream_t)stream);
 }
 
+extern "C" size_t imcui_hip_gemm_desc_bytes(void) { return sizeof(imcui_hip_gemm_desc); }
+extern "C" int imcui_hip_gemm_probe_f32(imcui_hip_t* h, const imcui_hip_gemm_desc* d, void* stream) {
+    if (!h || !d) return imcui_set_err(h, IMCUI_ERR_ARG, "gemm_probe: null argument");
+    GemmP g;
+    g.epi = d->epi;
+    g.A = d->A;
+    g.lda = d->lda;
+    g.A2 = d->A2;
+    g.lda2 = d->lda2;
+    g.K1 = d->K1;
+    g.W = d->W;
+    g.ldw = d->ldw;
+    g.Wh = d->Wh;
+    g.Wl = d->Wl;
+    g.wscale = d->wscale;
+    g.bias = d->bias;
+    g.C = d->C;
+    g.ldc = d->ldc;
+    g.M = d->M;
+    g.N = d->N;
+    g.K = d->K;
+    g.alpha = d->alpha;
+    g.cnt = d->cnt;
+    g.active = d->active;
+    g.rows_per_seq = d->rows_per_seq;
+    g.wsel = d->wsel;
+    g.wsel_off = d->wsel_off;
+    g.w_stride = d->w_stride;
+    g.b_stride = d->b_stride;
+    g.batch = d->batch;
+    g.a_bs = d->a_bs;
+    g.a2_bs = d->a2_bs;
+    g.w_bs = d->w_bs;
+    g.c_bs = d->c_bs;
+    g.mcnt = d->mcnt;
+    g.ncnt = d->ncnt;
+    g.cnt_stride = d->cnt_stride;
+    g.Q = d->Q;
+    g.Kt = d->Kt;
+    g.V = d->V;
+    g.v_transposed = d->v_transposed;
+    g.split_out = d->split_out;
+    g.plane_halves = d->plane_halves;
+    g.conv_k = d->conv_k;
+    g.conv_stride = d->conv_stride;
+    g.conv_pad = d->conv_pad;
+    g.conv_hin = d->conv_hin;
+    g.conv_win = d->conv_win;
+    g.conv_hout = d->conv_hout;
+    g.conv_wout = d->conv_wout;
+    g.conv_cin = d->conv_cin;
+    g.resid = d->resid;
+    g.ldr = d->ldr;
+    g.rup_h = d->rup_h;
+    g.rup_w = d->rup_w;
+    g.rup_align = d->rup_align;
+    g.act = d->act;
+    g.single = d->single;
+    g.rope_cos = d->rope_cos;
+    g.rope_sin = d->rope_sin;
+    g.heads = d->heads;
+    g.role0 = d->role0;
+    g.rope_seq_row0 = d->rope_seq_row0;
+    g.ln_stats = d->ln_stats;
+    g.ln_rowsum = d->ln_rowsum;
+    g.ln_stride = d->ln_stride;
+    return gemm_launch(h, g, (hipStream_t)stream);
+}
+extern "C" int imcui_hip_gemm_last_route(const imcui_hip_t* h) { return h ? h->gemm_last_route : -1; }
+extern "C" int imcui_hip_gemm_route_counts(const imcui_hip_t* h, int* out, int n) {
+    if (!h || (!out && n > 0)) return -1;
+    for (int i = 0; i < n && i < IMCUI_GEMM_ROUTE_SLOTS; ++i) out[i] = h->gemm_route_count[i];
+    return IMCUI_GEMM_ROUTE_SLOTS;
+}
+extern "C" int imcui_hip_gemm_route_reset(imcui_hip_t* h) {
+    if (!h) return IMCUI_ERR_ARG;
+    memset(h->gemm_route_count, 0, sizeof h->gemm_route_count);
+    h->gemm_last_route = 0;
+    return IMCUI_OK;
+}
+
 // ------------------------------------------------------------------ device-side preprocessing (step before the path)
 // 4 pixels per thread: 12 bytes in (three dwords), 16 bytes out; HBM-bound byte work (7 B / pixel).
 __global__ __launch_bounds__(256) void rgb_to_gray_kernel(const unsigned* __restrict__ rgb, float4* __restrict__ out, long nquad) {

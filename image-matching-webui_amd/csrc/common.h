@@ -176,6 +176,8 @@ enum {
     OPT_NCNT
 };
 
+#define IMCUI_GEMM_ROUTE_SLOTS 320  // GEMM_ROUTE(kind, epi) < 20 x 16 (gemm.h)
+
 // optional per-kernel-class HIP-event timing (bench.py's live roofline measurement)
 enum { PROF_ATTN = 0, PROF_CONV = 1, PROF_GEMM = 2, PROF_NCLS = 3 };
 #define PROF_MAX_EVENTS 4096
@@ -197,6 +199,10 @@ struct imcui_hip_s {
     int opt[OPT_NCNT];  // A/B switches (above)
     int loftr_fine_mode;  // how the last imcui_hip_loftr_forward evaluated the last FPN stage: 0 dense maps, 1 on the windows of the matches (bench.py reports it)
     int loftr_fine_matches;  // the match count that call read back (-1: no read-back)
+    // which GEMM instantiation gemm_launch launched last (GEMM_ROUTE of gemm.h, 0 = none) and how often each one ran since the last
+    // imcui_hip_gemm_route_reset: stored by the launch sites themselves, read by the kernel-variant tests
+    int gemm_last_route;
+    int gemm_route_count[IMCUI_GEMM_ROUTE_SLOTS];
 };
 // scan `rows` x `cols` f32 values (row stride ld; rows of sequence s beyond cnt[s] are padding and skipped) into h->range_flag
 void imcui_range_check(imcui_hip_s* h, const float* x, long rows, int cols, long ld, const int* cnt, int rows_per_seq, hipStream_t s);

@@ -97,19 +97,52 @@ struct GemmP {
     // nullptr: every sequence reads the table from row 0
     const int* rope_seq_row0 = nullptr;
     // LayerNorm folded into the layer (DUSt3R; gemm_wreg_kernel, EPI_CONV and EPI_QKV_VIT only): A holds the RAW rows x, the weights carry
-    // gamma and the bias carries W beta (pack time), and the epilogue applies  out = rstd_row (acc - mean_row ln_rowsum[n]) + bias[n]
-    // where the plain layer computes acc + bias[n].  ln_stats [M][2] = (mean, rstd) of every row of A, ln_rowsum [N] = sum_k W[n][k] of
-    // the packed (gamma-folded) weights, + ln_stride floats per selected weight set (wsel)
+    // gamma and the bias carries W beta (pack time); the kernel centres every row while it stages it (x - mean_row) and the epilogue
+    // applies  out = rstd_row acc + bias[n]  where the plain layer computes acc + bias[n].  ln_stats [M][2] = (mean, rstd) of every row
+    // of A.  ln_rowsum [N] = sum_k W[n][k] of the packed weights (+ ln_stride floats per weight set) served the uncentred fold,
+    // rstd (acc - mean rowsum), and is no longer read: the packed DUSt3R format still carries it
     const float* ln_stats = nullptr;
     const float* ln_rowsum = nullptr;
     long ln_stride = 0;
 };
 
+// Route of a launch: which kernel instantiation gemm_launch chose, GEMM_ROUTE(kind, epilogue).  The launch sites store it in the
+// handle (imcui_hip_gemm_last_route / _route_counts), so the report cannot disagree with what ran.  Values are part of the test
+// ABI (tests/test_gpu_gemm_variants.py mirrors them; a CPU test compares the two).
+enum GemmRouteKind {
+    GR_NONE = 0,
+    GR_EXACT = 1,            // gemm_kernel<EPI>
+    GR_SPLIT_F32B = 2,       // gemm_split_kernel<EPI, 0, false, 2>: f32 B operand split on the fly
+    GR_SPLIT_128 = 3,        // gemm_split_kernel<EPI, 0, true, 2>
+    GR_SPLIT_256 = 4,        // gemm_split_kernel<EPI, 0, true, 4>
+    GR_SPLIT_128_SINGLE = 5, // gemm_split_kernel<EPI_CONV, 0, true, 2, true>
+    GR_SPLIT_256_SINGLE = 6, // gemm_split_kernel<EPI_CONV, 0, true, 4, true>
+    GR_CONV_F32B = 7,        // gemm_split_kernel<EPI_CONV, 1, false, 2>
+    GR_CONV_128 = 8,         // gemm_split_kernel<EPI_CONV, 1, true, 2>
+    GR_CONV_256 = 9,         // gemm_split_kernel<EPI_CONV, 1, true, 4>
+    GR_CONV_128_SINGLE = 10, // gemm_split_kernel<EPI_CONV, 1, true, 2, true>
+    GR_CONV_256_SINGLE = 11, // gemm_split_kernel<EPI_CONV, 1, true, 4, true>
+    GR_WREG_ROLLED = 12,     // gemm_wreg_kernel<EPI, false, false, 4>
+    GR_WREG_PIPE = 13,       // gemm_wreg_kernel<EPI, false, true, 4>
+    GR_WREG_ROLLED_SINGLE = 14,  // gemm_wreg_kernel<EPI_CONV, true, false, 4>
+    GR_WREG_PIPE_SINGLE = 15,    // gemm_wreg_kernel<EPI_CONV, true, true, 4>
+    GR_WREG_MT2 = 16,        // gemm_wreg_kernel<EPI, false, true, 2>
+    GR_WREG_MT1 = 17,        // gemm_wreg_kernel<EPI, false, true, 1>
+    GR_NKIND = 18
+};
+#define GEMM_ROUTE(kind, epi) ((kind) * 16 + (epi))
+static_assert(GR_NKIND * 16 <= IMCUI_GEMM_ROUTE_SLOTS, "route table of imcui_hip_s too small");
+static inline void gemm_route_note(imcui_hip_s* h, int kind, int epi) {
+    const int r = GEMM_ROUTE(kind, epi);
+    h->gemm_last_route = r;
+    ++h->gemm_route_count[r];
+}
+
 int gemm_launch(imcui_hip_s* h, const GemmP& p, hipStream_t stream);
 // gemm_wreg.hip: the weights-in-registers kernel for projection layers (split mode, pre-split weight planes); gemm_launch
 // routes eligible launches to it
 bool gemm_wreg_ok(const imcui_hip_s* h, const GemmP& p);
-void gemm_wreg_launch(const imcui_hip_s* h, const GemmP& p, hipStream_t stream);
+void gemm_wreg_launch(imcui_hip_s* h, const GemmP& p, hipStream_t stream);
 
 // host: OIHW conv weight -> GEMM weight [Cout][tap][Cin] (K order of the implicit im2col)
 void pack_conv_gemm(const float* w_oihw, int Cout, int Cin, int ksize, int Cin_pad, float* dst);

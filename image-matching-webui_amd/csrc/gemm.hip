@@ -1058,51 +1058,67 @@ static unsigned occupancy_pad(long nblocks) {
 // parking passes than the main loop gains, so they stay on 128-column tiles).
 static bool wide_ok(const GemmP& p) { return p.Wh != nullptr && p.N % 256 == 0 && p.epi != EPI_QKV && p.epi != EPI_CROSS; }
 template <int EPI>
-static void launch_one(const GemmP& p, bool split, hipStream_t stream) {
+static void launch_one(imcui_hip_s* h, const GemmP& p, bool split, hipStream_t stream) {
     const bool wide = split && wide_ok(p);
     const dim3 grid(cdiv(p.M, BM) * cdiv(p.N, wide ? 256 : BN), 1, p.batch);
-    if (!split)
+    if (!split) {
+        gemm_route_note(h, GR_EXACT, EPI);
         hipLaunchKernelGGL(gemm_kernel<EPI>, grid, dim3(256), 0, stream, p);
-    else if (wide) {
+    } else if (wide) {
         if constexpr (EPI == EPI_CONV) {
             if (p.single) {
+                gemm_route_note(h, GR_SPLIT_256_SINGLE, EPI);
                 hipLaunchKernelGGL((gemm_split_kernel<EPI, 0, true, 4, true>), grid, dim3(256), 0, stream, p);
                 return;
             }
         }
-        if constexpr (EPI != EPI_QKV && EPI != EPI_CROSS)
+        if constexpr (EPI != EPI_QKV && EPI != EPI_CROSS) {
+            gemm_route_note(h, GR_SPLIT_256, EPI);
             hipLaunchKernelGGL((gemm_split_kernel<EPI, 0, true, 4>), grid, dim3(256), 0, stream, p);
+        }
     }
     else if (p.Wh != nullptr) {
         if constexpr (EPI == EPI_CONV) {
             if (p.single) {
+                gemm_route_note(h, GR_SPLIT_128_SINGLE, EPI);
                 hipLaunchKernelGGL((gemm_split_kernel<EPI, 0, true, 2, true>), grid, dim3(256), occupancy_pad((long)grid.x * grid.z), stream, p);
                 return;
             }
         }
+        gemm_route_note(h, GR_SPLIT_128, EPI);
         hipLaunchKernelGGL((gemm_split_kernel<EPI, 0, true, 2>), grid, dim3(256), occupancy_pad((long)grid.x * grid.z), stream, p);
     }
-    else
+    else {
+        gemm_route_note(h, GR_SPLIT_F32B, EPI);
         hipLaunchKernelGGL((gemm_split_kernel<EPI, 0, false, 2>), grid, dim3(256), 0, stream, p);
+    }
 }
-static void launch_conv(const GemmP& p, bool split, hipStream_t stream) {
+static void launch_conv(imcui_hip_s* h, const GemmP& p, bool split, hipStream_t stream) {
     const bool wide = split && wide_ok(p);
     const dim3 grid(cdiv(p.M, BM) * cdiv(p.N, wide ? 256 : BN), 1, p.batch);
-    if (!split)
+    if (!split) {
+        gemm_route_note(h, GR_EXACT, EPI_CONV);
         hipLaunchKernelGGL(gemm_kernel<EPI_CONV>, grid, dim3(256), 0, stream, p);
-    else if (wide && p.single)
+    } else if (wide && p.single) {
+        gemm_route_note(h, GR_CONV_256_SINGLE, EPI_CONV);
         hipLaunchKernelGGL((gemm_split_kernel<EPI_CONV, 1, true, 4, true>), grid, dim3(256), 0, stream, p);
-    else if (wide)
+    } else if (wide) {
+        gemm_route_note(h, GR_CONV_256, EPI_CONV);
         hipLaunchKernelGGL((gemm_split_kernel<EPI_CONV, 1, true, 4>), grid, dim3(256), 0, stream, p);
-    else if (p.Wh != nullptr && p.single)
+    } else if (p.Wh != nullptr && p.single) {
+        gemm_route_note(h, GR_CONV_128_SINGLE, EPI_CONV);
         hipLaunchKernelGGL((gemm_split_kernel<EPI_CONV, 1, true, 2, true>), grid, dim3(256), occupancy_pad((long)grid.x * grid.z), stream, p);
-    else if (p.Wh != nullptr)
+    } else if (p.Wh != nullptr) {
+        gemm_route_note(h, GR_CONV_128, EPI_CONV);
         hipLaunchKernelGGL((gemm_split_kernel<EPI_CONV, 1, true, 2>), grid, dim3(256), occupancy_pad((long)grid.x * grid.z), stream, p);
-    else
+    } else {
+        gemm_route_note(h, GR_CONV_F32B, EPI_CONV);
         hipLaunchKernelGGL((gemm_split_kernel<EPI_CONV, 1, false, 2>), grid, dim3(256), 0, stream, p);
+    }
 }
 
 int gemm_launch(imcui_hip_s* h, const GemmP& p, hipStream_t stream) {
+    h->gemm_last_route = GEMM_ROUTE(GR_NONE, 0);
     if (p.K % BK32 != 0 || p.K <= 0) return imcui_set_err(h, IMCUI_ERR_ARG, "gemm: K=%d must be a positive multiple of %d", p.K, BK32);
     if (p.A2 && (p.K1 % BK32 != 0)) return imcui_set_err(h, IMCUI_ERR_ARG, "gemm: K1=%d must be a multiple of %d", p.K1, BK32);
     if (p.rows_per_seq > 0 && p.rows_per_seq % BM != 0)
@@ -1148,24 +1164,25 @@ int gemm_launch(imcui_hip_s* h, const GemmP& p, hipStream_t stream) {
         return IMCUI_OK;
     }
     switch (p.epi) {
-        case EPI_BIAS: launch_one<EPI_BIAS>(p, split, stream); break;
-        case EPI_RELU: launch_one<EPI_RELU>(p, split, stream); break;
-        case EPI_RESID: launch_one<EPI_RESID>(p, split, stream); break;
-        case EPI_QKV: launch_one<EPI_QKV>(p, split, stream); break;
-        case EPI_CROSS: launch_one<EPI_CROSS>(p, split, stream); break;
+        case EPI_BIAS: launch_one<EPI_BIAS>(h, p, split, stream); break;
+        case EPI_RELU: launch_one<EPI_RELU>(h, p, split, stream); break;
+        case EPI_RESID: launch_one<EPI_RESID>(h, p, split, stream); break;
+        case EPI_QKV: launch_one<EPI_QKV>(h, p, split, stream); break;
+        case EPI_CROSS: launch_one<EPI_CROSS>(h, p, split, stream); break;
         case EPI_QKV_VIT:
             return imcui_set_err(h, IMCUI_ERR_UNSUPPORTED, "gemm: EPI_QKV_VIT is implemented by gemm_wreg_kernel only (split mode, pre-split weights, N %% (64 heads) == 0)");
         case EPI_NNSTAT:
             if (!split || p.Wh != nullptr || !p.st_rpm || !p.st_rps || !p.st_rpi || !p.st_cpm || !p.st_cps || !p.st_cpi || p.bias != nullptr || p.st_rpitch < p.M ||
                 p.st_cpitch < p.N || p.st_nct < cdiv(p.N, BN) || p.st_nrh < 2 * cdiv(p.M, BM))
                 return imcui_set_err(h, IMCUI_ERR_ARG, "gemm: EPI_NNSTAT needs the split mode, an f32 B operand, no bias and the six partial buffers");
+            gemm_route_note(h, GR_SPLIT_F32B, EPI_NNSTAT);
             hipLaunchKernelGGL((gemm_split_kernel<EPI_NNSTAT, 0, false, 2>), dim3(cdiv(p.M, BM) * cdiv(p.N, BN), 1, p.batch), dim3(256), 0, stream, p);
             break;
         case EPI_CONV:
             if (p.conv_k > 0)
-                launch_conv(p, split, stream);
+                launch_conv(h, p, split, stream);
             else
-                launch_one<EPI_CONV>(p, split, stream);
+                launch_one<EPI_CONV>(h, p, split, stream);
             break;
         default: return imcui_set_err(h, IMCUI_ERR_ARG, "gemm: bad epilogue %d", p.epi);
     }

@@ -95,6 +95,19 @@ __global__ __launch_bounds__(256, 2) void gemm_wreg_kernel(GemmP p) {
     const int wo1 = (((g >> 1) * 4 + (rl1 >> 5)) * 64 + (g & 1) * 32 + ((rl1 & 31) ^ (2 * g))) * 16;
     const float* pa0 = A + (size_t)min(c.row0 + (st0 ? rl0 : 0), c.M - 1) * p.lda + g * 8;
     const float* pa1 = A + (size_t)min(c.row0 + (st1 ? rl1 : 0), c.M - 1) * p.lda + g * 8;
+    // LayerNorm folded into the layer (ln_stats): each row is centred while it is staged (x - mean, then split) and the epilogue applies
+    // rstd alone.  The uncentred fold, rstd (acc - mean rowsum), subtracted two terms of size |mean| |rowsum| after the f32 accumulation
+    // and lost ~7e-7 (K = 256) to ~1.4e-6 (K = 1024) of the output per unit of |mean| / std; x - mean is exact for x within a factor two
+    // of the mean (Sterbenz), so what remains is the f32 rounding of the mean itself (tests/test_gpu_gemm_variants.py)
+    bool lnc = false;
+    float mu0 = 0.f, mu1 = 0.f;
+    if constexpr (EPI == EPI_QKV_VIT || EPI == EPI_CONV) {
+        lnc = p.ln_stats != nullptr;
+        if (lnc) {
+            mu0 = p.ln_stats[2 * (size_t)min(c.row0 + (st0 ? rl0 : 0), c.M - 1)];
+            mu1 = p.ln_stats[2 * (size_t)min(c.row0 + (st1 ? rl1 : 0), c.M - 1)];
+        }
+    }
     f32x4 xa0, xb0, xa1, xb1;
     auto issue = [&](int kt) __attribute__((always_inline)) {
         if (st0) {
@@ -108,6 +121,14 @@ __global__ __launch_bounds__(256, 2) void gemm_wreg_kernel(GemmP p) {
     };
     auto store = [&](int stg) __attribute__((always_inline)) {
         uint4 h, l;
+        if constexpr (EPI == EPI_QKV_VIT || EPI == EPI_CONV) {
+            if (lnc) {
+                xa0 -= mu0;
+                xb0 -= mu0;
+                xa1 -= mu1;
+                xb1 -= mu1;
+            }
+        }
         if constexpr (SINGLE) {  // one product: the nearest f16 of either operand (common.h)
             if (st0) *reinterpret_cast<uint4*>(sm + stg * 16384 + wo0) = half8_rtn(__builtin_bit_cast(float4, xa0), __builtin_bit_cast(float4, xb0));
             if (st1) *reinterpret_cast<uint4*>(sm + stg * 16384 + wo1) = half8_rtn(__builtin_bit_cast(float4, xa1), __builtin_bit_cast(float4, xb1));
@@ -248,11 +269,7 @@ __global__ __launch_bounds__(256, 2) void gemm_wreg_kernel(GemmP p) {
         return;
     }
     bool do_store = !(labf & WR_F_NOSTORE);
-    // LayerNorm folded into this layer: per-feature row sums of the (gamma-folded) weights, per-token (mean, rstd) of the raw input
-    const float* lrs = nullptr;
-    if constexpr (EPI == EPI_QKV_VIT || EPI == EPI_CONV) {
-        if (p.ln_stats != nullptr) lrs = p.ln_rowsum + (size_t)c.wsel * p.ln_stride;
-    }
+    // LayerNorm folded into this layer (rows centred while staged): the epilogue scales by the row's rstd
     auto park_rows = [&](int m) __attribute__((always_inline)) {
 #pragma unroll
         for (int n = 0; n < 2; ++n)
@@ -298,14 +315,6 @@ __global__ __launch_bounds__(256, 2) void gemm_wreg_kernel(GemmP p) {
                 pa = *reinterpret_cast<const float4*>(c.bias + fw0 + dp);
                 pb = *reinterpret_cast<const float4*>(c.bias + fw0 + dp + 4);
             }
-            float sm_[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, sp_[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};  // row sums: mine / partner
-            if (lrs != nullptr) {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    sm_[j] = lrs[fw0 + d0 + j];
-                    sp_[j] = lrs[fw0 + dp + j];
-                }
-            }
 #pragma unroll
             for (int m = 0; m < MT; ++m) {
                 float4 tc[4][2], ts[4][2];
@@ -328,14 +337,14 @@ __global__ __launch_bounds__(256, 2) void gemm_wreg_kernel(GemmP p) {
                     const float4 wb = *reinterpret_cast<const float4*>(st + tl * WR_STG_ROW + dp + 4);
                     float mine[8] = {va.x + ba.x, va.y + ba.y, va.z + ba.z, va.w + ba.w, vb.x + bb.x, vb.y + bb.y, vb.z + bb.z, vb.w + bb.w};
                     float part[8] = {wa.x + pa.x, wa.y + pa.y, wa.z + pa.z, wa.w + pa.w, wb.x + pb.x, wb.y + pb.y, wb.z + pb.z, wb.w + pb.w};
-                    if (lrs != nullptr) {
+                    if (lnc) {
                         const float2 mr = *reinterpret_cast<const float2*>(p.ln_stats + 2 * (size_t)(c.row0 + 32 * m + tl));
                         const float xa[8] = {va.x, va.y, va.z, va.w, vb.x, vb.y, vb.z, vb.w}, xp[8] = {wa.x, wa.y, wa.z, wa.w, wb.x, wb.y, wb.z, wb.w};
                         const float ba8[8] = {ba.x, ba.y, ba.z, ba.w, bb.x, bb.y, bb.z, bb.w}, pa8[8] = {pa.x, pa.y, pa.z, pa.w, pb.x, pb.y, pb.z, pb.w};
 #pragma unroll
                         for (int j = 0; j < 8; ++j) {
-                            mine[j] = mr.y * (xa[j] - mr.x * sm_[j]) + ba8[j];
-                            part[j] = mr.y * (xp[j] - mr.x * sp_[j]) + pa8[j];
+                            mine[j] = mr.y * xa[j] + ba8[j];
+                            part[j] = mr.y * xp[j] + pa8[j];
                         }
                     }
                     const float cw[8] = {tc[pass][0].x, tc[pass][0].y, tc[pass][0].z, tc[pass][0].w, tc[pass][1].x, tc[pass][1].y, tc[pass][1].z, tc[pass][1].w};
@@ -434,12 +443,11 @@ __global__ __launch_bounds__(256, 2) void gemm_wreg_kernel(GemmP p) {
                     const float bd = c.bias ? c.bias[fw0 + d] : 0.0f;
                     float4 va = *reinterpret_cast<const float4*>(st + d * WR_STG_TROW + tk);
                     float4 vb = *reinterpret_cast<const float4*>(st + d * WR_STG_TROW + tk + 4);
-                    if (lrs != nullptr) {  // the lane's 8 consecutive tokens: (mean, rstd) pairs are 64 contiguous bytes
-                        const float sd = lrs[fw0 + d];
+                    if (lnc) {  // the lane's 8 consecutive tokens: (mean, rstd) pairs are 64 contiguous bytes
                         const float4* ms4 = reinterpret_cast<const float4*>(p.ln_stats + 2 * (size_t)(c.row0 + 32 * m + tk));
                         const float4 q0 = ms4[0], q1 = ms4[1], q2 = ms4[2], q3 = ms4[3];
-                        va = make_float4(q0.y * (va.x - q0.x * sd), q0.w * (va.y - q0.z * sd), q1.y * (va.z - q1.x * sd), q1.w * (va.w - q1.z * sd));
-                        vb = make_float4(q2.y * (vb.x - q2.x * sd), q2.w * (vb.y - q2.z * sd), q3.y * (vb.z - q3.x * sd), q3.w * (vb.w - q3.z * sd));
+                        va = make_float4(q0.y * va.x, q0.w * va.y, q1.y * va.z, q1.w * va.w);
+                        vb = make_float4(q2.y * vb.x, q2.w * vb.y, q3.y * vb.z, q3.w * vb.w);
                     }
                     uint4 hv, lv;
                     split8(make_float4(va.x + bd, va.y + bd, va.z + bd, va.w + bd), make_float4(vb.x + bd, vb.y + bd, vb.z + bd, vb.w + bd), hv, lv);
@@ -459,8 +467,6 @@ __global__ __launch_bounds__(256, 2) void gemm_wreg_kernel(GemmP p) {
         const int f0 = fw0 + fl;
         float4 b4 = make_float4(0.f, 0.f, 0.f, 0.f);
         if (c.bias != nullptr) b4 = *reinterpret_cast<const float4*>(c.bias + f0);
-        float4 s4 = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (lrs != nullptr) s4 = *reinterpret_cast<const float4*>(lrs + f0);
 #pragma unroll
         for (int m = 0; m < MT; ++m) {
             park_rows(m);
@@ -471,9 +477,9 @@ __global__ __launch_bounds__(256, 2) void gemm_wreg_kernel(GemmP p) {
                 const int row = c.row0 + 32 * m + tl;
                 if (row < c.M) {
                     float4 t4 = *reinterpret_cast<const float4*>(st + tl * WR_STG_ROW + fl);
-                    if (lrs != nullptr) {
-                        const float2 mr = *reinterpret_cast<const float2*>(p.ln_stats + 2 * (size_t)row);
-                        t4 = make_float4(mr.y * (t4.x - mr.x * s4.x), mr.y * (t4.y - mr.x * s4.y), mr.y * (t4.z - mr.x * s4.z), mr.y * (t4.w - mr.x * s4.w));
+                    if (lnc) {
+                        const float rs = p.ln_stats[2 * (size_t)row + 1];
+                        t4 = make_float4(rs * t4.x, rs * t4.y, rs * t4.z, rs * t4.w);
                     }
                     float v[4] = {t4.x + b4.x, t4.y + b4.y, t4.z + b4.z, t4.w + b4.w};
                     float* dstp = C + (size_t)row * p.ldc + f0;
@@ -526,7 +532,7 @@ bool gemm_wreg_ok(const imcui_hip_s* h, const GemmP& p) {
         p.rup_h > 0)
         return false;
     if (p.K % 32 != 0 || p.N % 64 != 0 || (p.lda & 3) != 0) return false;
-    if (p.ln_stats != nullptr && (p.ln_rowsum == nullptr || (p.epi != EPI_QKV_VIT && p.epi != EPI_CONV))) return false;
+    if (p.ln_stats != nullptr && p.epi != EPI_QKV_VIT && p.epi != EPI_CONV) return false;
     if (p.epi == EPI_QKV_VIT)
         return p.split_out && p.v_transposed && p.heads % 4 == 0 && p.N % (p.heads * 64) == 0 && p.rows_per_seq > 0 && p.rows_per_seq % 128 == 0 && p.M % 128 == 0 && !p.single;
     if (p.epi == EPI_QKV || p.epi == EPI_CROSS)
@@ -539,7 +545,8 @@ bool gemm_wreg_ok(const imcui_hip_s* h, const GemmP& p) {
 // small-batch row tiles (LightGlue's attention-layout projections, plain-bias and activation-epilogue launches): the largest of 128 / 64 / 32 tokens that
 // still gives every CU a workgroup
 template <int EPI, int MT>
-static void wreg_launch_small(const GemmP& p, hipStream_t stream) {
+static void wreg_launch_small(imcui_hip_s* h, const GemmP& p, hipStream_t stream) {
+    gemm_route_note(h, MT == 2 ? GR_WREG_MT2 : GR_WREG_MT1, EPI);
     hipLaunchKernelGGL((gemm_wreg_kernel<EPI, false, true, MT>), dim3(cdiv(p.M, 32 * MT) * cdiv(p.N, WR_BN), 1, 1), dim3(256), 0, stream, p);
 }
 static int wreg_tile_tokens(const imcui_hip_s* h, const GemmP& p) {
@@ -553,37 +560,41 @@ static int wreg_tile_tokens(const imcui_hip_s* h, const GemmP& p) {
     return 32;
 }
 template <bool PIPE>
-static void wreg_launch(const GemmP& p, hipStream_t stream) {
+static void wreg_launch(imcui_hip_s* h, const GemmP& p, hipStream_t stream) {
     const dim3 grid(cdiv(p.M, BM) * cdiv(p.N, WR_BN), 1, 1);
+    const int kind = PIPE ? GR_WREG_PIPE : GR_WREG_ROLLED;
     switch (p.epi) {
-        case EPI_BIAS: hipLaunchKernelGGL((gemm_wreg_kernel<EPI_BIAS, false, PIPE>), grid, dim3(256), 0, stream, p); break;
-        case EPI_RELU: hipLaunchKernelGGL((gemm_wreg_kernel<EPI_RELU, false, PIPE>), grid, dim3(256), 0, stream, p); break;
-        case EPI_RESID: hipLaunchKernelGGL((gemm_wreg_kernel<EPI_RESID, false, PIPE>), grid, dim3(256), 0, stream, p); break;
-        case EPI_QKV: hipLaunchKernelGGL((gemm_wreg_kernel<EPI_QKV, false, PIPE>), grid, dim3(256), 0, stream, p); break;
-        case EPI_CROSS: hipLaunchKernelGGL((gemm_wreg_kernel<EPI_CROSS, false, PIPE>), grid, dim3(256), 0, stream, p); break;
-        case EPI_QKV_VIT: hipLaunchKernelGGL((gemm_wreg_kernel<EPI_QKV_VIT, false, PIPE>), grid, dim3(256), 0, stream, p); break;
+        case EPI_BIAS: gemm_route_note(h, kind, EPI_BIAS); hipLaunchKernelGGL((gemm_wreg_kernel<EPI_BIAS, false, PIPE>), grid, dim3(256), 0, stream, p); break;
+        case EPI_RELU: gemm_route_note(h, kind, EPI_RELU); hipLaunchKernelGGL((gemm_wreg_kernel<EPI_RELU, false, PIPE>), grid, dim3(256), 0, stream, p); break;
+        case EPI_RESID: gemm_route_note(h, kind, EPI_RESID); hipLaunchKernelGGL((gemm_wreg_kernel<EPI_RESID, false, PIPE>), grid, dim3(256), 0, stream, p); break;
+        case EPI_QKV: gemm_route_note(h, kind, EPI_QKV); hipLaunchKernelGGL((gemm_wreg_kernel<EPI_QKV, false, PIPE>), grid, dim3(256), 0, stream, p); break;
+        case EPI_CROSS: gemm_route_note(h, kind, EPI_CROSS); hipLaunchKernelGGL((gemm_wreg_kernel<EPI_CROSS, false, PIPE>), grid, dim3(256), 0, stream, p); break;
+        case EPI_QKV_VIT: gemm_route_note(h, kind, EPI_QKV_VIT); hipLaunchKernelGGL((gemm_wreg_kernel<EPI_QKV_VIT, false, PIPE>), grid, dim3(256), 0, stream, p); break;
         default:
-            if (p.single)
+            if (p.single) {
+                gemm_route_note(h, PIPE ? GR_WREG_PIPE_SINGLE : GR_WREG_ROLLED_SINGLE, EPI_CONV);
                 hipLaunchKernelGGL((gemm_wreg_kernel<EPI_CONV, true, PIPE>), grid, dim3(256), 0, stream, p);
-            else
+            } else {
+                gemm_route_note(h, kind, EPI_CONV);
                 hipLaunchKernelGGL((gemm_wreg_kernel<EPI_CONV, false, PIPE>), grid, dim3(256), 0, stream, p);
+            }
     }
 }
-void gemm_wreg_launch(const imcui_hip_s* h, const GemmP& p, hipStream_t stream) {
+void gemm_wreg_launch(imcui_hip_s* h, const GemmP& p, hipStream_t stream) {
     const int tok = wreg_tile_tokens(h, p);
     if (tok != 128) {
         if (p.epi == EPI_QKV)
-            tok == 64 ? wreg_launch_small<EPI_QKV, 2>(p, stream) : wreg_launch_small<EPI_QKV, 1>(p, stream);
+            tok == 64 ? wreg_launch_small<EPI_QKV, 2>(h, p, stream) : wreg_launch_small<EPI_QKV, 1>(h, p, stream);
         else if (p.epi == EPI_CROSS)
-            tok == 64 ? wreg_launch_small<EPI_CROSS, 2>(p, stream) : wreg_launch_small<EPI_CROSS, 1>(p, stream);
+            tok == 64 ? wreg_launch_small<EPI_CROSS, 2>(h, p, stream) : wreg_launch_small<EPI_CROSS, 1>(h, p, stream);
         else if (p.epi == EPI_CONV)  // (EfficientLoFTR's projections on 300-token aggregated grids)
-            tok == 64 ? wreg_launch_small<EPI_CONV, 2>(p, stream) : wreg_launch_small<EPI_CONV, 1>(p, stream);
+            tok == 64 ? wreg_launch_small<EPI_CONV, 2>(h, p, stream) : wreg_launch_small<EPI_CONV, 1>(h, p, stream);
         else
-            tok == 64 ? wreg_launch_small<EPI_BIAS, 2>(p, stream) : wreg_launch_small<EPI_BIAS, 1>(p, stream);
+            tok == 64 ? wreg_launch_small<EPI_BIAS, 2>(h, p, stream) : wreg_launch_small<EPI_BIAS, 1>(h, p, stream);
         return;
     }
     if (h && h->opt[OPT_WREG_PIPE] == 0)  // A/B switch: 0 = the rolled K loop
-        wreg_launch<false>(p, stream);
+        wreg_launch<false>(h, p, stream);
     else
-        wreg_launch<true>(p, stream);
+        wreg_launch<true>(h, p, stream);
 }

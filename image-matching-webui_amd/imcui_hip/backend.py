@@ -1438,6 +1438,112 @@ def conv3x3_f32(x_nhwc: torch.Tensor, w_oihw: torch.Tensor, bias: torch.Tensor, 
     return out
 
 
+# ------------------------------------------------------------------ the shared GEMM, entered directly (kernel-variant tests)
+GEMM_EPI = {"bias": 0, "relu": 1, "resid": 2, "qkv": 3, "cross": 4, "conv": 5, "qkv_vit": 7, "nnstat": 8}
+# GemmRouteKind of csrc/gemm.h: a route is 16 kind + epilogue (imcui_hip_gemm_last_route)
+GEMM_ROUTE_KINDS = {"none": 0, "exact": 1, "split_f32b": 2, "split_128": 3, "split_256": 4, "split_128_single": 5, "split_256_single": 6,
+                    "conv_f32b": 7, "conv_128": 8, "conv_256": 9, "conv_128_single": 10, "conv_256_single": 11, "wreg_rolled": 12,
+                    "wreg_pipe": 13, "wreg_rolled_single": 14, "wreg_pipe_single": 15, "wreg_mt2": 16, "wreg_mt1": 17}  # fmt: skip
+
+
+def gemm_route(kind: str, epi: str) -> int:
+    return GEMM_ROUTE_KINDS[kind] * 16 + GEMM_EPI[epi]
+
+
+def gemm_route_name(route: int) -> str:
+    kinds = {v: k for k, v in GEMM_ROUTE_KINDS.items()}
+    epis = {v: k for k, v in GEMM_EPI.items()}
+    return f"{kinds.get(route // 16, route // 16)}/{epis.get(route % 16, route % 16)}"
+
+
+class GemmDesc(C.Structure):
+    """ctypes mirror of imcui_hip_gemm_desc (include/imcui_hip.h); the CPU suite compares its size with the library's."""
+
+    _fields_ = [("epi", C.c_int), ("A", C.c_void_p), ("lda", C.c_long), ("A2", C.c_void_p), ("lda2", C.c_long), ("K1", C.c_int),
+                ("W", C.c_void_p), ("ldw", C.c_long), ("Wh", C.c_void_p), ("Wl", C.c_void_p), ("wscale", C.c_void_p), ("bias", C.c_void_p),
+                ("C", C.c_void_p), ("ldc", C.c_long), ("M", C.c_int), ("N", C.c_int), ("K", C.c_int), ("alpha", C.c_float),
+                ("cnt", C.c_void_p), ("active", C.c_void_p), ("rows_per_seq", C.c_int), ("wsel", C.c_void_p), ("wsel_off", C.c_int),
+                ("w_stride", C.c_long), ("b_stride", C.c_long), ("batch", C.c_int), ("a_bs", C.c_long), ("a2_bs", C.c_long),
+                ("w_bs", C.c_long), ("c_bs", C.c_long), ("mcnt", C.c_void_p), ("ncnt", C.c_void_p), ("cnt_stride", C.c_int),
+                ("Q", C.c_void_p), ("Kt", C.c_void_p), ("V", C.c_void_p), ("v_transposed", C.c_int), ("split_out", C.c_int),
+                ("plane_halves", C.c_size_t), ("conv_k", C.c_int), ("conv_stride", C.c_int), ("conv_pad", C.c_int), ("conv_hin", C.c_int),
+                ("conv_win", C.c_int), ("conv_hout", C.c_int), ("conv_wout", C.c_int), ("conv_cin", C.c_int), ("resid", C.c_void_p),
+                ("ldr", C.c_long), ("rup_h", C.c_int), ("rup_w", C.c_int), ("rup_align", C.c_int), ("act", C.c_int), ("single", C.c_int),
+                ("rope_cos", C.c_void_p), ("rope_sin", C.c_void_p), ("heads", C.c_int), ("role0", C.c_int), ("rope_seq_row0", C.c_void_p),
+                ("ln_stats", C.c_void_p), ("ln_rowsum", C.c_void_p), ("ln_stride", C.c_long)]  # fmt: skip
+    DEFAULTS = {"batch": 1, "cnt_stride": 1, "conv_stride": 1, "rup_align": 1, "heads": 4, "alpha": 1.0}
+
+
+class GemmWeights:
+    """One or more weight sets [N, K] (host) in both operand formats of the GEMM, on `device`: f32 rows (W, set stride in floats) and the
+    pre-split fragment-major planes of pack_linear_split (Wh / Wl, set stride in halves; wscale[set] = that set's 2^-e)."""
+
+    def __init__(self, sets, device):
+        sets = [_as_f32_host(w) for w in sets]
+        self.N, self.K = sets[0].shape
+        packs = [pack_linear_split(w) for w in sets]
+        self.W = torch.from_numpy(np.concatenate([w.reshape(-1) for w in sets])).to(device)
+        self.Wh = torch.from_numpy(np.concatenate([p[0] for p in packs]).view(np.int16)).to(device)
+        self.Wl = torch.from_numpy(np.concatenate([p[1] for p in packs]).view(np.int16)).to(device)
+        self.wscale = torch.tensor([p[2] for p in packs], dtype=torch.float32, device=device)
+        self.f32_stride, self.half_stride = self.N * self.K, packs[0][0].size
+
+    @classmethod
+    def conv(cls, w_oihw_sets, device):
+        """OIHW convolution weights -> the GEMM weight [Cout][tap][Cin] of the implicit im2col (_conv_gemm_layout)."""
+        mats = []
+        for w in w_oihw_sets:
+            w = w.float().cpu()
+            mats.append(_conv_gemm_layout(w, torch.zeros(w.shape[0]), w.shape[0], w.shape[1])[0])
+        return cls(mats, device)
+
+    def fields(self, split: bool, planes: bool = True) -> dict:
+        """Descriptor fields of this operand: the planes (split mode, `planes`) or the f32 rows; w_stride in the matching unit."""
+        if split and planes:
+            return {"Wh": self.Wh, "Wl": self.Wl, "wscale": self.wscale, "W": self.W, "ldw": self.K, "w_stride": self.half_stride}
+        return {"W": self.W, "ldw": self.K, "wscale": self.wscale, "w_stride": self.f32_stride}
+
+
+def gemm_probe(device: torch.device, check: bool = True, **fields) -> int:
+    """One launch through gemm_launch (imcui_hip_gemm_probe_f32) with the descriptor `fields` (tensors become device pointers, `epi`
+    may be a GEMM_EPI name).  Returns the route of the launch (GEMM_ROUTE_KINDS); with check=False a refused call returns its
+    negative status instead of raising."""
+    hd = get_handle(device)
+    d = GemmDesc()
+    for k, v in {**GemmDesc.DEFAULTS, **fields}.items():
+        if k == "epi" and isinstance(v, str):
+            v = GEMM_EPI[v]
+        if isinstance(v, torch.Tensor):
+            if v.device.type != "cuda":
+                raise ImcuiHipError(f"gemm_probe: field {k} must be a device tensor")
+            v = v.data_ptr()
+        elif v is None:
+            v = 0
+        setattr(d, k, v)
+    if check:
+        hd.launch(hd.lib.imcui_hip_gemm_probe_f32, C.byref(d))
+    else:
+        with torch.cuda.device(hd.device_index):
+            rc = hd.lib.imcui_hip_gemm_probe_f32(hd.h, C.byref(d), _stream_ptr())
+        if rc != 0:
+            return rc
+    return int(hd.lib.imcui_hip_gemm_last_route(hd.h))
+
+
+def gemm_route_counts(device: torch.device) -> dict:
+    """{route: launches} of every GEMM launch on the device's handle since gemm_route_reset."""
+    hd = get_handle(device)
+    n = hd.lib.imcui_hip_gemm_route_counts(hd.h, None, 0)
+    buf = (C.c_int * n)()
+    hd.lib.imcui_hip_gemm_route_counts(hd.h, buf, n)
+    return {r: c for r, c in enumerate(buf) if c}
+
+
+def gemm_route_reset(device: torch.device) -> None:
+    hd = get_handle(device)
+    hd.call(hd.lib.imcui_hip_gemm_route_reset)
+
+
 def _split_planes(t: torch.Tensor) -> torch.Tensor:
     """f32 tensor -> [2, ...] f16 (hi, lo) planes, the operand format of the split attention kernel."""
     hi = t.half()

@@ -635,6 +635,65 @@ size_t imcui_hip_attention_mx_scratch_bytes(int S, int heads, int rows);
 int imcui_hip_attention_mx_f32(imcui_hip_t* h, const float* Q, const float* K, const float* V, float* O, const int* cnt, int S,
                                int heads, int rows, int cross, void* scratch, size_t scratch_bytes, void* stream);
 
+/* ---- test entry into the shared GEMM (tests/test_gpu_gemm_variants.py) ------------------------------------------------------
+ * The fields the networks set on the one matrix engine under every network (csrc/gemm.h, GemmP; meanings there).  Device pointers;
+ * unset fields zero except M / N / K, batch = cnt_stride = 1, conv_stride = 1, rup_align = 1, heads = 4, alpha = 1. */
+typedef struct imcui_hip_gemm_desc {
+    int epi;
+    const float* A;
+    long lda;
+    const float* A2;
+    long lda2;
+    int K1;
+    const float* W;
+    long ldw;
+    const unsigned short* Wh;
+    const unsigned short* Wl;
+    const float* wscale;
+    const float* bias;
+    float* C;
+    long ldc;
+    int M, N, K;
+    float alpha;
+    const int* cnt;
+    const int* active;
+    int rows_per_seq;
+    const int* wsel;
+    int wsel_off;
+    long w_stride, b_stride;
+    int batch;
+    long a_bs, a2_bs, w_bs, c_bs;
+    const int* mcnt;
+    const int* ncnt;
+    int cnt_stride;
+    float* Q;
+    float* Kt;
+    float* V;
+    int v_transposed, split_out;
+    size_t plane_halves;
+    int conv_k, conv_stride, conv_pad, conv_hin, conv_win, conv_hout, conv_wout, conv_cin;
+    const float* resid;
+    long ldr;
+    int rup_h, rup_w, rup_align, act, single;
+    const float* rope_cos;
+    const float* rope_sin;
+    int heads, role0;
+    const int* rope_seq_row0;
+    const float* ln_stats;
+    const float* ln_rowsum;
+    long ln_stride;
+} imcui_hip_gemm_desc;
+/* Copies *d into the kernel parameters and calls the GEMM launcher unchanged (its own refusals are the only checks); a null
+ * handle or descriptor is IMCUI_HIP_ERR_ARG.  sizeof(imcui_hip_gemm_desc) for the bindings' mirror: imcui_hip_gemm_desc_bytes. */
+int imcui_hip_gemm_probe_f32(imcui_hip_t* h, const imcui_hip_gemm_desc* d, void* stream);
+size_t imcui_hip_gemm_desc_bytes(void);
+/* Route of the last GEMM launch on this handle = 16 kind + epilogue (csrc/gemm.h GemmRouteKind, GemmEpi; 0 = nothing launched,
+ * e.g. a refused call), and launches per route since imcui_hip_gemm_route_reset: route_counts copies min(n, slots) counters to
+ * out and returns the slot count.  Every GEMM launch of every network records its route (one host-side store). */
+int imcui_hip_gemm_last_route(const imcui_hip_t* h);
+int imcui_hip_gemm_route_counts(const imcui_hip_t* h, int* out, int n);
+int imcui_hip_gemm_route_reset(imcui_hip_t* h);
+
 #ifdef __cplusplus
 }
 #endif
