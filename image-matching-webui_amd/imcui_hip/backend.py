@@ -295,6 +295,130 @@ class DiskHIP:
         return out
 
 
+# ------------------------------------------------------------------ ALIKED
+ALIKED_MODELS = ("aliked-n16", "aliked-n16rot")  # (c1,c2,c3,c4,dim,K,M) = (16,32,64,128,128,3,16): what csrc/aliked.hip is built for
+
+
+def aliked_tensor_names() -> list[str]:
+    lib = load_library()
+    return [lib.imcui_hip_aliked_tensor_name(i).decode() for i in range(lib.imcui_hip_aliked_num_tensors())]
+
+
+def aliked_tensor_shapes() -> dict:
+    """Upstream ALIKED's state-dict shapes for aliked-n16 (without the `num_batches_tracked` counters)."""
+    ch = [3, 16, 32, 64, 128]
+    shapes = {}
+    for b in range(1, 5):
+        cin, cout = ch[b - 1], ch[b]
+        for j in (1, 2):
+            ci = cin if j == 1 else cout
+            if b >= 3:
+                shapes[f"block{b}.conv{j}.offset_conv.weight"] = (18, ci, 3, 3)
+                shapes[f"block{b}.conv{j}.offset_conv.bias"] = (18,)
+                shapes[f"block{b}.conv{j}.regular_conv.weight"] = (cout, ci, 3, 3)
+            else:
+                shapes[f"block{b}.conv{j}.weight"] = (cout, ci, 3, 3)
+            for k in ("weight", "bias", "running_mean", "running_var"):
+                shapes[f"block{b}.bn{j}.{k}"] = (cout,)
+        if b >= 2:
+            shapes[f"block{b}.downsample.weight"] = (cout, cin, 1, 1)
+    for i in range(1, 5):
+        shapes[f"conv{i}.weight"] = (32, ch[i], 1, 1)
+    shapes.update({"score_head.0.weight": (8, 128, 1, 1), "score_head.2.weight": (4, 8, 3, 3), "score_head.4.weight": (4, 4, 3, 3),
+                   "score_head.6.weight": (1, 4, 3, 3), "desc_head.agg_weights": (16, 128, 128), "desc_head.offset_conv.0.weight": (32, 128, 3, 3),
+                   "desc_head.offset_conv.0.bias": (32,), "desc_head.offset_conv.2.weight": (32, 32, 1, 1), "desc_head.offset_conv.2.bias": (32,),
+                   "desc_head.sf_conv.weight": (128, 128, 1, 1)})  # fmt: skip
+    return shapes
+
+
+def aliked_check_model(model_name: str) -> None:
+    if model_name not in ALIKED_MODELS:
+        known = "aliked-t16 / aliked-n32 have other channel counts and sample numbers" if model_name in ("aliked-t16", "aliked-n32") else "unknown name"
+        raise ImcuiHipError(f"ALIKED model '{model_name}' is not served by the HIP backend ({known}); supported: {', '.join(ALIKED_MODELS)}")
+
+
+def pack_aliked(state_dict: dict, model_name: str = "aliked-n16") -> torch.Tensor:
+    """Upstream ALIKED state dict -> packed float32 buffer (host); BatchNorm (eval) is folded into the convolutions by the packer.
+    Strict: `num_batches_tracked` counters are ignored, every other key is consumed exactly once, every shape checked."""
+    aliked_check_model(model_name)
+    lib = load_library()
+    names = aliked_tensor_names()
+    shapes = aliked_tensor_shapes()
+    sd = {k: v for k, v in state_dict.items() if not k.endswith("num_batches_tracked")}
+    missing = [n for n in names if n not in sd]
+    extra = sorted(set(sd) - set(names))
+    if missing or extra:
+        raise ImcuiHipError(f"ALIKED state dict does not match upstream's {model_name} layout: missing {missing[:4]}, unexpected {extra[:4]}")
+    arrs = []
+    for n in names:
+        a = _as_f32_host(sd[n])
+        if a.shape != shapes[n]:
+            raise ImcuiHipError(f"ALIKED state dict: '{n}' has shape {a.shape}, expected {shapes[n]}")
+        arrs.append(a)
+    packed = np.zeros(lib.imcui_hip_aliked_packed_floats(), dtype=np.float32)
+    tp = (C.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
+    rc = lib.imcui_hip_aliked_pack_weights(tp, packed.ctypes.data)
+    if rc != 0:
+        raise ImcuiHipError(f"imcui_hip_aliked_pack_weights failed ({rc})")
+    return torch.from_numpy(packed)
+
+
+def aliked_check_args(image_shape, nms_radius: int) -> None:
+    """Refusals raised before anything is launched."""
+    if len(image_shape) != 4 or image_shape[1] != 3:
+        raise ValueError(f"ALIKED expects an RGB image [B,3,H,W], got shape {tuple(image_shape)}")
+    if not 1 <= int(nms_radius) <= 4:
+        raise ValueError(f"nms_radius={nms_radius} is outside what the NMS kernel serves (1..4)")
+    if image_shape[2] < 32 or image_shape[3] < 32:
+        raise ValueError(f"ALIKED needs images of at least 32 x 32, got {tuple(image_shape[2:])}")
+
+
+class AlikedHIP:
+    N_LIMIT_MAX = 20000  # upstream's n_limit_max
+
+    def __init__(self):
+        self._ws = _Workspace()
+
+    def forward(self, packed: torch.Tensor, image: torch.Tensor, conf: dict, want_maps: bool = False, kcap: int | None = None):
+        """image [B,3,H,W] float32 on the GPU -> fixed-stride outputs, no host synchronisation: keypoints [B,K,2] (refined pixels,
+        row-major order of their integer candidates), scores [B,K], descriptors [B,K,128], num_keypoints [B] int32, status [1] int32
+        (bit 1: `kcap` too small).  want_maps adds score_map [B,H,W], keypoints_norm [B,K,2] and the outputs of the two deformable
+        blocks x3 [B,Hp/8,Wp/8,64], x4 [B,Hp/32,Wp/32,128].  K = min(n_limit, the NMS bound)."""
+        r = int(conf["nms_radius"])
+        aliked_check_args(tuple(image.shape), r)
+        hd = get_handle(image.device)
+        if packed.device != image.device:
+            raise ImcuiHipError("packed weights and image live on different devices")
+        lib = hd.lib
+        image = image.contiguous().float()
+        B, _, H, W = image.shape
+        maxk = int(conf["max_num_keypoints"])
+        limit = maxk if maxk > 0 else self.N_LIMIT_MAX
+        if kcap is None:
+            kcap = max(1, min(limit, lib.imcui_hip_aliked_max_keypoints_bound(H, W, r)))
+        dev = image.device
+        f32 = dict(dtype=torch.float32, device=dev)
+        kpts = torch.empty((B, kcap, 2), **f32)
+        scores = torch.empty((B, kcap), **f32)
+        desc = torch.empty((B, kcap, 128), **f32)
+        nk = torch.empty((B,), dtype=torch.int32, device=dev)
+        status = torch.empty((1,), dtype=torch.int32, device=dev)
+        Hp, Wp = (H + 31) // 32 * 32, (W + 31) // 32 * 32
+        smap = torch.empty((B, H, W), **f32) if want_maps else None
+        kn = torch.empty((B, kcap, 2), **f32) if want_maps else None
+        x3 = torch.empty((B, Hp // 8, Wp // 8, 64), **f32) if want_maps else None
+        x4 = torch.empty((B, Hp // 32, Wp // 32, 128), **f32) if want_maps else None
+        with self._ws.use(lib.imcui_hip_aliked_workspace_bytes(B, H, W), dev) as ws:
+            hd.launch(
+                lib.imcui_hip_aliked_forward, _ptr(packed), _ptr(image), B, H, W, r, float(conf["detection_threshold"]), maxk, kcap,
+                _ptr(kpts), _ptr(scores), _ptr(desc), _ptr(nk), _ptr(status), _ptr(smap), _ptr(kn), _ptr(x3), _ptr(x4), _ptr(ws), ws.numel(),
+            )  # fmt: skip
+        out = {"keypoints": kpts, "scores": scores, "descriptors": desc, "num_keypoints": nk, "status": status}
+        if want_maps:
+            out.update(score_map=smap, keypoints_norm=kn, x3=x3, x4=x4)
+        return out
+
+
 # ------------------------------------------------------------------ LightGlue
 def lightglue_tensor_names() -> list[str]:
     lib = load_library()

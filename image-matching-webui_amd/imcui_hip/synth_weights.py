@@ -553,3 +553,67 @@ def disk_state_dict(seed: int = 0, heat_gain: float = 4.0) -> dict:
         sd[f"{name}.3.weight"] = w
         sd[f"{name}.3.bias"] = b
     return sd
+
+
+def aliked_state_dict(seed: int = 0, score_gain: float = 4.0, score_shift: float = -3.6) -> dict:
+    """Seeded ALIKED weights (aliked-n16 layout, upstream's key names, 65 tensors without the `num_batches_tracked` counters).
+    Convolutions are LeCun-scaled (SELU keeps unit variance); BatchNorm running statistics are NOT the identity.  The offset
+    convolutions of the deformable layers give offsets of a few pixels (some beyond the +-max(h, w) / 4 clamp of the 1/32 map, some
+    samples outside the map), the descriptor head's offsets likewise.
+    The score head has no bias anywhere, so the logits are centred through the weights: one channel is a constant all the way --
+    x1[15] = SELU(block1.bn2.bias[15]) behind an all-zero filter, passed on by one-hot 1x1 / centre-tap weights (conv1 row 31,
+    score_head.0 row 7, score_head.2 / .4 row 3), each SELU multiplying the positive constant by 1.0507 -- and score_head.6 weighs it
+    so that every logit is shifted by exactly `score_shift`.  The other channels of score_head.6 carry `score_gain`.  With the
+    defaults the 0.2 threshold falls inside the distribution of the NMS survivors (tests/test_aliked_cpu.py asserts it)."""
+    g = torch.Generator().manual_seed(seed)
+    sd = {}
+
+    def rn(*shape, scale=1.0):
+        return torch.randn(*shape, generator=g) * scale
+
+    def conv(name, cout, cin, k, gain=1.0):
+        sd[name] = rn(cout, cin, k, k, scale=gain / math.sqrt(cin * k * k))
+
+    def bn(name, c):
+        sd[f"{name}.weight"] = 1.0 + 0.2 * rn(c)
+        sd[f"{name}.bias"] = 0.1 * rn(c)
+        sd[f"{name}.running_mean"] = 0.2 * rn(c)
+        sd[f"{name}.running_var"] = 0.5 + torch.rand(c, generator=g)
+
+    ch = [3, 16, 32, 64, 128]
+    for b in range(1, 5):
+        cin, cout = ch[b - 1], ch[b]
+        for j in (1, 2):
+            ci = cin if j == 1 else cout
+            if b >= 3:
+                conv(f"block{b}.conv{j}.offset_conv.weight", 18, ci, 3, gain=3.0)
+                sd[f"block{b}.conv{j}.offset_conv.bias"] = rn(18)
+                conv(f"block{b}.conv{j}.regular_conv.weight", cout, ci, 3)
+            else:
+                conv(f"block{b}.conv{j}.weight", cout, ci, 3, gain=2.0 if b == 1 and j == 1 else 1.0)
+            bn(f"block{b}.bn{j}", cout)
+        if b >= 2:
+            conv(f"block{b}.downsample.weight", cout, cin, 1)
+    for i in range(1, 5):
+        conv(f"conv{i}.weight", 32, ch[i], 1)
+    conv("score_head.0.weight", 8, 128, 1)
+    conv("score_head.2.weight", 4, 8, 3)
+    conv("score_head.4.weight", 4, 4, 3)
+    conv("score_head.6.weight", 1, 4, 3, gain=score_gain)
+    # the constant channel (see above)
+    sd["block1.conv2.weight"][15] = 0.0
+    for k, v in (("weight", 1.0), ("bias", 1.0), ("running_mean", 0.0), ("running_var", 1.0)):
+        sd[f"block1.bn2.{k}"][15] = v
+    for name, row, col in (("conv1.weight", 31, 15), ("score_head.0.weight", 7, 31), ("score_head.2.weight", 3, 7), ("score_head.4.weight", 3, 3)):
+        sd[name][row] = 0.0
+        sd[name][row, col, sd[name].shape[2] // 2, sd[name].shape[3] // 2] = 1.0
+    selu_scale = 1.0507009873554805
+    sd["score_head.6.weight"][0, 3] = 0.0
+    sd["score_head.6.weight"][0, 3, 1, 1] = score_shift / selu_scale**5
+    sd["desc_head.agg_weights"] = rn(16, 128, 128, scale=1.0 / math.sqrt(16 * 128))
+    sd["desc_head.offset_conv.0.weight"] = rn(32, 128, 3, 3, scale=1.0 / 3.0)  # (the patch is 9 unit vectors)
+    sd["desc_head.offset_conv.0.bias"] = 0.3 * rn(32)
+    sd["desc_head.offset_conv.2.weight"] = rn(32, 32, 1, 1, scale=3.0 / math.sqrt(32))
+    sd["desc_head.offset_conv.2.bias"] = rn(32)
+    sd["desc_head.sf_conv.weight"] = rn(128, 128, 1, 1)  # (a sample is a unit vector, or an interpolation of four)
+    return sd

@@ -150,6 +150,39 @@ int imcui_hip_disk_forward(imcui_hip_t* h, const float* packed, const float* ima
                            float threshold, int max_keypoints, int kcap, float* keypoints, float* scores, float* descriptors, int* num_keypoints,
                            int* status, float* heatmap, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- ALIKED (zoo entry aliked+lightglue; imcui/hloc/extractors/aliked.py:24-32 -> LightGlue's ALIKED.forward) -------- */
+/* aliked-n16 / aliked-n16rot: (c1,c2,c3,c4,dim,K,M) = (16,32,64,128,128,3,16).  Weight packing runs on the HOST (replaces the
+ * `ALIKED(**conf)` construction and `load_state_dict` of imcui/hloc/extractors/aliked.py:19-22): tensor i is the upstream state-dict
+ * entry named imcui_hip_aliked_tensor_name(i), in upstream's order without the `num_batches_tracked` counters; BatchNorm (eval) is
+ * folded into the convolution before it.  `packed` receives imcui_hip_aliked_packed_floats() floats; it begins with block1.conv1
+ * folded with block1.bn1 as [9 taps][3][16] floats followed (from float 448) by the 16 folded biases. */
+size_t imcui_hip_aliked_packed_floats(void);
+int imcui_hip_aliked_num_tensors(void);
+const char* imcui_hip_aliked_tensor_name(int i);
+int imcui_hip_aliked_pack_weights(const float* const* tensors, float* packed);
+/* Scratch of imcui_hip_aliked_forward for B images of H x W (independent of the radius, the threshold and kcap): less than ONE dense
+ * 128-channel map of the padded images, B * Hp * Wp * 128 * 4 bytes. */
+size_t imcui_hip_aliked_workspace_bytes(int B, int H, int W);
+/* Bound on the key-points of an H x W image whose scores do not tie exactly: simple_nms survivors are more than nms_radius apart. */
+int imcui_hip_aliked_max_keypoints_bound(int H, int W, int nms_radius);
+/* imcui/hloc/extractors/aliked.py:24-32 `self.model(data)`: InputPadder (replicate, multiples of 32), encoder, score head, DKD, SDDH.
+ * image [dev, B,3,H,W] RGB in [0,1], H, W >= 32.  nms_radius 1..4.  threshold > 0: candidates are nms > threshold, or nms > mean(score
+ * map) when an image has none (decided per image); more than n_limit (max_keypoints if > 0, else 20000): the n_limit highest scores
+ * stay, ties to the lower flat index.  threshold <= 0 and max_keypoints > 0: the max_keypoints highest positive NMS scores.
+ * threshold <= 0 and max_keypoints <= 0: nms > mean.
+ * Outputs, fixed stride `kcap` per image, first num_keypoints[b] entries valid, the rest zero, ROW-MAJOR order of the integer
+ * candidate (not sorted by score):
+ *   keypoints [dev, B,kcap,2] (x, y) refined, in pixels;  scores [dev, B,kcap] score map sampled there
+ *   descriptors [dev, B,kcap,128] L2-normalised rows;  num_keypoints [dev, B] int32
+ *   status [dev, 1] int32 optional: 0 = fine, bit 1 = more key-points than kcap (the first kcap are returned)
+ *   score_map [dev, B,H,W] optional;  keypoints_norm [dev, B,kcap,2] optional: the key-points in [-1, 1] as DKD hands them to SDDH
+ *   dbg_x3 [dev, B,Hp/8,Wp/8,64], dbg_x4 [dev, B,Hp/32,Wp/32,128] optional: outputs of the two deformable blocks (NHWC, padded size)
+ * The descriptor head runs in two launches per batch whatever kcap is; while it runs, floats 0..31 of a key-point's descriptor row hold
+ * its sample offsets.  No host synchronisation. */
+int imcui_hip_aliked_forward(imcui_hip_t* h, const float* packed, const float* image, int B, int H, int W, int nms_radius, float threshold,
+                             int max_keypoints, int kcap, float* keypoints, float* scores, float* descriptors, int* num_keypoints, int* status,
+                             float* score_map, float* keypoints_norm, float* dbg_x3, float* dbg_x4, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- LightGlue --------------------------------------------- */
 /* Host-side packing of the upstream state dict (9 layers, dim 256, 4 heads).  `tensors` holds the
  * host pointers of imcui_hip_lightglue_num_tensors() tensors; tensor i is the upstream state-dict
