@@ -516,3 +516,46 @@ extern "C" int imcui_hip_attention_mx_f32(imcui_hip_t* h, const float* Q, const 
     a.V6 = (unsigned char*)scratch;
     return attention_launch(h, a, (hipStream_t)stream);
 }
+
+extern "C" size_t imcui_hip_attn_desc_bytes(void) { return sizeof(imcui_hip_attn_desc); }
+extern "C" size_t imcui_hip_attention_part_floats(int S, int heads, int rows) { return (S > 0 && heads > 0 && rows > 0) ? attn_part_floats(S, heads, rows) : 0; }
+extern "C" int imcui_hip_attention_probe_f32(imcui_hip_t* h, const imcui_hip_attn_desc* d, void* stream) {
+    if (h) h->attn_last_route = 0;
+    if (!h || !d || !d->Q || !d->K || !d->V || !d->O || !d->cnt) return imcui_set_err(h, IMCUI_ERR_ARG, "attention_probe: null argument");
+    if (d->nseq > 0 && d->heads > 0 && d->rows_per_seq > 0) {
+        if (d->V6 && d->V6_bytes < attn_v6_bytes(d->nseq, d->heads, d->rows_per_seq))
+            return imcui_set_err(h, IMCUI_ERR_WS, "attention_probe: V6 scratch of %zu bytes needed", attn_v6_bytes(d->nseq, d->heads, d->rows_per_seq));
+        if (d->part && d->part_bytes < attn_part_floats(d->nseq, d->heads, d->rows_per_seq) * sizeof(float))
+            return imcui_set_err(h, IMCUI_ERR_WS, "attention_probe: part scratch of %zu floats needed", attn_part_floats(d->nseq, d->heads, d->rows_per_seq));
+    }
+    AttnP a;
+    a.Q = d->Q;
+    a.K = d->K;
+    a.V = d->V;
+    a.O = d->O;
+    a.cnt = d->cnt;
+    a.active = d->active;
+    a.nseq = d->nseq;
+    a.heads = d->heads;
+    a.rows_per_seq = d->rows_per_seq;
+    a.cross = d->cross;
+    a.log2_domain = d->log2_domain;
+    a.single = d->single;
+    a.variant = d->variant;
+    a.V6 = d->V6;
+    a.v6_ready = d->v6_ready;
+    a.part = d->part;
+    return attention_launch(h, a, (hipStream_t)stream);
+}
+extern "C" int imcui_hip_attn_last_route(const imcui_hip_t* h) { return h ? h->attn_last_route : -1; }
+extern "C" int imcui_hip_attn_route_counts(const imcui_hip_t* h, int* out, int n) {
+    if (!h || (!out && n > 0)) return -1;
+    for (int i = 0; i < n && i < IMCUI_ATTN_ROUTE_SLOTS; ++i) out[i] = h->attn_route_count[i];
+    return IMCUI_ATTN_ROUTE_SLOTS;
+}
+extern "C" int imcui_hip_attn_route_reset(imcui_hip_t* h) {
+    if (!h) return IMCUI_ERR_ARG;
+    memset(h->attn_route_count, 0, sizeof h->attn_route_count);
+    h->attn_last_route = 0;
+    return IMCUI_OK;
+}

@@ -36,5 +36,27 @@ struct AttnP {
 static inline size_t attn_part_floats(int nseq, int heads, int rows_per_seq) { return (size_t)ATTN_MAX_CHUNKS(rows_per_seq) * nseq * heads * rows_per_seq * 66; }
 #define ATTN_V6_TILE_BYTES 6400  // hi6 [128 slots][16 B] + [128][8 B], lo6 likewise, 256 scale bytes
 static inline size_t attn_v6_bytes(int nseq, int heads, int rows_per_seq) { return (size_t)nseq * heads * (rows_per_seq / 64) * ATTN_V6_TILE_BYTES; }
+
+// Route of a launch: which kernel instantiation attention_launch chose, ATTN_ROUTE(kind, split).  The launch sites store it in the handle
+// (imcui_hip_attn_last_route / _route_counts), so the report cannot disagree with what ran; host code only.  Values are part of the test
+// ABI (imcui_hip/backend.py mirrors them; a CPU test compares the two).
+enum AttnRouteKind {
+    AR_NONE = 0,
+    AR_EXACT = 1,        // attn_kernel: exact f32
+    AR_NATLOG = 2,       // attn_split_kernel<false, 0, false>: split arithmetic, natural-log operands
+    AR_L2D_V8 = 3,       // attn_split_kernel<true, 8, SPLIT>: log2 domain, three products in both contractions
+    AR_L2D_V7 = 4,       // attn_split_kernel<true, 7, SPLIT>: two-product P.V, probabilities rounded to f16
+    AR_L2D_SINGLE = 5,   // attn_split_kernel<true, 4, SPLIT>: AttnP.single, one f16 product
+    AR_MX = 6,           // attn_mx_kernel (attention_mx.hip): variant 9
+    AR_NKIND = 7
+};
+#define ATTN_ROUTE(kind, split) ((kind) * 2 + (split))  // split = 1: the key-split launch (attn_split_kernel<.., true> + attn_combine_kernel)
+static_assert(AR_NKIND * 2 <= IMCUI_ATTN_ROUTE_SLOTS, "route table of imcui_hip_s too small");
+static inline void attn_route_note(imcui_hip_s* h, int kind, int split) {
+    const int r = ATTN_ROUTE(kind, split);
+    h->attn_last_route = r;
+    ++h->attn_route_count[r];
+}
+
 int attention_launch(imcui_hip_s* h, const AttnP& p, hipStream_t stream);
 int attention_mx_launch(imcui_hip_s* h, const AttnP& p, hipStream_t stream);  // attention_mx.hip

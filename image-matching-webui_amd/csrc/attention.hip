@@ -241,7 +241,10 @@ __device__ __forceinline__ const void* uniform_ptr(const void* p) {
 // VAR (option "attn_variant"; rounds 3-5 also carried wave-priority schedules 1-3, a double-buffered tile 5 and the un-pipelined
 // schedules 0 / 6 -- all measured within noise or slower, removed in round 6; the option values map onto the two survivors):
 // VAR 4 (AttnP.single, DUSt3R's opt-in `arith = 1`): ONE f16 product per element pair -- only the hi planes of Q / K / V are loaded,
-// staged and multiplied, P is rounded to the nearest f16 (f32 accumulation and an f32 normaliser as before).  Not a parity mode.
+// staged and multiplied, P is rounded to the nearest f16 (f32 accumulation).  The normaliser is the sum of the ROUNDED probabilities, as in VAR 7 below and
+// for the same reason: O stays an exact weighted mean of the values and the rounding of P costs sum_j p_j e_j (v_j - O).  With the sum of the unrounded
+// probabilities (the normaliser of this variant until the float64 case table, tests/test_gpu_attention_variants.py) it cost sum_j p_j e_j v_j: 2^-12 |v| on a
+// peaked row, 30 x the bound below.  Not a parity mode.
 // VAR 7 (option values 6, 7; the audited "reduced-product P.V"): K.Q^T keeps its three products (an error there is an
 // error of the EXPONENT), V^T.P^T runs as (vh + vl) . ph with the probabilities rounded to the nearest f16: two MFMAs per product
 // instead of three (48 -> 40 per key tile) and one v_cvt_pk_f16_f32 per probability pair instead of v_cvt_pkrtz + two v_fma_mix.  The
@@ -560,7 +563,7 @@ __global__ __launch_bounds__(256, 2) void attn_split_kernel(AttnP p) {
                         for (int r = 0; r < 16; ++r) o[f][r] *= alpha;
                 }
             }
-            if constexpr (PV2) {
+            if constexpr (PV2 || SINGLE) {
                 // the probabilities are summed AFTER their rounding to f16 (below, next to the conversion)
 #pragma unroll
                 for (int f = 0; f < 2; ++f)
@@ -584,7 +587,7 @@ __global__ __launch_bounds__(256, 2) void attn_split_kernel(AttnP p) {
             }
         }
         // step (f, t) covers keys 32f + 16t + {4hi..4hi+3, 8+4hi..8+4hi+3}
-        float lsum0 = 0.0f, lsum1 = 0.0f;  // PV2: this tile's sum of the rounded probabilities
+        float lsum0 = 0.0f, lsum1 = 0.0f;  // PV2, SINGLE: this tile's sum of the rounded probabilities
 #pragma unroll
         for (int f = 0; f < 2; ++f)
 #pragma unroll
@@ -605,6 +608,10 @@ __global__ __launch_bounds__(256, 2) void attn_split_kernel(AttnP p) {
                     ph.y = half2_rtn(s[f][8 * t + 2], s[f][8 * t + 3]);
                     ph.z = half2_rtn(s[f][8 * t + 4], s[f][8 * t + 5]);
                     ph.w = half2_rtn(s[f][8 * t + 6], s[f][8 * t + 7]);
+                    lsum0 = fdot2_ones(ph.x, lsum0);
+                    lsum1 = fdot2_ones(ph.y, lsum1);
+                    lsum0 = fdot2_ones(ph.z, lsum0);
+                    lsum1 = fdot2_ones(ph.w, lsum1);
                 } else {
                     split2(s[f][8 * t + 0], s[f][8 * t + 1], ph.x, pl.x);
                     split2(s[f][8 * t + 2], s[f][8 * t + 3], ph.y, pl.y);
@@ -629,7 +636,7 @@ __global__ __launch_bounds__(256, 2) void attn_split_kernel(AttnP p) {
                     }
                 }
             }
-        if constexpr (PV2) l_run += lsum0 + lsum1;
+        if constexpr (PV2 || SINGLE) l_run += lsum0 + lsum1;
     };
 
     const int ntile = (nk + KT - 1) / KT;
@@ -780,7 +787,8 @@ __global__ __launch_bounds__(256) void attn_combine_kernel(AttnP p) {
 }
 
 template <int VAR>
-static void attn_launch_l2d(const AttnP& p, bool split, hipStream_t stream) {
+static void attn_launch_l2d(imcui_hip_s* h, const AttnP& p, bool split, hipStream_t stream) {
+    attn_route_note(h, VAR == 4 ? AR_L2D_SINGLE : (VAR == 7 ? AR_L2D_V7 : AR_L2D_V8), split ? 1 : 0);
     const unsigned nwg = (unsigned)((p.rows_per_seq / 128) * p.heads * p.nseq);
     if (split) {
         hipLaunchKernelGGL((attn_split_kernel<true, VAR, true>), dim3(nwg * (unsigned)ATTN_MAX_CHUNKS(p.rows_per_seq)), dim3(256), 0, stream, p);
@@ -792,6 +800,7 @@ static void attn_launch_l2d(const AttnP& p, bool split, hipStream_t stream) {
 }
 
 int attention_launch(imcui_hip_s* h, const AttnP& p, hipStream_t stream) {
+    h->attn_last_route = ATTN_ROUTE(AR_NONE, 0);
     if (p.rows_per_seq % 128 != 0) return imcui_set_err(h, IMCUI_ERR_ARG, "attention: rows_per_seq=%d must be a multiple of 128", p.rows_per_seq);
     if (p.nseq <= 0) return IMCUI_OK;
     if ((p.heads * p.nseq) % 8 != 0) return imcui_set_err(h, IMCUI_ERR_ARG, "attention: heads*nseq=%d must be a multiple of 8", p.heads * p.nseq);
@@ -808,15 +817,18 @@ int attention_launch(imcui_hip_s* h, const AttnP& p, hipStream_t stream) {
             const int rc = attention_mx_launch(h, p, stream);
             if (rc != IMCUI_OK) return rc;
         } else if (p.single)
-            attn_launch_l2d<4>(p, split, stream);
+            attn_launch_l2d<4>(h, p, split, stream);
         else if (var == 6 || var == 7)
-            attn_launch_l2d<7>(p, split, stream);
+            attn_launch_l2d<7>(h, p, split, stream);
         else
-            attn_launch_l2d<8>(p, split, stream);
-    } else if (h->precision == 1)
+            attn_launch_l2d<8>(h, p, split, stream);
+    } else if (h->precision == 1) {
+        attn_route_note(h, AR_NATLOG, 0);
         hipLaunchKernelGGL((attn_split_kernel<false, 0, false>), grid, dim3(256), 0, stream, p);
-    else
+    } else {
+        attn_route_note(h, AR_EXACT, 0);
         hipLaunchKernelGGL(attn_kernel, grid, dim3(256), 0, stream, p);
+    }
     imcui_prof_end(h, PROF_ATTN, stream);
     IMCUI_CHECK_LAUNCH(h);
     return IMCUI_OK;

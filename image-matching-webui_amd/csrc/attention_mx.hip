@@ -423,6 +423,7 @@ int attention_mx_launch(imcui_hip_s* h, const AttnP& p, hipStream_t stream) {
     if (!p.v6_ready)
         hipLaunchKernelGGL(attn_v6_pack_kernel, dim3((unsigned)(p.nseq * p.heads * (p.rows_per_seq >> 6))), dim3(128), 0, stream, reinterpret_cast<const unsigned short*>(p.V), plane,
                            p.V6, p.cnt, p.active, p.heads, p.rows_per_seq);
+    attn_route_note(h, AR_MX, 0);
     hipLaunchKernelGGL(attn_mx_kernel, dim3((unsigned)((p.rows_per_seq / 128) * p.heads * p.nseq)), dim3(256), 0, stream, p);
     return IMCUI_OK;
 }

@@ -177,6 +177,7 @@ enum {
 };
 
 #define IMCUI_GEMM_ROUTE_SLOTS 320  // GEMM_ROUTE(kind, epi) < 20 x 16 (gemm.h)
+#define IMCUI_ATTN_ROUTE_SLOTS 16   // ATTN_ROUTE(kind, split) < 8 x 2 (attention.h)
 
 // optional per-kernel-class HIP-event timing (bench.py's live roofline measurement)
 enum { PROF_ATTN = 0, PROF_CONV = 1, PROF_GEMM = 2, PROF_NCLS = 3 };
@@ -203,6 +204,9 @@ struct imcui_hip_s {
     // imcui_hip_gemm_route_reset: stored by the launch sites themselves, read by the kernel-variant tests
     int gemm_last_route;
     int gemm_route_count[IMCUI_GEMM_ROUTE_SLOTS];
+    // the same for attention_launch (ATTN_ROUTE of attention.h; imcui_hip_attn_route_reset)
+    int attn_last_route;
+    int attn_route_count[IMCUI_ATTN_ROUTE_SLOTS];
 };
 // scan `rows` x `cols` f32 values (row stride ld; rows of sequence s beyond cnt[s] are padding and skipped) into h->range_flag
 void imcui_range_check(imcui_hip_s* h, const float* x, long rows, int cols, long ld, const int* cnt, int rows_per_seq, hipStream_t s);

@@ -1668,6 +1668,76 @@ def gemm_route_reset(device: torch.device) -> None:
     hd.call(hd.lib.imcui_hip_gemm_route_reset)
 
 
+# ------------------------------------------------------------------ the attention launcher, entered directly (kernel-variant tests)
+# AttnRouteKind of csrc/attention.h: a route is 2 kind + split (imcui_hip_attn_last_route); split = 1: the key-split launch + combine
+ATTN_ROUTE_KINDS = {"none": 0, "exact": 1, "natlog": 2, "l2d_v8": 3, "l2d_v7": 4, "l2d_single": 5, "mx": 6}
+
+
+def attn_route(kind: str, split: bool = False) -> int:
+    return ATTN_ROUTE_KINDS[kind] * 2 + int(bool(split))
+
+
+def attn_route_name(route: int) -> str:
+    kinds = {v: k for k, v in ATTN_ROUTE_KINDS.items()}
+    return f"{kinds.get(route // 2, route // 2)}{'/split' if route % 2 else ''}"
+
+
+class AttnDesc(C.Structure):
+    """ctypes mirror of imcui_hip_attn_desc (include/imcui_hip.h); the CPU suite compares its size with the library's."""
+
+    _fields_ = [("Q", C.c_void_p), ("K", C.c_void_p), ("V", C.c_void_p), ("O", C.c_void_p), ("cnt", C.c_void_p), ("active", C.c_void_p),
+                ("nseq", C.c_int), ("heads", C.c_int), ("rows_per_seq", C.c_int), ("cross", C.c_int), ("log2_domain", C.c_int),
+                ("single", C.c_int), ("variant", C.c_int), ("V6", C.c_void_p), ("V6_bytes", C.c_size_t), ("v6_ready", C.c_int),
+                ("part", C.c_void_p), ("part_bytes", C.c_size_t)]  # fmt: skip
+    DEFAULTS = {"heads": 4, "variant": -1}
+
+
+def attention_probe(device: torch.device, check: bool = True, **fields) -> int:
+    """One launch through attention_launch (imcui_hip_attention_probe_f32) with the descriptor `fields` (tensors become device pointers;
+    V6_bytes / part_bytes default to the sizes of the tensors given as V6 / part).  Returns the route of the launch (ATTN_ROUTE_KINDS);
+    with check=False a refused call returns its negative status instead of raising."""
+    hd = get_handle(device)
+    d = AttnDesc()
+    fields = {**AttnDesc.DEFAULTS, **fields}
+    for k in ("V6", "part"):
+        if isinstance(fields.get(k), torch.Tensor):
+            fields.setdefault(k + "_bytes", fields[k].numel() * fields[k].element_size())
+    for k, v in fields.items():
+        if isinstance(v, torch.Tensor):
+            if v.device.type != "cuda":
+                raise ImcuiHipError(f"attention_probe: field {k} must be a device tensor")
+            v = v.data_ptr()
+        elif v is None:
+            v = 0
+        setattr(d, k, v)
+    if check:
+        hd.launch(hd.lib.imcui_hip_attention_probe_f32, C.byref(d))
+    else:
+        with torch.cuda.device(hd.device_index):
+            rc = hd.lib.imcui_hip_attention_probe_f32(hd.h, C.byref(d), _stream_ptr())
+        if rc != 0:
+            return rc
+    return int(hd.lib.imcui_hip_attn_last_route(hd.h))
+
+
+def attention_part_floats(device: torch.device, S: int, heads: int, rows: int) -> int:
+    return int(get_handle(device).lib.imcui_hip_attention_part_floats(S, heads, rows))
+
+
+def attn_route_counts(device: torch.device) -> dict:
+    """{route: launches} of every attention launch on the device's handle since attn_route_reset."""
+    hd = get_handle(device)
+    n = hd.lib.imcui_hip_attn_route_counts(hd.h, None, 0)
+    buf = (C.c_int * n)()
+    hd.lib.imcui_hip_attn_route_counts(hd.h, buf, n)
+    return {r: c for r, c in enumerate(buf) if c}
+
+
+def attn_route_reset(device: torch.device) -> None:
+    hd = get_handle(device)
+    hd.call(hd.lib.imcui_hip_attn_route_reset)
+
+
 def _split_planes(t: torch.Tensor) -> torch.Tensor:
     """f32 tensor -> [2, ...] f16 (hi, lo) planes, the operand format of the split attention kernel."""
     hi = t.half()

@@ -727,6 +727,37 @@ int imcui_hip_gemm_last_route(const imcui_hip_t* h);
 int imcui_hip_gemm_route_counts(const imcui_hip_t* h, int* out, int n);
 int imcui_hip_gemm_route_reset(imcui_hip_t* h);
 
+/* ---- test entry into the attention launcher (tests/test_gpu_attention_variants.py) -------------------------------------------
+ * Every field of the launcher's parameters (csrc/attention.h, AttnP; meanings there).  Device pointers; unset fields zero except
+ * heads = 4 and variant = -1 (the handle's "attn_variant").  V6_bytes / part_bytes: sizes of the two scratch buffers. */
+typedef struct imcui_hip_attn_desc {
+    const float* Q;
+    const float* K;
+    const float* V;
+    float* O;
+    const int* cnt;
+    const int* active;
+    int nseq, heads, rows_per_seq;
+    int cross, log2_domain, single, variant;
+    unsigned char* V6;
+    size_t V6_bytes;
+    int v6_ready;
+    float* part;
+    size_t part_bytes;
+} imcui_hip_attn_desc;
+/* Copies *d into the kernel parameters and calls the attention launcher unchanged.  Checks of its own: a null handle, descriptor, Q, K,
+ * V, O or cnt is IMCUI_HIP_ERR_ARG; a V6 or part scratch shorter than the launch would use (imcui_hip_attention_mx_scratch_bytes,
+ * 4 * imcui_hip_attention_part_floats) is IMCUI_HIP_ERR_WS.  Nothing is launched by a refused call. */
+int imcui_hip_attention_probe_f32(imcui_hip_t* h, const imcui_hip_attn_desc* d, void* stream);
+size_t imcui_hip_attn_desc_bytes(void);
+/* floats of the key-split scratch (AttnP.part) for S sequences of `rows` rows; 0 for arguments that are not positive */
+size_t imcui_hip_attention_part_floats(int S, int heads, int rows);
+/* Route of the last attention launch on this handle = 2 kind + split (csrc/attention.h AttnRouteKind; 0 = nothing launched), and
+ * launches per route since imcui_hip_attn_route_reset, as for the GEMM above. */
+int imcui_hip_attn_last_route(const imcui_hip_t* h);
+int imcui_hip_attn_route_counts(const imcui_hip_t* h, int* out, int n);
+int imcui_hip_attn_route_reset(imcui_hip_t* h);
+
 #ifdef __cplusplus
 }
 #endif

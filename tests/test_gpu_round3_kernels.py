@@ -190,6 +190,9 @@ def test_plain_projection_token_tiles_are_bitwise_equal(M, N):
 
 
 def test_attention_priority_variants_bitwise():
+    """Option values 0 - 3, 5 and 8 are ONE instantiation since round 6 (attn_split_kernel<true, 8, .>; the wave-priority schedules they
+    named were removed), values 6 and 7 the other (<true, 7, .>: two-product P.V): the bitwise comparison below compares a kernel with
+    itself, and the recorded routes say so.  That the option selects anything is shown by variant 7 differing from variant 8."""
     from imcui_hip import backend
 
     dev = torch.device("cuda:0")
@@ -200,12 +203,23 @@ def test_attention_priority_variants_bitwise():
     q = (torch.randn(S, Hh, R, 64, generator=g) * 0.5).to(dev)
     k = torch.randn(S, Hh, R, 64, generator=g).to(dev)
     v = torch.randn(S, Hh, R, 64, generator=g).to(dev)
-    outs = []
-    for var in (0, 1, 2, 3, 8):  # scheduling only: wave priorities, the pipelined K.Q^T of round 4 (the default)
+    hd = backend.get_handle(dev)
+    outs, routes = {}, {}
+    for var in (0, 1, 2, 3, 5, 8, 6, 7):
         with backend.option(dev, attn_variant=var):
-            outs.append(backend.attention_f32(q, k, v, cnt, True, True).cpu())
-    for o in outs[1:]:
-        assert torch.equal(outs[0], o)
+            outs[var] = backend.attention_f32(q, k, v, cnt, True, True).cpu()
+            routes[var] = int(hd.lib.imcui_hip_attn_last_route(hd.h))
+    print("attn_variant -> route: " + ", ".join(f"{var}: {backend.attn_route_name(r)}" for var, r in routes.items()))
+    for var in (0, 1, 2, 3, 5, 8):
+        assert routes[var] == backend.attn_route("l2d_v8"), (var, backend.attn_route_name(routes[var]))
+    for var in (6, 7):
+        assert routes[var] == backend.attn_route("l2d_v7"), (var, backend.attn_route_name(routes[var]))
+    for var in (1, 2, 3, 8):  # scheduling only: wave priorities, the pipelined K.Q^T of round 4 (the default)
+        assert torch.equal(outs[0], outs[var])
+    assert torch.equal(outs[0], outs[5]) and torch.equal(outs[6], outs[7])
+    valid = torch.cat([outs[7].view(S, R, -1)[s, : int(cnt[s])].reshape(-1) for s in range(S)])
+    valid8 = torch.cat([outs[8].view(S, R, -1)[s, : int(cnt[s])].reshape(-1) for s in range(S)])
+    assert not torch.equal(valid, valid8), "attn_variant = 7 gave the bits of variant 8: the option selects nothing"
 
 
 def test_split_range_check_reports_saturation():
