@@ -419,6 +419,104 @@ class AlikedHIP:
         return out
 
 
+# ------------------------------------------------------------------ SIFT
+SIFT_LAYERS = (3, 4, 5)  # nOctaveLayers (the wrapper's `num_octaves`) csrc/sift.hip is written for: blur radius at most 13
+
+
+def sift_check_args(image_shape, conf: dict) -> None:
+    """Refusals raised before anything is launched (imcui/hloc/extractors/sift.py: backend "opencv" only)."""
+    if len(image_shape) != 4 or image_shape[1] not in (1, 3):
+        raise ValueError(f"SIFT expects an image [B,1,H,W] or [B,3,H,W], got shape {tuple(image_shape)}")
+    if image_shape[2] < 8 or image_shape[3] < 8:
+        raise ValueError(f"SIFT needs images of at least 8 x 8, got {tuple(image_shape[2:])}")
+    backend_name = str(conf.get("backend", "opencv"))
+    if backend_name.startswith("pycolmap"):
+        raise ImcuiHipError(f"SIFT backend '{backend_name}' is not served by the HIP backend: only `opencv` (the default, and what `sift` / `sift-lightglue` use)")
+    if backend_name != "opencv":
+        raise ValueError(f"Unknown backend: {backend_name} not in {{opencv,pycolmap,pycolmap_cpu,pycolmap_cuda}}.")
+    if conf.get("first_octave", -1) != -1:
+        raise ImcuiHipError("SIFT `first_octave` is only read by the pycolmap backends (ignored by `opencv`): leave it at its default -1")
+    if int(conf["num_octaves"]) not in SIFT_LAYERS:
+        raise ImcuiHipError(f"SIFT num_octaves={conf['num_octaves']} (passed to OpenCV as nOctaveLayers) is outside what the HIP kernels serve: {SIFT_LAYERS}")
+    r = conf.get("nms_radius")
+    if r is not None and not 0 <= int(r) <= 64:
+        raise ValueError(f"nms_radius={r} is outside 0..64 (None skips the filter)")
+
+
+def sift_octave_shapes(H: int, W: int) -> list[tuple[int, int]]:
+    """(h, w) of every octave of an H x W image (octave 0 is the doubled image)."""
+    n = load_library().imcui_hip_sift_num_octaves(H, W)
+    out, h, w = [], 2 * H, 2 * W
+    for _ in range(n):
+        if h < 1 or w < 1:
+            break
+        out.append((h, w))
+        h, w = h // 2, w // 2
+    return out
+
+
+class SiftHIP:
+    def __init__(self):
+        self._ws = _Workspace()
+
+    @staticmethod
+    def default_ccap(H: int, W: int) -> int:
+        """Room for the extrema of an image: a quarter of its pixels (structured images have 5-10 %); `forward_checked` retries."""
+        return max(1024, H * W // 4)
+
+    def forward(self, image: torch.Tensor, conf: dict, kcap: int | None = None, ccap: int | None = None, debug: bool = False):
+        """image [B,1|3,H,W] float in [0,1] on the GPU -> fixed-stride outputs, no host synchronisation: keypoints [B,K,2], scores,
+        scales, oris [B,K], descriptors [B,K,128], num_keypoints [B] int32, status [1] int32 (bit 1: `kcap` too small, bit 2: `ccap` too
+        small), counts [B,3] int32 (extrema, oriented key-points, survivors: unclipped).  debug adds pyramid (list per octave of
+        [B,layers+3,h,w] views), extrema, refined, hist, table, desc_raw."""
+        sift_check_args(tuple(image.shape), conf)
+        hd = get_handle(image.device)
+        lib = hd.lib
+        image = image.contiguous().float()
+        B, C, H, W = image.shape
+        layers = int(conf["num_octaves"])
+        maxk = conf.get("max_keypoints")
+        maxk = int(maxk) if maxk is not None and int(maxk) > 0 else 0
+        r = conf.get("nms_radius")
+        r = -1 if r is None else int(r)
+        if ccap is None:
+            ccap = self.default_ccap(H, W)
+        if kcap is None:
+            kcap = min(maxk, ccap) if maxk else ccap
+        ccap = int(ccap)
+        kcap = max(1, min(int(kcap), ccap))
+        nbytes = lib.imcui_hip_sift_workspace_bytes(B, H, W, layers, ccap, kcap)
+        if nbytes == 0:
+            raise ImcuiHipError(f"SIFT: unsupported launch (B={B}, {H}x{W}, layers={layers}, ccap={ccap}, kcap={kcap})")
+        dev = image.device
+        f32, i32 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.int32, device=dev)
+        kpts = torch.empty((B, kcap, 2), **f32)
+        scores, scales, oris = (torch.empty((B, kcap), **f32) for _ in range(3))
+        desc = torch.empty((B, kcap, 128), **f32)
+        nk, status, counts = torch.empty((B,), **i32), torch.empty((1,), **i32), torch.empty((B, 3), **i32)
+        dbg = {}
+        if debug:
+            dbg = dict(pyramid=torch.empty((lib.imcui_hip_sift_pyramid_floats(B, H, W, layers),), **f32), extrema=torch.empty((B, ccap), **i32),
+                       refined=torch.empty((B, ccap, 16), **f32), hist=torch.empty((B, ccap, 36), **f32), table=torch.empty((B, ccap, 12), **f32),
+                       desc_raw=torch.empty((B, kcap, 128), **f32))  # fmt: skip
+        with self._ws.use(nbytes, dev) as ws:
+            hd.launch(
+                lib.imcui_hip_sift_forward, _ptr(image), B, C, H, W, layers, float(conf["detection_threshold"]), float(conf["edge_threshold"]), maxk, r, maxk,
+                int(bool(conf["rootsift"])), ccap, kcap, _ptr(kpts), _ptr(scores), _ptr(scales), _ptr(oris), _ptr(desc), _ptr(nk), _ptr(status), _ptr(counts),
+                _ptr(dbg.get("pyramid")), _ptr(dbg.get("extrema")), _ptr(dbg.get("refined")), _ptr(dbg.get("hist")), _ptr(dbg.get("table")),
+                _ptr(dbg.get("desc_raw")), _ptr(ws), ws.numel(),
+            )  # fmt: skip
+        out = {"keypoints": kpts, "scores": scores, "scales": scales, "oris": oris, "descriptors": desc, "num_keypoints": nk, "status": status, "counts": counts}
+        if debug:
+            flat, off, pyr = dbg.pop("pyramid"), 0, []
+            for h, w in sift_octave_shapes(H, W):
+                n = B * (layers + 3) * h * w
+                pyr.append(flat[off : off + n].view(B, layers + 3, h, w))
+                off += n
+            out.update(dbg, pyramid=pyr)
+        return out
+
+
 # ------------------------------------------------------------------ LightGlue
 def lightglue_tensor_names() -> list[str]:
     lib = load_library()

@@ -298,6 +298,7 @@ def main(conf: Dict, image_dir: Path, export_dir: Optional[Path] = None, as_half
             out = model.forward_batched(batch)
             counts = out["num_keypoints"].tolist()
         kp, sc, de = out["keypoints"].cpu().numpy(), out["scores"].cpu().numpy(), out["descriptors"].cpu().numpy()
+        extra = {k: out[k].cpu().numpy() for k in ("scales", "oris") if k in out}  # extractors with scale / orientation (SIFT), reference :216-217
         with open_h5(feature_path, "a") as fd:
             for b, (name, img, original_size) in enumerate(items):
                 n = counts[b]
@@ -309,6 +310,10 @@ def main(conf: Dict, image_dir: Path, export_dir: Optional[Path] = None, as_half
                     "descriptors": np.ascontiguousarray(de[b, :n].T),  # [D, N] like the reference plugin
                     "image_size": original_size,
                 }
+                if "scales" in extra:
+                    pred["scales"] = extra["scales"][b, :n] * scales.mean()
+                if "oris" in extra:
+                    pred["oris"] = extra["oris"][b, :n]
                 uncertainty = noise * scales.mean()
                 if as_half:
                     pred = {k: (v.astype(np.float16) if v.dtype == np.float32 else v) for k, v in pred.items()}

@@ -184,6 +184,13 @@ def collate(pairs, idxs, feats_q, feats_r, device):
                 s[b, :n] = _as_tensor(f["scores"], device)
             d[b, :n] = _as_tensor(f["descriptors"], device).t()
         out[f"keypoints{side}"], out[f"scores{side}"], out[f"descriptors{side}"] = k, s, d
+        for name in ("scales", "oris"):  # reference match_features.py:227-234: forwarded when the feature file holds them
+            if all(name in f for f in fs):
+                t = torch.zeros(B, ncap, device=device)
+                for b, (f, n) in enumerate(zip(fs, cs)):
+                    if n:
+                        t[b, :n] = _as_tensor(f[name], device)
+                out[f"{name}{side}"] = t
         out[f"n{side}"] = torch.tensor(cs, dtype=torch.int32, device=device)
     return out, c0, c1
 
@@ -193,6 +200,12 @@ def _call_batched(model, batch: dict, size0, size1) -> dict:
     import inspect
 
     params = inspect.signature(model.forward_batched).parameters
+    if getattr(model, "add_scale_ori", False) and "scales_oris" in params:  # sift-lightglue: (x, y, scale, orientation) positional encoding
+        missing = [k for k in ("scales0", "oris0", "scales1", "oris1") if k not in batch]
+        if missing:
+            raise ValueError(f"the matcher was trained with add_scale_ori but the features hold no {missing}")
+        return model.forward_batched(batch["keypoints0"], batch["keypoints1"], batch["descriptors0"], batch["descriptors1"], batch["n0"], batch["n1"],
+                                     size0, size1, scales_oris=(batch["scales0"], batch["oris0"], batch["scales1"], batch["oris1"]))  # fmt: skip
     if "scores0" in params:
         return model.forward_batched(batch["keypoints0"], batch["keypoints1"], batch["scores0"], batch["scores1"], batch["descriptors0"],
                                      batch["descriptors1"], batch["n0"], batch["n1"], size0, size1)  # fmt: skip

@@ -71,6 +71,13 @@ SIGNATURES = {
         C.c_int,
         [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_float, C.c_int, C.c_int] + [C.c_void_p] * 9 + [C.c_void_p, C.c_size_t, C.c_void_p],
     ),
+    "imcui_hip_sift_num_octaves": (C.c_int, [C.c_int] * 2),
+    "imcui_hip_sift_pyramid_floats": (C.c_size_t, [C.c_int] * 4),
+    "imcui_hip_sift_workspace_bytes": (C.c_size_t, [C.c_int] * 6),
+    "imcui_hip_sift_forward": (
+        C.c_int,
+        [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_float] * 2 + [C.c_int] * 6 + [C.c_void_p] * 14 + [C.c_void_p, C.c_size_t, C.c_void_p],
+    ),
     "imcui_hip_superpoint_packed_floats": (C.c_size_t, []),
     "imcui_hip_superpoint_pack_weights": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p]),
     "imcui_hip_superpoint_workspace_bytes": (C.c_size_t, [C.c_int] * 4),

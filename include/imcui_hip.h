@@ -183,6 +183,42 @@ int imcui_hip_aliked_forward(imcui_hip_t* h, const float* packed, const float* i
                              int max_keypoints, int kcap, float* keypoints, float* scores, float* descriptors, int* num_keypoints, int* status,
                              float* score_map, float* keypoints_norm, float* dbg_x3, float* dbg_x4, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- SIFT (zoo entry sift-lightglue, and `sift` + NN; imcui/hloc/extractors/sift.py, backend "opencv") ------------------- */
+/* OpenCV 4.x SIFT_create(contrastThreshold, nfeatures, edgeThreshold, nOctaveLayers = `layers`; sigma 1.6, first octave -1, float
+ * pipeline) -> detectAndCompute (sift.py:61-78), then `filter_dog_point` (:19-52), the score top-k (:188-193) and
+ * `sift_to_rootsift` (:55-58).  No weights.  OpenCV's sources are restated from its documentation (tests/sift_reference.py is the
+ * written definition); the angle of a gradient is atan2, not cv2's fastAtan2 polynomial.
+ * Octaves of an H x W image: cvRound(log2(min(2W, 2H)) - 2) + 1; octave o is (2H >> o) x (2W >> o) with layers + 3 levels. */
+int imcui_hip_sift_num_octaves(int H, int W);
+/* Floats of the Gaussian pyramid of B images: octave after octave, each a block [B][layers + 3][h_o][w_o]. */
+size_t imcui_hip_sift_pyramid_floats(int B, int H, int W, int layers);
+/* Scratch of imcui_hip_sift_forward: the pyramid, one 2H x 2W plane and the candidate lists (ccap entries per image). */
+size_t imcui_hip_sift_workspace_bytes(int B, int H, int W, int layers, int ccap, int kcap);
+/* image [dev, B,C,H,W] float in [0,1], C = 1 or 3 (gray = 0.299 R + 0.587 G + 0.114 B in float, kornia's rgb_to_grayscale), then
+ * `(x * 255.0)` truncated to uint8 (sift.py:158).  layers 3..5; H, W >= 8.
+ * nfeatures > 0: OpenCV's retainBest (ties stay); nms_radius < 0 skips `filter_dog_point` (the wrapper's `nms_radius: None`), 0 keeps
+ * the highest score and then the lowest |angle| of a pixel, > 0 adds the max-pool NMS; max_keypoints > 0: the max_keypoints highest
+ * scores (ties to the earlier key-point).  rootsift != 0: RootSIFT rows, else the 0..255 integers as float.
+ * Order of the outputs: detection order (octave, layer, row, column, orientation bin) of the survivors, NOT sorted by score.
+ * Outputs (device; capacity kcap per image, rows beyond num_keypoints[b] are not written):
+ *   keypoints [B,kcap,2] (x, y) pixels;  scores (|contrast|), scales (KeyPoint.size), oris (radians) [B,kcap];
+ *   descriptors [B,kcap,128];  num_keypoints [B];  status [1]: bit 1 = more survivors than kcap, bit 2 = more extrema or more
+ *   oriented key-points than ccap (call again with larger capacities; `counts` tells how large)
+ *   counts [B,3] optional: extrema found, table rows (oriented key-points), survivors -- the true numbers, not clipped
+ * Optional outputs for the tests:
+ *   dbg_pyramid [imcui_hip_sift_pyramid_floats];  dbg_extrema [B,ccap] int: index (octave, layer - 1, row, column) of each extremum
+ *   in the image's search space;  dbg_refined [B,ccap,16]: valid, octave, layer, r, c, xc, xr, xi, contrast (signed), size, x, y,
+ *   edge quantity tr^2 e - (e+1)^2 det, det, 0, 0;  dbg_hist [B,ccap,36]: smoothed orientation histogram of every valid candidate
+ *   dbg_table [B,ccap,12]: the key-point table before removeDuplicated / retainBest / halving and the wrapper stages: octave, layer,
+ *   r, c, xc, xr, xi, response, size, angle (degrees), x, y (size, x, y in the doubled image's units)
+ *   dbg_desc_raw [B,kcap,128]: the descriptor after x 512 / norm, before saturate_cast
+ * No float atomics and no host synchronisation: results are bitwise reproducible and the call is graph-capturable. */
+int imcui_hip_sift_forward(imcui_hip_t* h, const float* image, int B, int C, int H, int W, int layers, float contrast_threshold,
+                           float edge_threshold, int nfeatures, int nms_radius, int max_keypoints, int rootsift, int ccap, int kcap,
+                           float* keypoints, float* scores, float* scales, float* oris, float* descriptors, int* num_keypoints, int* status,
+                           int* counts, float* dbg_pyramid, int* dbg_extrema, float* dbg_refined, float* dbg_hist, float* dbg_table,
+                           float* dbg_desc_raw, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- LightGlue --------------------------------------------- */
 /* Host-side packing of the upstream state dict (9 layers, dim 256, 4 heads).  `tensors` holds the
  * host pointers of imcui_hip_lightglue_num_tensors() tensors; tensor i is the upstream state-dict
