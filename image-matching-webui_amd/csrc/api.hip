@@ -559,3 +559,53 @@ extern "C" int imcui_hip_attn_route_reset(imcui_hip_t* h) {
     h->attn_last_route = 0;
     return IMCUI_OK;
 }
+
+extern "C" size_t imcui_hip_conv_desc_bytes(void) { return sizeof(imcui_hip_conv_desc); }
+extern "C" int imcui_hip_conv_probe_f32(imcui_hip_t* h, const imcui_hip_conv_desc* d, void* stream) {
+    if (h) h->conv_last_route = 0;
+    if (!h || !d || !d->in) return imcui_set_err(h, IMCUI_ERR_ARG, "conv_probe: null argument");
+    hipStream_t s = (hipStream_t)stream;
+    switch (d->entry) {
+        case 0:
+            if (!d->wp || !d->bias || !d->out) return imcui_set_err(h, IMCUI_ERR_ARG, "conv_probe: null argument (entry 0)");
+            return conv3x3_launch(h, d->in, d->wp, d->bias, d->out, d->B, d->H, d->W, d->Cin, d->Cout, d->relu, d->pool, s);
+        case 1: {
+            // `out` and the head's pointers are the launcher's to refuse
+            if (!d->wh || (!d->wl && !d->single) || !d->wscale || !d->bias) return imcui_set_err(h, IMCUI_ERR_ARG, "conv_probe: null argument (entry 1)");
+            ConvHead hd;
+            hd.w = d->head_w;
+            hd.b = d->head_b;
+            hd.pts = d->head_pts;
+            hd.conf = d->head_conf;
+            hd.raw = d->head_raw;
+            return conv3x3_split_launch(h, d->in, d->wh, d->wl, d->wscale, d->bias, d->out, d->B, d->H, d->W, d->Cin, d->Cout, d->relu, d->pool, s, d->resid,
+                                        d->cin_stride, d->cout_live, d->single, d->resid2, d->head ? &hd : nullptr);
+        }
+        case 2:
+            if (!d->w1a || !d->b1a || !d->wh || !d->wl || !d->wscale || !d->bias || !d->out)
+                return imcui_set_err(h, IMCUI_ERR_ARG, "conv_probe: null argument (entry 2)");
+            return conv1ab_fused_split_launch(h, d->in, d->w1a, d->b1a, d->wh, d->wl, d->wscale, d->bias, d->out, d->B, d->H, d->W, d->pool, s);
+        case 3:
+            if (!d->w1a || !d->b1a || !d->out) return imcui_set_err(h, IMCUI_ERR_ARG, "conv_probe: null argument (entry 3)");
+            return conv1a_launch(h, d->in, d->w1a, d->b1a, d->out, d->B, d->H, d->W, s);
+    }
+    return imcui_set_err(h, IMCUI_ERR_ARG, "conv_probe: entry %d", d->entry);
+}
+extern "C" int imcui_hip_conv_last_route(const imcui_hip_t* h) { return h ? h->conv_last_route : -1; }
+extern "C" int imcui_hip_conv_route_counts(const imcui_hip_t* h, int* out, int n) {
+    if (!h || (!out && n > 0)) return -1;
+    for (int i = 0; i < n && i < IMCUI_CONV_ROUTE_SLOTS; ++i) out[i] = h->conv_route_count[i];
+    return IMCUI_CONV_ROUTE_SLOTS;
+}
+extern "C" int imcui_hip_conv_route_features(const imcui_hip_t* h, int* out, int n) {
+    if (!h || (!out && n > 0)) return -1;
+    for (int i = 0; i < n && i < IMCUI_CONV_ROUTE_SLOTS; ++i) out[i] = h->conv_route_features[i];
+    return IMCUI_CONV_ROUTE_SLOTS;
+}
+extern "C" int imcui_hip_conv_route_reset(imcui_hip_t* h) {
+    if (!h) return IMCUI_ERR_ARG;
+    memset(h->conv_route_count, 0, sizeof h->conv_route_count);
+    memset(h->conv_route_features, 0, sizeof h->conv_route_features);
+    h->conv_last_route = 0;
+    return IMCUI_OK;
+}

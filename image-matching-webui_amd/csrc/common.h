@@ -178,6 +178,7 @@ enum {
 
 #define IMCUI_GEMM_ROUTE_SLOTS 320  // GEMM_ROUTE(kind, epi) < 20 x 16 (gemm.h)
 #define IMCUI_ATTN_ROUTE_SLOTS 16   // ATTN_ROUTE(kind, split) < 8 x 2 (attention.h)
+#define IMCUI_CONV_ROUTE_SLOTS 16   // CONV_ROUTE(kind) < 16 (conv.h)
 
 // optional per-kernel-class HIP-event timing (bench.py's live roofline measurement)
 enum { PROF_ATTN = 0, PROF_CONV = 1, PROF_GEMM = 2, PROF_NCLS = 3 };
@@ -207,6 +208,11 @@ struct imcui_hip_s {
     // the same for attention_launch (ATTN_ROUTE of attention.h; imcui_hip_attn_route_reset)
     int attn_last_route;
     int attn_route_count[IMCUI_ATTN_ROUTE_SLOTS];
+    // the same for the 3x3 convolution launchers of conv.hip (CONV_ROUTE of conv.h; imcui_hip_conv_route_reset), plus the OR of the
+    // fused features (ConvFeature) every launch of a route ran with
+    int conv_last_route;
+    int conv_route_count[IMCUI_CONV_ROUTE_SLOTS];
+    int conv_route_features[IMCUI_CONV_ROUTE_SLOTS];
 };
 // scan `rows` x `cols` f32 values (row stride ld; rows of sequence s beyond cnt[s] are padding and skipped) into h->range_flag
 void imcui_range_check(imcui_hip_s* h, const float* x, long rows, int cols, long ld, const int* cnt, int rows_per_seq, hipStream_t s);

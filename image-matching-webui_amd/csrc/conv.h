@@ -2,6 +2,45 @@
 #pragma once
 #include "common.h"
 
+// Route of a launch: which kernel instantiation the launchers below chose, CONV_ROUTE(kind), and the fused features it ran with (a
+// mask of ConvFeature bits: here most of the hand-written index arithmetic sits in the features, not in the choice of kernel).  The
+// launch sites store both in the handle (imcui_hip_conv_last_route / _route_counts / _route_features), so the report cannot disagree
+// with what ran; host code only.  Values are part of the test interface (imcui_hip/backend.py CONV_ROUTE_KINDS, CONV_FEATURES).
+enum ConvRouteKind {
+    CR_NONE = 0,             // nothing launched (a refused call, an empty map)
+    CR_F32 = 1,              // conv3x3_kernel (exact f32)
+    CR_SPLIT_N2 = 2,         // conv3x3_split_kernel<false, 2>
+    CR_SPLIT_N4 = 3,         // conv3x3_split_kernel<false, 4>
+    CR_SPLIT_N2_SINGLE = 4,  // conv3x3_split_kernel<false, 2, true>
+    CR_SPLIT_N4_SINGLE = 5,  // conv3x3_split_kernel<false, 4, true>
+    CR_TALL = 6,             // conv3x3_tall_kernel<false>
+    CR_TALL_SINGLE = 7,      // conv3x3_tall_kernel<false, true>
+    CR_FUSED_8ROW = 8,       // conv3x3_split_kernel<true, 2>
+    CR_FUSED_TALL = 9,       // conv3x3_tall_kernel<true>
+    CR_CONV1A = 10,          // conv1a_kernel
+    CR_NKIND = 11
+};
+enum ConvFeature {
+    CF_POOL = 1,            // fused 2x2 max-pool
+    CF_RESID = 2,           // residual map added before the activation
+    CF_RESID2 = 4,          // second residual map
+    CF_LEAKY = 8,           // activation code 2
+    CF_RELU_IN = 16,        // relu bit 2: ReLU on the input while it is staged
+    CF_CIN_STRIDE = 32,     // cin_stride != Cin
+    CF_COUT_LIVE = 64,      // cout_live < Cout
+    CF_HEAD = 128,          // fused point-map head
+    CF_HEAD_NO_OUT = 256,   // ... without the 128-channel map
+    CF_HEAD_RAW = 512       // ... with the raw 4-channel output
+};
+#define CONV_ROUTE(kind) (kind)
+static_assert(CR_NKIND <= IMCUI_CONV_ROUTE_SLOTS, "route table of imcui_hip_s too small");
+static inline void conv_route_note(imcui_hip_s* h, int kind, int features) {
+    const int r = CONV_ROUTE(kind);
+    h->conv_last_route = r;
+    ++h->conv_route_count[r];
+    h->conv_route_features[r] |= features;
+}
+
 // 3x3, pad 1, stride 1, +bias, +ReLU, optional fused 2x2/2 max-pool.
 // in  : [B, H, W, Cin]  (NHWC), Cin % 32 == 0
 // wp  : packed weights  [Cin/32][9 taps][8 cq][Cout][4]   (see pack_conv3x3)

@@ -124,6 +124,7 @@ __global__ __launch_bounds__(256) void conv3x3_kernel(const float* __restrict__ 
 
 int conv3x3_launch(imcui_hip_s* h, const float* in, const float* wp, const float* bias, float* out, int B, int H, int W,
                    int Cin, int Cout, int relu, int pool, hipStream_t stream) {
+    h->conv_last_route = CONV_ROUTE(CR_NONE);
     if (Cin % 32 != 0 || Cout % 64 != 0)
         return imcui_set_err(h, IMCUI_ERR_ARG, "conv3x3: Cin=%d must be a multiple of 32, Cout=%d of 64", Cin, Cout);
     if (pool && ((H | W) & 1)) return imcui_set_err(h, IMCUI_ERR_ARG, "conv3x3: pooled layer needs even H,W (%dx%d)", H, W);
@@ -133,6 +134,7 @@ int conv3x3_launch(imcui_hip_s* h, const float* in, const float* wp, const float
     imcui_prof_begin(h, PROF_CONV, stream);
     hipLaunchKernelGGL(conv3x3_kernel, dim3((unsigned)nwg), dim3(256), 0, stream, in, wp, bias, out, H, W, Cin, Cout,
                        tiles_x, tiles_y, relu, pool);
+    conv_route_note(h, CR_F32, pool ? CF_POOL : 0);
     imcui_prof_end(h, PROF_CONV, stream);
     IMCUI_CHECK_LAUNCH(h);
     return IMCUI_OK;
@@ -825,6 +827,7 @@ int conv3x3_split_launch(imcui_hip_s* h, const float* in, const unsigned short* 
                          const float* wscale, const float* bias, float* out, int B, int H, int W, int Cin, int Cout,
                          int relu, int pool, hipStream_t stream, const float* resid, int cin_stride, int cout_live, int single, const float* resid2,
                          const ConvHead* head) {
+    h->conv_last_route = CONV_ROUTE(CR_NONE);
     if (cin_stride <= 0) cin_stride = Cin;
     if (cout_live <= 0 || cout_live > Cout) cout_live = Cout;
     if (cin_stride < Cin || cin_stride % 4 != 0) return imcui_set_err(h, IMCUI_ERR_ARG, "conv3x3: pixel stride %d for %d input channels", cin_stride, Cin);
@@ -837,6 +840,9 @@ int conv3x3_split_launch(imcui_hip_s* h, const float* in, const unsigned short* 
     if (Cin % 32 != 0 || Cout % 64 != 0)
         return imcui_set_err(h, IMCUI_ERR_ARG, "conv3x3: Cin=%d must be a multiple of 32, Cout=%d of 64", Cin, Cout);
     if (pool && ((H | W) & 1)) return imcui_set_err(h, IMCUI_ERR_ARG, "conv3x3: pooled layer needs even H,W (%dx%d)", H, W);
+    const int feat = (pool ? CF_POOL : 0) | (resid ? CF_RESID : 0) | (resid2 ? CF_RESID2 : 0) | ((relu & 3) == 2 ? CF_LEAKY : 0) | ((relu & 4) ? CF_RELU_IN : 0) |
+                     (cin_stride != Cin ? CF_CIN_STRIDE : 0) | (cout_live < Cout ? CF_COUT_LIVE : 0) |
+                     (head ? CF_HEAD | (out ? 0 : CF_HEAD_NO_OUT) | (head->raw ? CF_HEAD_RAW : 0) : 0);
     const int tiles_x = cdiv(W, STW);
     // 128 output channels per workgroup when the layer has them (fewer LDS fragment reads and barriers per MFMA)
     bool narrow_only = conv_narrow_env(h);  // A/B switch
@@ -856,6 +862,7 @@ int conv3x3_split_launch(imcui_hip_s* h, const float* in, const unsigned short* 
         else
             hipLaunchKernelGGL((conv3x3_tall_kernel<false>), dim3((unsigned)nwg_t), dim3(256), 0, stream, in, wh, wl, wscale, bias, out, H, W, Cin, Cout,
                                tiles_x, tiles_t, relu, pool, resid, resid2, cin_stride);
+        conv_route_note(h, single ? CR_TALL_SINGLE : CR_TALL, feat);
         imcui_prof_end(h, PROF_CONV, stream);
         IMCUI_CHECK_LAUNCH(h);
         return IMCUI_OK;
@@ -877,6 +884,7 @@ int conv3x3_split_launch(imcui_hip_s* h, const float* in, const unsigned short* 
     else
         hipLaunchKernelGGL((conv3x3_split_kernel<false, 2>), dim3((unsigned)nwg), dim3(256), 0, stream, in, wh, wl, wscale, bias, out, H, W, Cin, Cout,
                            tiles_x, tiles_y, relu, pool, resid, resid2, cin_stride, cout_live, head ? *head : ConvHead{});
+    conv_route_note(h, wide ? (single ? CR_SPLIT_N4_SINGLE : CR_SPLIT_N4) : (single ? CR_SPLIT_N2_SINGLE : CR_SPLIT_N2), feat);
     imcui_prof_end(h, PROF_CONV, stream);
     IMCUI_CHECK_LAUNCH(h);
     return IMCUI_OK;
@@ -885,6 +893,7 @@ int conv3x3_split_launch(imcui_hip_s* h, const float* in, const unsigned short* 
 int conv1ab_fused_split_launch(imcui_hip_s* h, const float* image, const float* w1a, const float* b1a,
                                const unsigned short* wh, const unsigned short* wl, const float* wscale, const float* bias,
                                float* out, int B, int H, int W, int pool, hipStream_t stream) {
+    h->conv_last_route = CONV_ROUTE(CR_NONE);
     if (pool && ((H | W) & 1)) return imcui_set_err(h, IMCUI_ERR_ARG, "conv1ab: pooled layer needs even H,W (%dx%d)", H, W);
     const bool tall = conv_tall_mode(h) >= 1;
     const int tiles_x = cdiv(W, STW), tiles_y = cdiv(H, tall ? TTH : STH);
@@ -897,6 +906,7 @@ int conv1ab_fused_split_launch(imcui_hip_s* h, const float* image, const float* 
     else
         hipLaunchKernelGGL((conv3x3_split_kernel<true, 2>), dim3((unsigned)nwg), dim3(256), 0, stream, image, wh, wl, wscale, bias, out, H,
                            W, 64, 64, tiles_x, tiles_y, 1, pool, w1a, b1a, 64, 64, ConvHead{});
+    conv_route_note(h, tall ? CR_FUSED_TALL : CR_FUSED_8ROW, pool ? CF_POOL : 0);
     imcui_prof_end(h, PROF_CONV, stream);
     IMCUI_CHECK_LAUNCH(h);
     return IMCUI_OK;
@@ -944,11 +954,13 @@ __global__ __launch_bounds__(256) void conv1a_kernel(const float* __restrict__ i
 
 int conv1a_launch(imcui_hip_s* h, const float* in, const float* w, const float* bias, float* out, int B, int H, int W,
                   hipStream_t stream) {
+    h->conv_last_route = CONV_ROUTE(CR_NONE);
     const long npix = (long)B * H * W;
     if (npix <= 0) return IMCUI_OK;
     long blocks = (npix + 15) / 16;
     if (blocks > 256 * 32) blocks = 256 * 32;
     hipLaunchKernelGGL(conv1a_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, in, w, bias, out, H, W, npix);
+    conv_route_note(h, CR_CONV1A, 0);
     IMCUI_CHECK_LAUNCH(h);
     return IMCUI_OK;
 }

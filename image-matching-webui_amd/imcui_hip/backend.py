@@ -1836,6 +1836,131 @@ def attn_route_reset(device: torch.device) -> None:
     hd.call(hd.lib.imcui_hip_attn_route_reset)
 
 
+# ------------------------------------------------------------------ the 3x3 convolution launchers, entered directly (kernel-variant tests)
+# ConvRouteKind / ConvFeature of csrc/conv.h (imcui_hip_conv_last_route, imcui_hip_conv_route_features)
+CONV_ROUTE_KINDS = {"none": 0, "f32": 1, "split_n2": 2, "split_n4": 3, "split_n2_single": 4, "split_n4_single": 5, "tall": 6,
+                    "tall_single": 7, "fused_8row": 8, "fused_tall": 9, "conv1a": 10}  # fmt: skip
+CONV_FEATURES = {"pool": 1, "resid": 2, "resid2": 4, "leaky": 8, "relu_in": 16, "cin_stride": 32, "cout_live": 64, "head": 128,
+                 "head_no_out": 256, "head_raw": 512}  # fmt: skip
+CONV_ENTRIES = {"f32": 0, "split": 1, "fused": 2, "conv1a": 3}
+
+
+def conv_route(kind: str) -> int:
+    return CONV_ROUTE_KINDS[kind]
+
+
+def conv_route_name(route: int) -> str:
+    return {v: k for k, v in CONV_ROUTE_KINDS.items()}.get(route, str(route))
+
+
+def conv_feature_names(mask: int) -> list:
+    return [k for k, v in CONV_FEATURES.items() if mask & v]
+
+
+class ConvDesc(C.Structure):
+    """ctypes mirror of imcui_hip_conv_desc (include/imcui_hip.h); the CPU suite compares its size with the library's."""
+
+    _fields_ = [("entry", C.c_int), ("inp", C.c_void_p), ("wp", C.c_void_p), ("wh", C.c_void_p), ("wl", C.c_void_p), ("wscale", C.c_void_p),
+                ("bias", C.c_void_p), ("out", C.c_void_p), ("B", C.c_int), ("H", C.c_int), ("W", C.c_int), ("Cin", C.c_int), ("Cout", C.c_int),
+                ("relu", C.c_int), ("pool", C.c_int), ("resid", C.c_void_p), ("resid2", C.c_void_p), ("cin_stride", C.c_int),
+                ("cout_live", C.c_int), ("single", C.c_int), ("head", C.c_int), ("head_w", C.c_void_p), ("head_b", C.c_void_p),
+                ("head_pts", C.c_void_p), ("head_conf", C.c_void_p), ("head_raw", C.c_void_p), ("w1a", C.c_void_p), ("b1a", C.c_void_p)]  # fmt: skip
+
+
+class ConvWeights:
+    """A 3x3 layer (host OIHW weights, bias) in the operand formats of csrc/conv.hip, on `device`: the packed f32 layout of
+    conv3x3_kernel (wp), the pre-split f16 hi / lo planes of w * 2^e (wh / wl) with wscale = 2^-e, and the bias.
+    cout_pad: the layer is zero-padded to that many output channels (zero weights and bias: what cout_live skips);
+    cin_used: only the first cin_used input channels are packed (the stored map has more: cin_stride)."""
+
+    def __init__(self, w_oihw, bias, device, cout_pad=None, cin_used=None):
+        w = torch.as_tensor(w_oihw).float().cpu()
+        b = torch.as_tensor(bias).float().cpu()
+        if cin_used is not None:
+            w = w[:, :cin_used]
+        if cout_pad is not None and cout_pad > w.shape[0]:
+            w = torch.cat([w, torch.zeros(cout_pad - w.shape[0], *w.shape[1:])])
+            b = torch.cat([b, torch.zeros(cout_pad - b.shape[0])])
+        self.Cout, self.Cin = w.shape[0], w.shape[1]
+        if self.Cin % 32 or self.Cout % 64 or tuple(w.shape[2:]) != (3, 3):
+            raise ImcuiHipError(f"ConvWeights: [{self.Cout}, {self.Cin}, {tuple(w.shape[2:])}] is no layer of conv.hip (Cin % 32, Cout % 64, 3x3)")
+        lib = load_library()
+        wh = _as_f32_host(w)
+        n = self.Cout * self.Cin * 9
+        packed, hi, lo = np.zeros(n, dtype=np.float32), np.zeros(n, dtype=np.uint16), np.zeros(n, dtype=np.uint16)
+        if lib.imcui_hip_conv3x3_pack(wh.ctypes.data, self.Cout, self.Cin, packed.ctypes.data) != 0:
+            raise ImcuiHipError("conv3x3_pack failed")
+        self.scale = float(lib.imcui_hip_conv3x3_pack_split(wh.ctypes.data, self.Cout, self.Cin, hi.ctypes.data, lo.ctypes.data))
+        if self.scale == 0.0:
+            raise ImcuiHipError("conv3x3_pack_split failed")
+        self.w_oihw, self.bias_host, self.packed_host, self.hi_host, self.lo_host = w, b, packed, hi, lo
+        self.wp = torch.from_numpy(packed).to(device)
+        self.wh = torch.from_numpy(hi.view(np.int16)).to(device)
+        self.wl = torch.from_numpy(lo.view(np.int16)).to(device)
+        self.wscale = torch.tensor([self.scale], dtype=torch.float32, device=device)
+        self.bias = b.to(device)
+
+    @staticmethod
+    def first_layer(w_oihw) -> torch.Tensor:
+        """[64, 1, 3, 3] -> [9 taps][64] (pack_conv1a), host."""
+        return torch.as_tensor(w_oihw).float().cpu().reshape(64, 9).t().contiguous()
+
+    def fields(self, split: bool) -> dict:
+        if split:
+            return {"wh": self.wh, "wl": self.wl, "wscale": self.wscale, "bias": self.bias}
+        return {"wp": self.wp, "bias": self.bias}
+
+
+def conv_probe(device: torch.device, check: bool = True, **fields) -> int:
+    """One launch through a launcher of csrc/conv.h (imcui_hip_conv_probe_f32) with the descriptor `fields` (tensors become device
+    pointers, `entry` may be a CONV_ENTRIES name).  Returns the route of the launch (CONV_ROUTE_KINDS); with check=False a refused call
+    returns its negative status instead of raising."""
+    hd = get_handle(device)
+    d = ConvDesc()
+    for k, v in fields.items():
+        if k == "entry" and isinstance(v, str):
+            v = CONV_ENTRIES[v]
+        if isinstance(v, torch.Tensor):
+            if v.device.type != "cuda":
+                raise ImcuiHipError(f"conv_probe: field {k} must be a device tensor")
+            v = v.data_ptr()
+        elif v is None:
+            v = 0
+        setattr(d, k, v)
+    if check:
+        hd.launch(hd.lib.imcui_hip_conv_probe_f32, C.byref(d))
+    else:
+        with torch.cuda.device(hd.device_index):
+            rc = hd.lib.imcui_hip_conv_probe_f32(hd.h, C.byref(d), _stream_ptr())
+        if rc != 0:
+            return rc
+    return int(hd.lib.imcui_hip_conv_last_route(hd.h))
+
+
+def _conv_route_table(device: torch.device, fn_name: str) -> dict:
+    hd = get_handle(device)
+    fn = getattr(hd.lib, fn_name)
+    n = fn(hd.h, None, 0)
+    buf = (C.c_int * n)()
+    fn(hd.h, buf, n)
+    return {r: c for r, c in enumerate(buf) if c}
+
+
+def conv_route_counts(device: torch.device) -> dict:
+    """{route: launches} of every launch of csrc/conv.hip on the device's handle since conv_route_reset."""
+    return _conv_route_table(device, "imcui_hip_conv_route_counts")
+
+
+def conv_route_features(device: torch.device) -> dict:
+    """{route: OR of the CONV_FEATURES bits its launches ran with} since conv_route_reset (routes with no feature are absent)."""
+    return _conv_route_table(device, "imcui_hip_conv_route_features")
+
+
+def conv_route_reset(device: torch.device) -> None:
+    hd = get_handle(device)
+    hd.call(hd.lib.imcui_hip_conv_route_reset)
+
+
 def _split_planes(t: torch.Tensor) -> torch.Tensor:
     """f32 tensor -> [2, ...] f16 (hi, lo) planes, the operand format of the split attention kernel."""
     hi = t.half()

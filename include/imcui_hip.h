@@ -794,6 +794,49 @@ int imcui_hip_attn_last_route(const imcui_hip_t* h);
 int imcui_hip_attn_route_counts(const imcui_hip_t* h, int* out, int n);
 int imcui_hip_attn_route_reset(imcui_hip_t* h);
 
+/* ---- test entry into the 3x3 convolution launchers (tests/test_gpu_conv_variants.py) ------------------------------------------
+ * Every argument of the four launchers of csrc/conv.h (meanings there).  Device pointers; unset fields zero.
+ * entry 0: conv3x3_launch (exact f32; in, wp, bias, out, B, H, W, Cin, Cout, relu, pool)
+ * entry 1: conv3x3_split_launch (in, wh, wl, wscale, bias, out, B, H, W, Cin, Cout, relu, pool, resid, cin_stride, cout_live, single,
+ *          resid2; the point-map head {head_w, head_b, head_pts, head_conf, head_raw} is passed when `head` is not 0)
+ * entry 2: conv1ab_fused_split_launch (in = image [B,H,W], w1a [9][64], b1a, wh, wl, wscale, bias, out, B, H, W, pool)
+ * entry 3: conv1a_launch (in = image [B,H,W], w1a [9][64], b1a, out, B, H, W) */
+typedef struct imcui_hip_conv_desc {
+    int entry;
+    const float* in;
+    const float* wp;
+    const unsigned short* wh;
+    const unsigned short* wl;
+    const float* wscale;
+    const float* bias;
+    float* out;
+    int B, H, W, Cin, Cout;
+    int relu, pool;
+    const float* resid;
+    const float* resid2;
+    int cin_stride, cout_live, single;
+    int head;
+    const float* head_w;
+    const float* head_b;
+    float* head_pts;
+    float* head_conf;
+    float* head_raw;
+    const float* w1a;
+    const float* b1a;
+} imcui_hip_conv_desc;
+/* Calls the launcher named by `entry` with the fields unchanged.  Checks of its own: a null handle, descriptor or a null pointer the
+ * launcher would dereference without a check of its own (in, the weights and bias of the entry, `out` of entries 0, 2 and 3) is
+ * IMCUI_HIP_ERR_ARG; `out` and the head's pointers of entry 1 are left to the launcher's refusals.  Nothing is launched by a refused call. */
+int imcui_hip_conv_probe_f32(imcui_hip_t* h, const imcui_hip_conv_desc* d, void* stream);
+size_t imcui_hip_conv_desc_bytes(void);
+/* Route of the last convolution launch on this handle (csrc/conv.h ConvRouteKind; 0 = nothing launched: a refused call, an empty map),
+ * launches per route since imcui_hip_conv_route_reset, and per route the OR of the fused features its launches ran with (ConvFeature
+ * bits); both copy min(n, slots) values to out and return the slot count. */
+int imcui_hip_conv_last_route(const imcui_hip_t* h);
+int imcui_hip_conv_route_counts(const imcui_hip_t* h, int* out, int n);
+int imcui_hip_conv_route_features(const imcui_hip_t* h, int* out, int n);
+int imcui_hip_conv_route_reset(imcui_hip_t* h);
+
 #ifdef __cplusplus
 }
 #endif
