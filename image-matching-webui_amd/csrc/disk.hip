@@ -19,6 +19,7 @@
 
 #include "gemm.h"
 #include "imcui_hip.h"
+#include "select.h"
 
 // ------------------------------------------------------------------ packed weight layout
 // GEMM layers (5x5, pad 2): down 1..4, up 0..3 (the last one: descriptor rows 0..127 only)
@@ -344,91 +345,22 @@ __device__ __forceinline__ bool dk_keep(const float* __restrict__ hm, int y, int
     return true;
 }
 
-#define DK_SEL_CHUNK 4096  // pixels per block (16 consecutive per thread)
-__global__ __launch_bounds__(256) void dk_count_kernel(const float* __restrict__ heat, int h, int w, int r, float thr, int* __restrict__ blkcnt,
-                                                       int nchunk) {
-    __shared__ int wsum[4];
-    const int b = blockIdx.y, chunk = blockIdx.x;
-    const int npix = h * w;
-    const float* hm = heat + (long)b * npix;
-    const int base = chunk * DK_SEL_CHUNK + threadIdx.x * 16;
-    int c = 0;
-    for (int j = 0; j < 16; ++j) {
-        const int idx = base + j;
-        if (idx < npix && dk_keep(hm, idx / w, idx % w, h, w, r, thr)) ++c;
-    }
-    c = wave_sum_i(c);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) blkcnt[b * nchunk + chunk] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-}
-
-__global__ void dk_scan_kernel(const int* __restrict__ blkcnt, int* __restrict__ blkoff, int* __restrict__ ncand, int nchunk) {
-    if (threadIdx.x != 0) return;
-    const int b = blockIdx.x;
-    int run = 0;
-    for (int i = 0; i < nchunk; ++i) {
-        blkoff[b * nchunk + i] = run;
-        run += blkcnt[b * nchunk + i];
-    }
-    ncand[b] = run;
-}
-
-// candidates in row-major order: cscore [b][ccap] = heat value, cidx [b][ccap] = flat pixel index
-__global__ __launch_bounds__(256) void dk_compact_kernel(const float* __restrict__ heat, int h, int w, int r, float thr, const int* __restrict__ blkoff,
-                                                         int nchunk, float* __restrict__ cscore, int* __restrict__ cidx, int ccap) {
-    __shared__ int tcnt[256];
-    const int b = blockIdx.y, chunk = blockIdx.x;
-    const int npix = h * w;
-    const float* hm = heat + (long)b * npix;
-    const int base = chunk * DK_SEL_CHUNK + threadIdx.x * 16;
-    unsigned flags = 0;
-    int c = 0;
-    for (int j = 0; j < 16; ++j) {
-        const int idx = base + j;
-        if (idx < npix && dk_keep(hm, idx / w, idx % w, h, w, r, thr)) {
-            flags |= 1u << j;
-            ++c;
-        }
-    }
-    tcnt[threadIdx.x] = c;
-    __syncthreads();
-    for (int o = 1; o < 256; o <<= 1) {
-        const int add = (threadIdx.x >= o) ? tcnt[threadIdx.x - o] : 0;
-        __syncthreads();
-        tcnt[threadIdx.x] += add;
-        __syncthreads();
-    }
-    int pos = blkoff[b * nchunk + chunk] + tcnt[threadIdx.x] - c;
-    for (int j = 0; j < 16; ++j)
-        if (flags & (1u << j)) {
-            if (pos < ccap) {
-                cscore[(long)b * ccap + pos] = hm[base + j];
-                cidx[(long)b * ccap + pos] = base + j;
-            }
-            ++pos;
-        }
-}
+struct DkKeep {
+    int h, w, r;
+    float thr;
+    __device__ void bind(int) {}
+    __device__ bool operator()(const float* hm, int idx) const { return dk_keep(hm, idx / w, idx % w, h, w, r, thr); }
+};
 
 // ------------------------------------------------------------------ selection (heatmap_to_keypoints with n given)
 // n_ = min(n + 1, count); t = the n_-th largest score (radix select on order-preserving keys); keep score > t (strict), then the
 // first n in row-major order.  n < 0 (None): every candidate.  Zero candidates: zero key-points (the reference raises there).
 // One workgroup per image.  Outputs past the count are zero.
-__device__ __forceinline__ unsigned dk_key(float f) {
-    unsigned u = __float_as_uint(f);
-    if (u == 0x80000000u) u = 0u;  // -0 == +0
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
 __global__ __launch_bounds__(1024) void dk_select_kernel(const float* __restrict__ cscore, const int* __restrict__ cidx, int ccap,
                                                          const int* __restrict__ ncand, int maxk, int kcap, int w, float* __restrict__ kpts,
                                                          float* __restrict__ scores, int* __restrict__ nkpts, int* __restrict__ status) {
-    __shared__ int hist[256];
-    __shared__ unsigned s_prefix;
-    __shared__ int s_k;
     __shared__ int wcnt[16];
-    __shared__ int s_run;
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int b = blockIdx.x, tid = threadIdx.x;
     const float* cs = cscore + (long)b * ccap;
     const int* ci = cidx + (long)b * ccap;
     const int n = min(ncand[b], ccap);
@@ -438,45 +370,18 @@ __global__ __launch_bounds__(1024) void dk_select_kernel(const float* __restrict
     if (maxk >= 0 && n > 0) {
         filter = true;
         limit = min(maxk, n);
-        if (tid == 0) {
-            s_prefix = 0;
-            s_k = min(maxk + 1, n);
-        }
-        __syncthreads();
-        for (int byte = 3; byte >= 0; --byte) {
-            if (tid < 256) hist[tid] = 0;
-            __syncthreads();
-            const unsigned prefix = s_prefix;
-            const unsigned himask = (byte == 3) ? 0u : (~0u << (8 * (byte + 1)));
-            for (int i = tid; i < n; i += 1024) {
-                const unsigned key = dk_key(cs[i]);
-                if ((key & himask) == prefix) atomicAdd(&hist[(key >> (8 * byte)) & 0xFF], 1);
-            }
-            __syncthreads();
-            if (tid == 0) {  // walk the bins downwards until the running count reaches k
-                int k = s_k, d = 255;
-                for (; d > 0; --d) {
-                    if (hist[d] >= k) break;
-                    k -= hist[d];
-                }
-                s_prefix = prefix | ((unsigned)d << (8 * byte));
-                s_k = k;
-            }
-            __syncthreads();
-        }
-        kth = s_prefix;  // the n_-th largest key
+        // the n_-th largest key (n_ >= 1: maxk >= 0, n > 0)
+        kth = radix_select_kth<1024, unsigned>([&](int i) { return order_key(cs[i]); }, n, min(maxk + 1, n));
     }
     if (limit > kcap) {
         if (tid == 0) atomicOr(status, 2);  // output capacity too small
         limit = kcap;
     }
     // ordered compaction of the kept candidates, 1024 at a time
-    if (tid == 0) s_run = 0;
-    __syncthreads();
     float* kp = kpts + (long)b * kcap * 2;
     float* sc = scores + (long)b * kcap;
+    int run = 0;
     for (int base = 0; base < n; base += 1024) {
-        const int run = s_run;
         if (run >= limit) break;
         const int i = base + tid;
         bool keep = false;
@@ -485,28 +390,18 @@ __global__ __launch_bounds__(1024) void dk_select_kernel(const float* __restrict
         if (i < n) {
             v = cs[i];
             idx = ci[i];
-            keep = !filter || dk_key(v) > kth;
+            keep = !filter || order_key(v) > kth;
         }
-        const unsigned long long bal = __ballot(keep);
-        const int before = __popcll(bal & ((1ull << lane) - 1ull));
-        if (lane == 0) wcnt[wid] = __popcll(bal);
-        __syncthreads();
-        int off = 0, tot = 0;
-        for (int q = 0; q < 16; ++q) {
-            if (q < wid) off += wcnt[q];
-            tot += wcnt[q];
-        }
-        const int pos = run + off + before;
+        int tot;
+        const int pos = run + block_ordered_rank<16>(keep, wcnt, &tot);
         if (keep && pos < limit) {
             kp[2 * pos + 0] = (float)(idx % w);
             kp[2 * pos + 1] = (float)(idx / w);
             sc[pos] = v;
         }
-        __syncthreads();
-        if (tid == 0) s_run = run + tot;
-        __syncthreads();
+        run += tot;
     }
-    const int cnt = min(s_run, limit);
+    const int cnt = min(run, limit);
     for (int i = cnt + tid; i < kcap; i += 1024) {
         kp[2 * i + 0] = 0.0f;
         kp[2 * i + 1] = 0.0f;
@@ -584,7 +479,7 @@ static DkWs dk_carve(void* ws, size_t bytes, int B, int h, int w, int Hp, int Wp
     s.rstd = a.get<float>((size_t)B * 128);
     s.part = a.get<double>((size_t)B * cdiv((int)P0, DK_STAT_CHUNK) * 128 * 2);
     s.heat = a.get<float>((size_t)B * h * w);
-    const int nchunk = cdiv(h * w, DK_SEL_CHUNK);
+    const int nchunk = cdiv(h * w, SEL_CHUNK);
     s.blkcnt = a.get<int>((size_t)B * nchunk);
     s.blkoff = a.get<int>((size_t)B * nchunk);
     s.ncand = a.get<int>(B);
@@ -720,10 +615,12 @@ extern "C" int imcui_hip_disk_forward(imcui_hip_t* h, const float* packed, const
     IMCUI_CHECK_LAUNCH(h);
     int* st = status ? status : s.status;
     hipMemsetAsync(st, 0, sizeof(int), stream);
-    const int nchunk = cdiv(H * W, DK_SEL_CHUNK), r = window / 2, ccap = H * W;
-    hipLaunchKernelGGL(dk_count_kernel, dim3(nchunk, B), dim3(256), 0, stream, heat, H, W, r, threshold, s.blkcnt, nchunk);
-    hipLaunchKernelGGL(dk_scan_kernel, dim3(B), dim3(64), 0, stream, s.blkcnt, s.blkoff, s.ncand, nchunk);
-    hipLaunchKernelGGL(dk_compact_kernel, dim3(nchunk, B), dim3(256), 0, stream, heat, H, W, r, threshold, s.blkoff, nchunk, s.cscore, s.cidx, ccap);
+    const int nchunk = cdiv(H * W, SEL_CHUNK), r = window / 2, ccap = H * W;
+    const DkKeep keep{H, W, r, threshold};
+    hipLaunchKernelGGL(cand_count_kernel<DkKeep>, dim3(nchunk, B), dim3(256), 0, stream, heat, H * W, keep, s.blkcnt, nchunk);
+    hipLaunchKernelGGL(exclusive_scan_kernel<int>, dim3(B), dim3(1024), 0, stream, s.blkcnt, s.blkoff, s.ncand, (const int*)nullptr, nchunk, (long)nchunk);
+    hipLaunchKernelGGL((cand_compact_kernel<DkKeep, EmitScoreIndex>), dim3(nchunk, B), dim3(256), 0, stream, heat, H * W, keep, s.blkoff, nchunk, ccap,
+                       EmitScoreIndex{s.cscore, s.cidx, ccap});
     hipLaunchKernelGGL(dk_select_kernel, dim3(B), dim3(1024), 0, stream, s.cscore, s.cidx, ccap, s.ncand, max_keypoints, kcap, W, keypoints, scores,
                        num_keypoints, st);
     IMCUI_CHECK_LAUNCH(h);

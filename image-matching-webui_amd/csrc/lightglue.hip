@@ -19,6 +19,7 @@
 #include "gemm.h"
 #include "imcui_hip.h"
 #include "lightglue_assign.h"
+#include "select.h"
 #include "simred.h"
 
 #define LG_LAYERS 9
@@ -540,16 +541,10 @@ __global__ __launch_bounds__(256) void lg_decide_kernel(const float* __restrict_
                 keep = mtch[base + i] > keep_thr;
                 if (do_stop) keep = keep || (conf[base + i] <= tau);
             }
-            const unsigned long long bal = __ballot(keep);
-            const int wrank = __popcll(bal & ((1ull << lane) - 1ull));
-            if (lane == 0) red[wv] = __popcll(bal);
-            __syncthreads();
-            int woff = 0;
-            for (int w = 0; w < wv; ++w) woff += red[w];
-            const int tot = red[0] + red[1] + red[2] + red[3];
-            if (i < c) pos[base + i] = keep ? (run + woff + wrank) : -1;
+            int tot;
+            const int rank = block_ordered_rank<4>(keep, red, &tot);
+            if (i < c) pos[base + i] = keep ? (run + rank) : -1;
             run += tot;
-            __syncthreads();
         }
         newc[s] = run;
     }

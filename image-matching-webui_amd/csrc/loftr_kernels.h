@@ -3,6 +3,7 @@
 // dual-softmax coarse matching, fine window gather and fine matching.  Included by loftr.hip (all of it) and eloftr.hip (LayerNorm, dual-softmax matching).
 #pragma once
 #include "common.h"
+#include "select.h"
 
 namespace {  // internal linkage: loftr.hip and eloftr.hip both include these kernels
 
@@ -309,34 +310,22 @@ __global__ __launch_bounds__(1024) void lf_compact_kernel(const int* __restrict_
                                                           int* __restrict__ mb, int* __restrict__ mi, int* __restrict__ mj,
                                                           float* __restrict__ mconf, int* __restrict__ nmatch) {
     __shared__ int wsum[16];
-    __shared__ int s_run;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    if (tid == 0) s_run = 0;
-    __syncthreads();
+    const int tid = threadIdx.x;
+    int run = 0;
     for (long base = 0; base < n; base += 1024) {
         const long t = base + tid;
         const bool f = (t < n) && flag[t] != 0;
-        const unsigned long long bal = __ballot(f);
-        const int wrank = __popcll(bal & ((1ull << lane) - 1ull));
-        if (lane == 0) wsum[wv] = __popcll(bal);
-        __syncthreads();
-        int woff = 0, tot = 0;
-        for (int w = 0; w < 16; ++w) {
-            if (w < wv) woff += wsum[w];
-            tot += wsum[w];
-        }
-        const int pos = s_run + woff + wrank;
+        int tot;
+        const int pos = run + block_ordered_rank<16>(f, wsum, &tot);
         if (f && pos < cap) {
             mb[pos] = (int)(t / L);
             mi[pos] = (int)(t % L);
             mj[pos] = bestj[t];
             mconf[pos] = best[t];
         }
-        __syncthreads();
-        if (tid == 0) s_run += tot;
-        __syncthreads();
+        run += tot;
     }
-    if (tid == 0) *nmatch = min(s_run, cap);
+    if (tid == 0) *nmatch = min(run, cap);
 }
 
 // ------------------------------------------------------------------ fine level

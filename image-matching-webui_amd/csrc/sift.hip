@@ -8,7 +8,7 @@
 //                       repeatedly; the whole batch in one grid; every level is blurred from the previous level
 //   sf_down_kernel      next octave = every second pixel of level `layers`
 //   sf_extrema_kernel   26-neighbour extrema of the DoG (formed on the fly: L[i+1] - L[i] in fp32 is the stored DoG bit for bit); one
-//                       ballot word per wave + one count per workgroup, then sf_scan_kernel + sf_compact_kernel: the candidate list
+//                       ballot word per wave + one count per workgroup, then exclusive_scan_kernel (select.h) + sf_compact_kernel: the candidate list
 //                       is in (octave, layer, row, column) order by construction (count + scan, no sort, no float atomics)
 //   sf_refine_kernel    adjustLocalExtrema: up to 5 Newton steps, contrast and edge tests; one thread per candidate
 //   sf_orient_kernel    36-bin orientation histogram, one wave per candidate (capped grid, workgroups walk the list), a private histogram per lane in LDS summed in lane order
@@ -27,6 +27,7 @@
 
 #include "common.h"
 #include "imcui_hip.h"
+#include "select.h"
 
 #define SF_MAX_OCT 16
 #define SF_BORDER 5
@@ -251,34 +252,6 @@ __global__ __launch_bounds__(1024) void sf_extrema_kernel(const float* __restric
     }
 }
 
-// exclusive scan of in[b][0..n) (n = min(*n_dev[b], n_cap) when n_dev, else n_cap) -> out[b][.], total[b]; one workgroup per row
-__global__ __launch_bounds__(1024) void sf_scan_kernel(const int* in, int* out, int* total, const int* n_dev,
-                                                        int n_cap, long stride) {
-    __shared__ int s[1024];
-    const int b = blockIdx.x;
-    int n = n_cap;
-    if (n_dev) n = min(n_dev[b], n_cap);
-    const int* ib = in + (long)b * stride;
-    int* ob = out + (long)b * stride;
-    int carry = 0;
-    for (int base = 0; base < n; base += 1024) {
-        const int i = base + threadIdx.x;
-        const int v = i < n ? ib[i] : 0;
-        s[threadIdx.x] = v;
-        __syncthreads();
-        for (int d = 1; d < 1024; d <<= 1) {
-            const int t = threadIdx.x >= d ? s[threadIdx.x - d] : 0;
-            __syncthreads();
-            s[threadIdx.x] += t;
-            __syncthreads();
-        }
-        if (i < n) ob[i] = carry + s[threadIdx.x] - v;
-        carry += s[1023];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) total[b] = carry;
-}
-
 __global__ __launch_bounds__(1024) void sf_compact_kernel(const unsigned long long* __restrict__ bits, const int* __restrict__ wgoff, int nwg, unsigned total_px,
                                                            int ccap, int* __restrict__ cand) {
     const int b = blockIdx.y;
@@ -473,9 +446,10 @@ __global__ __launch_bounds__(64) void sf_orient_kernel(const float* __restrict__
             if (fabsf(ang - 360.f) < SF_EPS) ang = 0.f;
         }
     }
-    const unsigned long long m = __ballot(pk);
-    if (pk) peaks[((long)b * ccap + j) * SF_MAXP + __popcll(m & ((1ull << lane) - 1ull))] = ang;
-    if (lane == 0) npeaks[(long)b * ccap + j] = __popcll(m);
+    int npk;
+    const int slot = wave_ordered_rank(pk, &npk);
+    if (pk) peaks[((long)b * ccap + j) * SF_MAXP + slot] = ang;
+    if (lane == 0) npeaks[(long)b * ccap + j] = npk;
     __syncthreads();  // the LDS histograms are re-used by the next candidate
     }
 }
@@ -804,12 +778,12 @@ extern "C" int imcui_hip_sift_forward(imcui_hip_t* h, const float* image, int B,
     const unsigned total_px = g.px_off[g.nOct];
     const float thr = (float)(int)floor(0.5 * (double)contrast_threshold / layers * 255.0);
     hipLaunchKernelGGL(sf_extrema_kernel, dim3(s.nwg, B), dim3(1024), 0, stream, pyr, g, thr, s.bits, s.wgcnt, s.nwg);
-    hipLaunchKernelGGL(sf_scan_kernel, dim3(B), dim3(1024), 0, stream, s.wgcnt, s.wgcnt, s.ncand, (const int*)nullptr, s.nwg, (long)s.nwg);
+    hipLaunchKernelGGL(exclusive_scan_kernel<int>, dim3(B), dim3(1024), 0, stream, s.wgcnt, s.wgcnt, s.ncand, (const int*)nullptr, s.nwg, (long)s.nwg);
     hipLaunchKernelGGL(sf_compact_kernel, dim3(s.nwg, B), dim3(1024), 0, stream, s.bits, s.wgcnt, s.nwg, total_px, ccap, cand);
     // ---- refinement, orientations, table
     hipLaunchKernelGGL(sf_refine_kernel, dim3(cdiv(ccap, 256), B), dim3(256), 0, stream, pyr, g, cand, s.ncand, ccap, contrast_threshold, edge_threshold, rec, status);
     hipLaunchKernelGGL(sf_orient_kernel, dim3(min(ccap, SF_MAXWG), B), dim3(64), 0, stream, pyr, g, rec, s.ncand, ccap, s.npeaks, s.peaks, dbg_hist);
-    hipLaunchKernelGGL(sf_scan_kernel, dim3(B), dim3(1024), 0, stream, s.npeaks, s.tabofs, s.ntab, s.ncand, ccap, (long)ccap);
+    hipLaunchKernelGGL(exclusive_scan_kernel<int>, dim3(B), dim3(1024), 0, stream, s.npeaks, s.tabofs, s.ntab, s.ncand, ccap, (long)ccap);
     hipLaunchKernelGGL(sf_expand_kernel, dim3(cdiv(ccap, 256), B), dim3(256), 0, stream, rec, s.ncand, s.npeaks, s.tabofs, s.ntab, s.peaks, ccap, table, status);
     IMCUI_CHECK_LAUNCH(h);
     // ---- OpenCV's post-processing and the wrapper stages
@@ -830,7 +804,7 @@ extern "C" int imcui_hip_sift_forward(imcui_hip_t* h, const float* image, int B,
         if (nms_radius > 0) pass(sf_sel_kernel<4>, nms_radius);
     }
     if (max_keypoints > 0) pass(sf_sel_kernel<5>, max_keypoints);
-    hipLaunchKernelGGL(sf_scan_kernel, dim3(B), dim3(1024), 0, stream, cur, s.fofs, s.nfinal, s.ntab, ccap, (long)ccap);
+    hipLaunchKernelGGL(exclusive_scan_kernel<int>, dim3(B), dim3(1024), 0, stream, cur, s.fofs, s.nfinal, s.ntab, ccap, (long)ccap);
     hipLaunchKernelGGL(sf_final_kernel, sg, sb, 0, stream, table, s.ntab, cur, s.fofs, s.nfinal, ccap, kcap, keypoints, scores, scales, oris, s.rows, num_keypoints, counts,
                        s.ncand, status);
     hipLaunchKernelGGL(sf_desc_kernel, dim3(min(kcap, SF_MAXWG), B), dim3(64), 0, stream, pyr, g, table, s.rows, num_keypoints, ccap, kcap, rootsift, descriptors, dbg_desc_raw);

@@ -8,6 +8,7 @@
 #include "conv.h"
 #include "gemm.h"
 #include "imcui_hip.h"
+#include "select.h"
 
 // ------------------------------------------------------------------ packed weight layout
 struct SpLayout {
@@ -242,85 +243,27 @@ static int nms_launch(imcui_hip_s* h, const float* in, float* out, int B, int H,
     return IMCUI_OK;
 }
 
-// ------------------------------------------------------------------ ordered candidate compaction
+// ------------------------------------------------------------------ ordered candidate compaction (select.h)
 // candidate: nms score > thr and inside the border band.  Row-major order is preserved (the
 // reference returns `nonzero` order when no top-k is needed).
-#define SEL_CHUNK 4096  // pixels per block (16 consecutive per thread)
-
-__device__ __forceinline__ bool sp_is_cand(float s, int idx, int H, int W, float thr, int border) {
-    const int y = idx / W, x = idx - y * W;
-    return s > thr && y >= border && y < H - border && x >= border && x < W - border;
-}
-
-__global__ __launch_bounds__(256) void sp_count_kernel(const float* __restrict__ nms, int H, int W, float thr,
-                                                       int border, int* __restrict__ blkcnt, int nchunk) {
-    __shared__ int wsum[4];
-    const int b = blockIdx.y, chunk = blockIdx.x;
-    const int npix = H * W;
-    const float* img = nms + (size_t)b * npix;
-    const int base = chunk * SEL_CHUNK + threadIdx.x * 16;
-    int c = 0;
-    for (int j = 0; j < 16; ++j) {
-        const int idx = base + j;
-        if (idx < npix && sp_is_cand(img[idx], idx, H, W, thr, border)) ++c;
+struct SpIsCand {
+    int H, W;
+    float thr;
+    int border;
+    __device__ void bind(int) {}
+    __device__ bool operator()(const float* img, int idx) const {
+        const int y = idx / W, x = idx - y * W;
+        return img[idx] > thr && y >= border && y < H - border && x >= border && x < W - border;
     }
-    c = wave_sum_i(c);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) blkcnt[b * nchunk + chunk] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-}
-
-// exclusive scan of the per-chunk counts (one block per image, serial over <= a few hundred chunks)
-__global__ void sp_scan_kernel(const int* __restrict__ blkcnt, int* __restrict__ blkoff, int* __restrict__ ncand,
-                               int nchunk) {
-    if (threadIdx.x != 0) return;
-    const int b = blockIdx.x;
-    int run = 0;
-    for (int i = 0; i < nchunk; ++i) {
-        blkoff[b * nchunk + i] = run;
-        run += blkcnt[b * nchunk + i];
+};
+// 64-bit key (score bits << 32 | ~index) of candidate `pos`
+struct SpEmitKey {
+    unsigned long long* cand;  // [b][cand_cap]
+    int cand_cap;
+    __device__ void operator()(int b, int pos, int idx, float v) const {
+        cand[(size_t)b * cand_cap + pos] = ((unsigned long long)__float_as_uint(v) << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)idx);
     }
-    ncand[b] = run;
-}
-
-__global__ __launch_bounds__(256) void sp_compact_kernel(const float* __restrict__ nms, int H, int W, float thr,
-                                                         int border, const int* __restrict__ blkoff, int nchunk,
-                                                         unsigned long long* __restrict__ cand, int cand_cap) {
-    __shared__ int tcnt[256];
-    const int b = blockIdx.y, chunk = blockIdx.x;
-    const int npix = H * W;
-    const float* img = nms + (size_t)b * npix;
-    const int base = chunk * SEL_CHUNK + threadIdx.x * 16;
-    float v[16];
-    unsigned flags = 0;
-    int c = 0;
-    for (int j = 0; j < 16; ++j) {
-        const int idx = base + j;
-        v[j] = (idx < npix) ? img[idx] : 0.0f;
-        if (idx < npix && sp_is_cand(v[j], idx, H, W, thr, border)) {
-            flags |= 1u << j;
-            ++c;
-        }
-    }
-    tcnt[threadIdx.x] = c;
-    __syncthreads();
-    // exclusive prefix over the 256 per-thread counts (Hillis-Steele)
-    for (int o = 1; o < 256; o <<= 1) {
-        int add = (threadIdx.x >= o) ? tcnt[threadIdx.x - o] : 0;
-        __syncthreads();
-        tcnt[threadIdx.x] += add;
-        __syncthreads();
-    }
-    int pos = blkoff[b * nchunk + chunk] + tcnt[threadIdx.x] - c;
-    unsigned long long* dst = cand + (size_t)b * cand_cap;
-    for (int j = 0; j < 16; ++j)
-        if (flags & (1u << j)) {
-            const unsigned idx = (unsigned)(base + j);
-            if (pos < cand_cap)
-                dst[pos] = ((unsigned long long)__float_as_uint(v[j]) << 32) | (unsigned long long)(0xFFFFFFFFu - idx);
-            ++pos;
-        }
-}
+};
 
 // ------------------------------------------------------------------ top-k (score desc, index asc)
 // One block per image.  64-bit keys (score bits << 32 | ~index) are unique, so "the k largest
@@ -334,9 +277,7 @@ __global__ __launch_bounds__(1024) void sp_topk_kernel(const unsigned long long*
                                                        float* __restrict__ kpts, float* __restrict__ scores,
                                                        int* __restrict__ nkpts, int* __restrict__ status) {
     extern __shared__ __attribute__((aligned(16))) unsigned long long sel[];  // [roundup_pow2(min(max_kpts, TOPK_MAX))]
-    __shared__ int hist[256];
-    __shared__ unsigned long long s_prefix;
-    __shared__ int s_k, s_nsel;
+    __shared__ int s_nsel;
     const int b = blockIdx.x, tid = threadIdx.x;
     const unsigned long long* c = cand + (size_t)b * cand_cap;
     int n = ncand[b];
@@ -370,54 +311,9 @@ __global__ __launch_bounds__(1024) void sp_topk_kernel(const unsigned long long*
         }
         return;
     }
-    // ---- radix select: find the k-th largest key
-    if (tid == 0) {
-        s_prefix = 0;
-        s_k = k;
-    }
-    __syncthreads();
-    for (int byte = 7; byte >= 0; --byte) {
-        if (tid < 256) hist[tid] = 0;
-        __syncthreads();
-        const unsigned long long prefix = s_prefix;
-        const unsigned long long himask = (byte == 7) ? 0ull : (~0ull << (8 * (byte + 1)));
-        for (int i = tid; i < n; i += 1024) {
-            const unsigned long long key = c[i];
-            if ((key & himask) == prefix) atomicAdd(&hist[(int)((key >> (8 * byte)) & 0xFF)], 1);
-        }
-        __syncthreads();
-        // the digit of the k-th key: walk the bins downwards until the running count reaches k.  One wave does it in parallel (lane l owns
-        // bins 255 - 4 l .. 252 - 4 l, inclusive scan over the lanes, the first lane that reaches k finishes inside its four bins); one
-        // thread walking 255 dependent LDS reads, eight times, was most of this kernel's 84 us
-        if (tid < 64) {
-            const int d0 = 255 - 4 * tid;
-            const int h0 = hist[d0], h1 = hist[d0 - 1], h2 = hist[d0 - 2], h3 = hist[d0 - 3];
-            const int mine = h0 + h1 + h2 + h3;
-            int inc = mine;
-            for (int o = 1; o < 64; o <<= 1) {
-                const int up = __shfl_up(inc, o, 64);
-                if (tid >= o) inc += up;
-            }
-            const int kk = s_k;
-            const unsigned long long reach = __ballot(inc >= kk);
-            const int L = reach ? __ffsll((long long)reach) - 1 : 63;  // (never empty: at least k keys carry the prefix; 63 = bin 0 all the same)
-            if (tid == L) {
-                int k2 = kk - (inc - mine), d;
-                if (h0 >= k2)
-                    d = d0;
-                else if (h0 + h1 >= k2)
-                    d = d0 - 1, k2 -= h0;
-                else if (h0 + h1 + h2 >= k2)
-                    d = d0 - 2, k2 -= h0 + h1;
-                else
-                    d = d0 - 3, k2 -= h0 + h1 + h2;  // (lane 63: bin 0 takes what is left, as the sequential walk did)
-                s_prefix = prefix | ((unsigned long long)d << (8 * byte));
-                s_k = k2;
-            }
-        }
-        __syncthreads();
-    }
-    const unsigned long long kth = s_prefix;  // exactly k keys are >= kth
+    // ---- radix select: find the k-th largest key.  (k = 0, max_keypoints = 0 or kcap = 0, gets here too: every round then takes bin 255,
+    // kth is all ones, above every key, and nothing is kept -- what one thread walking the bins gave as well)
+    const unsigned long long kth = radix_select_kth<1024, unsigned long long>([&](int i) { return c[i]; }, n, k);  // exactly k keys are >= kth
     if (tid == 0) s_nsel = 0;
     __syncthreads();
     for (int i = tid; i < n; i += 1024) {
@@ -683,11 +579,11 @@ extern "C" int imcui_hip_superpoint_forward(imcui_hip_t* h, const float* packed,
     const int nchunk = cdiv(H * W, SEL_CHUNK);
     int* st = status ? status : s.status;
     hipMemsetAsync(st, 0, sizeof(int), stream);
-    hipLaunchKernelGGL(sp_count_kernel, dim3(nchunk, B), dim3(256), 0, stream, s.nms, H, W, keypoint_threshold,
-                       remove_borders, s.blkcnt, nchunk);
-    hipLaunchKernelGGL(sp_scan_kernel, dim3(B), dim3(64), 0, stream, s.blkcnt, s.blkoff, s.ncand, nchunk);
-    hipLaunchKernelGGL(sp_compact_kernel, dim3(nchunk, B), dim3(256), 0, stream, s.nms, H, W, keypoint_threshold,
-                       remove_borders, s.blkoff, nchunk, s.cand, cand_cap);
+    const SpIsCand is_cand{H, W, keypoint_threshold, remove_borders};
+    hipLaunchKernelGGL(cand_count_kernel<SpIsCand>, dim3(nchunk, B), dim3(256), 0, stream, s.nms, H * W, is_cand, s.blkcnt, nchunk);
+    hipLaunchKernelGGL(exclusive_scan_kernel<int>, dim3(B), dim3(1024), 0, stream, s.blkcnt, s.blkoff, s.ncand, (const int*)nullptr, nchunk, (long)nchunk);
+    hipLaunchKernelGGL((cand_compact_kernel<SpIsCand, SpEmitKey>), dim3(nchunk, B), dim3(256), 0, stream, s.nms, H * W, is_cand, s.blkoff, nchunk, cand_cap,
+                       SpEmitKey{s.cand, cand_cap});
     {
         int np2 = 1;
         const int kmax = max_keypoints < 0 ? 1 : (max_keypoints < TOPK_MAX ? max_keypoints : TOPK_MAX);

@@ -205,6 +205,47 @@ def test_mean_fallback_on_the_device(precision):
         assert (got - kp).abs().max().item() <= 2e-3
 
 
+@functools.lru_cache(maxsize=None)
+def _flat_plugin():
+    from imcui_hip.hloc.extractors.aliked import ALIKED
+
+    sd = {k: v.clone() for k, v in _sd().items()}
+    sd["score_head.6.weight"].zero_()  # the last layer of the score head (no bias): logit 0, score 0.5 at every pixel
+    return ALIKED({"state_dict": sd}).eval().to("cuda:0")
+
+
+@pytest.mark.parametrize("maxk", [300, 1500, -1])
+def test_device_ties_at_the_cut_on_a_flat_score_map(precision, maxk):
+    """The device's tie rule at the cut, driven on purpose: the score map is 0.5 everywhere, so every pixel is an NMS maximum and the
+    (72 - 4) x (88 - 4) = 5712 pixels of the radius band all tie.  With more candidates than `max_num_keypoints` every one of them EQUALS
+    the limit-th largest score: the first `limit` in row-major order stay (at 1500 the count of equal candidates is carried across a
+    1024-candidate batch of the select kernel); -1 keeps all 5712.  72 x 88 = 6336 pixels are two compaction chunks, the second one
+    partial.  Each case equals the restated rule on the same map."""
+    H, W, r = 72, 88, 2
+    m = _flat_plugin()
+    m.conf.update(dict(max_num_keypoints=maxk, detection_threshold=0.2, nms_radius=r))
+    out = m.forward_batched(image(H, W, 5).cuda(), want_maps=True, kcap=H * W)
+    sm = out["score_map"][0].cpu()
+    assert torch.equal(sm, torch.full((H, W), 0.5))
+    ys, xs = torch.meshgrid(torch.arange(r, H - r), torch.arange(r, W - r), indexing="ij")
+    band = (ys * W + xs).reshape(-1)
+    want = band[:maxk] if maxk > 0 else band
+    idx, branch = dkd_select(sm, r, 0.2, maxk)
+    assert branch == "threshold" and torch.equal(idx, want)
+    n = int(out["num_keypoints"][0])
+    assert n == want.numel() and int(out["status"]) == 0
+    kn, ks = dkd_refine(sm, idx, r)
+    kp = kn.new_tensor([W - 1, H - 1]) * (kn + 1) / 2
+    got = out["keypoints"][0].cpu()
+    err = (got[:n] - kp).abs().max().item()
+    print(f"flat map, max_num_keypoints {maxk}: {n} key-points, position error {err:.2e} px")
+    assert err <= 2e-3  # a differing candidate would sit at least a pixel away from the rule's
+    assert (out["keypoints_norm"][0, :n].cpu() - kn).abs().max().item() <= 2 * 2e-3 / (max(H, W) - 1)
+    assert (out["scores"][0, :n].cpu() - ks).abs().max().item() <= 1e-6  # (a bilinear sample of a constant map)
+    for k in ("keypoints", "keypoints_norm", "scores", "descriptors"):
+        assert not out[k][0, n:].any(), k  # entries past the count are zero
+
+
 # ------------------------------------------------------------------ determinism
 def test_batch_independence_and_graph_replay_are_bitwise(precision):
     m = _plugin()
