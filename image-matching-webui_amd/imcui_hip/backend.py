@@ -295,6 +295,132 @@ class DiskHIP:
         return out
 
 
+# ------------------------------------------------------------------ XFeat
+XFEAT_DETECTION_THRESHOLD = 0.05  # upstream XFeat.__init__'s default: imcui/hloc/extractors/xfeat.py never passes its `keypoint_threshold`
+
+
+def xfeat_tensor_names() -> list[str]:
+    lib = load_library()
+    return [lib.imcui_hip_xfeat_tensor_name(i).decode() for i in range(lib.imcui_hip_xfeat_num_tensors())]
+
+
+def xfeat_tensor_shapes() -> dict:
+    """XFeatModel's state-dict shapes (verlab/accelerated_features), without the `num_batches_tracked` counters and `fine_matcher.*`."""
+    blocks = [
+        ("block1", [(1, 4, 3), (4, 8, 3), (8, 8, 3), (8, 24, 3)], None),
+        ("block2", [(24, 24, 3), (24, 24, 3)], None),
+        ("block3", [(24, 64, 3), (64, 64, 3), (64, 64, 1)], None),
+        ("block4", [(64, 64, 3), (64, 64, 3), (64, 64, 3)], None),
+        ("block5", [(64, 128, 3), (128, 128, 3), (128, 128, 3), (128, 64, 1)], None),
+        ("block_fusion", [(64, 64, 3), (64, 64, 3)], (64, 64)),
+        ("heatmap_head", [(64, 64, 1), (64, 64, 1)], (64, 1)),
+        ("keypoint_head", [(64, 64, 1), (64, 64, 1), (64, 64, 1)], (64, 65)),
+    ]
+    shapes = {"skip1.1.weight": (24, 1, 1, 1), "skip1.1.bias": (24,)}
+    for name, layers, last in blocks:
+        for i, (cin, cout, k) in enumerate(layers):
+            shapes[f"{name}.{i}.layer.0.weight"] = (cout, cin, k, k)
+            shapes[f"{name}.{i}.layer.1.running_mean"] = (cout,)
+            shapes[f"{name}.{i}.layer.1.running_var"] = (cout,)
+        if last is not None:
+            shapes[f"{name}.{len(layers)}.weight"] = (last[1], last[0], 1, 1)
+            shapes[f"{name}.{len(layers)}.bias"] = (last[1],)
+    return shapes
+
+
+def pack_xfeat(state_dict: dict) -> torch.Tensor:
+    """XFeatModel state dict (a real `xfeat.pt`) -> packed float32 buffer (host); BatchNorm (eval, no affine part) is folded into the
+    convolutions by the packer.  `fine_matcher.*` (the semi-dense refinement MLP) and the `num_batches_tracked` counters are accepted
+    and ignored; every other key is consumed exactly once and every shape checked."""
+    lib = load_library()
+    names = xfeat_tensor_names()
+    shapes = xfeat_tensor_shapes()
+    own = {k: v for k, v in state_dict.items() if not k.startswith("fine_matcher.") and not k.endswith("num_batches_tracked")}
+    missing = [n for n in names if n not in own]
+    extra = sorted(set(own) - set(names))
+    if missing or extra:
+        raise ImcuiHipError(f"XFeat state dict does not match upstream's layout: missing {missing[:4]}, unexpected {extra[:4]}")
+    arrs = []
+    for n in names:
+        a = _as_f32_host(own[n])
+        if a.shape != shapes[n]:
+            raise ImcuiHipError(f"XFeat state dict: '{n}' has shape {a.shape}, expected {shapes[n]}")
+        arrs.append(a)
+    packed = np.zeros(lib.imcui_hip_xfeat_packed_floats(), dtype=np.float32)
+    tp = (C.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
+    rc = lib.imcui_hip_xfeat_pack_weights(tp, packed.ctypes.data)
+    if rc != 0:
+        raise ImcuiHipError(f"imcui_hip_xfeat_pack_weights failed ({rc})")
+    return torch.from_numpy(packed)
+
+
+def xfeat_check_args(image_shape) -> None:
+    """Refusals raised before anything is launched: upstream resizes to H // 32 * 32 x W // 32 * 32, which has to be non-empty."""
+    if len(image_shape) != 4 or image_shape[1] not in (1, 3):
+        raise ValueError(f"XFeat expects an image [B,1,H,W] or [B,3,H,W], got shape {tuple(image_shape)}")
+    if image_shape[2] < 32 or image_shape[3] < 32:
+        raise ValueError(f"XFeat needs images of at least 32 x 32, got {tuple(image_shape[2:])}")
+
+
+class XFeatHIP:
+    def __init__(self):
+        self._ws = _Workspace()
+
+    def forward(self, packed: torch.Tensor, image: torch.Tensor, conf: dict, want_dense: bool = False, kcap: int | None = None,
+                threshold: float = XFEAT_DETECTION_THRESHOLD):
+        """image [B,1|3,H,W] float32 on the GPU -> fixed-stride outputs in descending score order, no host synchronisation: keypoints
+        [B,K,2], scores [B,K], descriptors [B,K,64], num_keypoints [B] int32, status [1] int32 (bit 1: `kcap` too small); with
+        `want_dense` also kpt_heat [B,Hr,Wr], reliability [B,Hr/8,Wr/8], feats_norm [B,Hr/8,Wr/8,64].  `max_keypoints` is Python's
+        `[:top_k]` per image (-1 drops the lowest score); K = the NMS bound, cut to max_keypoints when that is not negative."""
+        xfeat_check_args(tuple(image.shape))
+        hd = get_handle(image.device)
+        if packed.device != image.device:
+            raise ImcuiHipError("packed weights and image live on different devices")
+        lib = hd.lib
+        image = image.contiguous().float()
+        B, Cc, H, W = image.shape
+        top_k = int(conf["max_keypoints"])
+        bound = lib.imcui_hip_xfeat_max_keypoints_bound(H, W)
+        if kcap is None:
+            kcap = bound if top_k < 0 else max(1, min(top_k, bound))
+        dev = image.device
+        Hr, Wr = H // 32 * 32, W // 32 * 32
+        kpts = torch.empty((B, kcap, 2), dtype=torch.float32, device=dev)
+        scores = torch.empty((B, kcap), dtype=torch.float32, device=dev)
+        desc = torch.empty((B, kcap, 64), dtype=torch.float32, device=dev)
+        nk = torch.empty((B,), dtype=torch.int32, device=dev)
+        status = torch.empty((1,), dtype=torch.int32, device=dev)
+        heat = torch.empty((B, Hr, Wr), dtype=torch.float32, device=dev) if want_dense else None
+        rel = torch.empty((B, Hr // 8, Wr // 8), dtype=torch.float32, device=dev) if want_dense else None
+        m1 = torch.empty((B, Hr // 8, Wr // 8, 64), dtype=torch.float32, device=dev) if want_dense else None
+        with self._ws.use(lib.imcui_hip_xfeat_workspace_bytes(B, H, W), dev) as ws:
+            hd.launch(
+                lib.imcui_hip_xfeat_forward, _ptr(packed), _ptr(image), B, Cc, H, W, float(threshold), top_k, kcap,
+                _ptr(kpts), _ptr(scores), _ptr(desc), _ptr(nk), _ptr(status), _ptr(heat), _ptr(rel), _ptr(m1), _ptr(ws), ws.numel(),
+            )  # fmt: skip
+        out = {"keypoints": kpts, "scores": scores, "descriptors": desc, "num_keypoints": nk, "status": status}
+        if want_dense:
+            out.update(kpt_heat=heat, reliability=rel, feats_norm=m1)
+        return out
+
+    def sample_probe(self, kpt_heat: torch.Tensor, reliability: torch.Tensor, feats: torch.Tensor, xy: torch.Tensor):
+        """The kernel's sampling rules at integer pixels xy [n,2] (x, y) of kpt_heat [H,W]: nearest(kpt_heat) [n], bilinear(reliability
+        [H/8,W/8]) [n], bicubic(feats [H/8,W/8,64]) [n,64] -- the test entry imcui_hip_xfeat_sample_probe."""
+        hd = get_handle(kpt_heat.device)
+        H, W = kpt_heat.shape
+        dev = kpt_heat.device
+        if tuple(reliability.shape) != (H // 8, W // 8) or tuple(feats.shape) != (H // 8, W // 8, 64):
+            raise ValueError(f"reliability {tuple(reliability.shape)} / feats {tuple(feats.shape)} do not match a {H} x {W} key-point map")
+        xy = xy.to(dev, torch.int32).contiguous()
+        n = xy.shape[0]
+        near = torch.empty((n,), dtype=torch.float32, device=dev)
+        bil = torch.empty((n,), dtype=torch.float32, device=dev)
+        cub = torch.empty((n, 64), dtype=torch.float32, device=dev)
+        hd.launch(hd.lib.imcui_hip_xfeat_sample_probe, _ptr(kpt_heat.contiguous().float()), _ptr(reliability.contiguous().float()),
+                  _ptr(feats.contiguous().float()), H, W, _ptr(xy), n, _ptr(near), _ptr(bil), _ptr(cub))  # fmt: skip
+        return near, bil, cub
+
+
 # ------------------------------------------------------------------ ALIKED
 ALIKED_MODELS = ("aliked-n16", "aliked-n16rot")  # (c1,c2,c3,c4,dim,K,M) = (16,32,64,128,128,3,16): what csrc/aliked.hip is built for
 

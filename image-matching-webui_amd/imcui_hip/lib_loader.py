@@ -78,6 +78,17 @@ SIGNATURES = {
         C.c_int,
         [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_float] * 2 + [C.c_int] * 6 + [C.c_void_p] * 14 + [C.c_void_p, C.c_size_t, C.c_void_p],
     ),
+    "imcui_hip_xfeat_packed_floats": (C.c_size_t, []),
+    "imcui_hip_xfeat_num_tensors": (C.c_int, []),
+    "imcui_hip_xfeat_tensor_name": (C.c_char_p, [C.c_int]),
+    "imcui_hip_xfeat_pack_weights": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p]),
+    "imcui_hip_xfeat_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
+    "imcui_hip_xfeat_max_keypoints_bound": (C.c_int, [C.c_int] * 2),
+    "imcui_hip_xfeat_forward": (
+        C.c_int,
+        [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_float, C.c_int, C.c_int] + [C.c_void_p] * 8 + [C.c_void_p, C.c_size_t, C.c_void_p],
+    ),
+    "imcui_hip_xfeat_sample_probe": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 2 + [C.c_void_p, C.c_int] + [C.c_void_p] * 4),
     "imcui_hip_superpoint_packed_floats": (C.c_size_t, []),
     "imcui_hip_superpoint_pack_weights": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p]),
     "imcui_hip_superpoint_workspace_bytes": (C.c_size_t, [C.c_int] * 4),

@@ -617,3 +617,50 @@ def aliked_state_dict(seed: int = 0, score_gain: float = 4.0, score_shift: float
     sd["desc_head.offset_conv.2.bias"] = rn(32)
     sd["desc_head.sf_conv.weight"] = rn(128, 128, 1, 1)  # (a sample is a unit vector, or an interpolation of four)
     return sd
+
+
+# XFeat (verlab/accelerated_features XFeatModel): (state-dict block, [(cin, cout, kernel)] of its BasicLayers, final plain convolution)
+XFEAT_BLOCKS = [
+    ("block1", [(1, 4, 3), (4, 8, 3), (8, 8, 3), (8, 24, 3)], None),
+    ("block2", [(24, 24, 3), (24, 24, 3)], None),
+    ("block3", [(24, 64, 3), (64, 64, 3), (64, 64, 1)], None),
+    ("block4", [(64, 64, 3), (64, 64, 3), (64, 64, 3)], None),
+    ("block5", [(64, 128, 3), (128, 128, 3), (128, 128, 3), (128, 64, 1)], None),
+    ("block_fusion", [(64, 64, 3), (64, 64, 3)], (64, 64)),
+    ("heatmap_head", [(64, 64, 1), (64, 64, 1)], (64, 1)),
+    ("keypoint_head", [(64, 64, 1), (64, 64, 1), (64, 64, 1)], (64, 65)),
+]
+
+
+def xfeat_state_dict(seed: int = 0, logit_gain: float = 0.5, dustbin_bias: float = 0.5, reliability_gain: float = 1.5) -> dict:
+    """Seeded XFeat weights with upstream's key names, the `num_batches_tracked` counters and two `fine_matcher.*` tensors included
+    (a loader has to skip both).  Convolutions are Kaiming-scaled, BatchNorm running statistics are NOT the identity.  The last
+    key-point convolution carries `logit_gain` and the dustbin `dustbin_bias`, so that the 65-way soft-max has peaks on both sides of
+    the 0.05 detection threshold (uniform would be 1/65).  The reliability convolution sees ReLU outputs, all positive: its weights are
+    centred over the channels and its bias is -1, and `reliability_gain` then spreads the logits over about a unit either side of zero, so
+    the sigmoid is not saturated (tests/test_xfeat_cpu.py asserts the key-point count on the seeded image and the reliability range)."""
+    g = torch.Generator().manual_seed(seed)
+    sd = {}
+
+    def rn(*shape, scale=1.0):
+        return torch.randn(*shape, generator=g) * scale
+
+    sd["skip1.1.weight"] = rn(24, 1, 1, 1, scale=0.5)
+    sd["skip1.1.bias"] = rn(24, scale=0.1)
+    for name, layers, last in XFEAT_BLOCKS:
+        for i, (cin, cout, k) in enumerate(layers):
+            sd[f"{name}.{i}.layer.0.weight"] = rn(cout, cin, k, k, scale=math.sqrt(2.0 / (cin * k * k)))
+            sd[f"{name}.{i}.layer.1.running_mean"] = rn(cout, scale=0.2)
+            sd[f"{name}.{i}.layer.1.running_var"] = 0.5 + torch.rand(cout, generator=g)
+            sd[f"{name}.{i}.layer.1.num_batches_tracked"] = torch.tensor(1000, dtype=torch.long)
+        if last is not None:
+            cin, cout = last
+            gain = {"keypoint_head": logit_gain, "heatmap_head": reliability_gain}.get(name, 1.0)
+            sd[f"{name}.{len(layers)}.weight"] = rn(cout, cin, 1, 1, scale=gain / math.sqrt(cin))
+            sd[f"{name}.{len(layers)}.bias"] = rn(cout, scale=0.05)
+    sd["keypoint_head.3.bias"][64] = dustbin_bias
+    sd["heatmap_head.2.weight"] -= sd["heatmap_head.2.weight"].mean()
+    sd["heatmap_head.2.bias"][0] = -1.0
+    sd["fine_matcher.0.weight"] = rn(512, 128, scale=1.0 / math.sqrt(128))
+    sd["fine_matcher.0.bias"] = rn(512, scale=0.05)
+    return sd

@@ -219,6 +219,42 @@ int imcui_hip_sift_forward(imcui_hip_t* h, const float* image, int B, int C, int
                            int* counts, float* dbg_pyramid, int* dbg_extrema, float* dbg_refined, float* dbg_hist, float* dbg_table,
                            float* dbg_desc_raw, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- XFeat (zoo entry xfeat(sparse) = `feature: xfeat` + NN-mutual; imcui/hloc/extractors/xfeat.py:8-34) ---------------- */
+/* Weight packing runs on the HOST (replaces the `torch.hub.load("verlab/accelerated_features", "XFeat")` of xfeat.py:17-21): tensor i
+ * is the XFeatModel state-dict entry named imcui_hip_xfeat_tensor_name(i) (skip1.1.*, then block1 .. keypoint_head in module order,
+ * without the `num_batches_tracked` counters and without `fine_matcher.*`); BatchNorm2d(affine=False) in eval mode is folded into the
+ * convolution before it: w / sqrt(var + 1e-5), bias -mean / sqrt(var + 1e-5).  `packed` receives imcui_hip_xfeat_packed_floats()
+ * floats; it begins with block1.0 folded as [9 taps][4] floats followed (from float 64) by its 4 folded biases. */
+size_t imcui_hip_xfeat_packed_floats(void);
+int imcui_hip_xfeat_num_tensors(void);
+const char* imcui_hip_xfeat_tensor_name(int i);
+int imcui_hip_xfeat_pack_weights(const float* const* tensors, float* packed);
+/* Scratch of imcui_hip_xfeat_forward for B images of H x W (independent of the threshold, top_k and kcap). */
+size_t imcui_hip_xfeat_workspace_bytes(int B, int H, int W);
+/* Bound on the key-points of an H x W image whose scores do not tie exactly: survivors of the 5x5 NMS are more than 2 pixels apart.
+ * An exact plateau (a constant image) keeps every member and can exceed it, up to (H / 32 * 32) * (W / 32 * 32). */
+int imcui_hip_xfeat_max_keypoints_bound(int H, int W);
+/* imcui/hloc/extractors/xfeat.py:26-34 `self.net.detectAndCompute(data["image"], top_k=max_keypoints)[0]`.
+ * image [dev, B,C,H,W] in [0,1], C = 1 or 3, H, W >= 32: resized (bilinear, align_corners=False) to Hr x Wr = multiples of 32, channel
+ * mean, InstanceNorm, XFeatModel, then NMS (5x5, `==` max and > threshold), score = nearest(key-point map) x bilinear(reliability), a
+ * key-point at (0, 0) scores -1, order by descending score (ties: lower flat index first), Python's `[:top_k]` per image (-1 drops the
+ * lowest), bicubic descriptors, key-points x (W / Wr, H / Hr), score > 0.  threshold: xfeat.py never passes its `keypoint_threshold`,
+ * so the reference runs at upstream's 0.05.
+ * Outputs, fixed stride `kcap` per image, first num_keypoints[b] entries valid, the rest zero, in descending score order:
+ *   keypoints [dev, B,kcap,2] (x, y) in pixels of the H x W image;  scores [dev, B,kcap]
+ *   descriptors [dev, B,kcap,64] L2-normalised rows;  num_keypoints [dev, B] int32
+ *   status [dev, 1] int32 optional: 0 = fine, bit 1 = more key-points than kcap (the first kcap are returned)
+ *   kpt_heat [dev, B,Hr,Wr], reliability [dev, B,Hr/8,Wr/8], feats_norm [dev, B,Hr/8,Wr/8,64] (NHWC) optional: the dense maps
+ * Zero key-points is a valid result.  No host synchronisation. */
+int imcui_hip_xfeat_forward(imcui_hip_t* h, const float* packed, const float* image, int B, int C, int H, int W, float threshold, int top_k, int kcap,
+                            float* keypoints, float* scores, float* descriptors, int* num_keypoints, int* status, float* kpt_heat, float* reliability,
+                            float* feats_norm, void* ws, size_t ws_bytes, void* stream);
+/* Test entry: the sampling rules of the selection (xfeat.py:30 -> InterpolateSparse2d: F.grid_sample at 2 * (xy / (W - 1, H - 1)) - 1,
+ * align_corners=False) at n integer pixels xy [dev, n,2] int32 of an H x W image (multiples of 8): kpt_heat [dev, H,W] sampled nearest,
+ * reliability [dev, H/8,W/8] bilinear, feats [dev, H/8,W/8,64] bicubic (not normalised) -> nearest [n], bilinear [n], bicubic [n,64]. */
+int imcui_hip_xfeat_sample_probe(imcui_hip_t* h, const float* kpt_heat, const float* reliability, const float* feats, int H, int W, const int* xy, int n,
+                                 float* nearest, float* bilinear, float* bicubic, void* stream);
+
 /* ---- LightGlue --------------------------------------------- */
 /* Host-side packing of the upstream state dict (9 layers, dim 256, 4 heads).  `tensors` holds the
  * host pointers of imcui_hip_lightglue_num_tensors() tensors; tensor i is the upstream state-dict
