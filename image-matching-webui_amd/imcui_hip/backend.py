@@ -545,6 +545,147 @@ class AlikedHIP:
         return out
 
 
+# ------------------------------------------------------------------ ALIKE
+ALIKE_MODELS = {"alike-t": 0, "alike-s": 1, "alike-n": 2}  # the variant numbers of include/imcui_hip.h
+ALIKE_CFG = {"alike-t": (8, 16, 32, 64, 64), "alike-s": (8, 16, 48, 96, 96), "alike-n": (16, 32, 64, 128, 128)}  # (c1, c2, c3, c4, dim)
+
+
+def alike_check_model(model_name: str) -> int:
+    """The variant number of a served model; alike-l and unknown names are refused by name."""
+    if model_name not in ALIKE_MODELS:
+        known = "alike-l has a second head layer (convhead1 + ReLU) that the sparse head cannot express" if model_name == "alike-l" else "unknown name"
+        raise ImcuiHipError(f"ALIKE model '{model_name}' is not served by the HIP backend ({known}); supported: {', '.join(ALIKE_MODELS)}")
+    return ALIKE_MODELS[model_name]
+
+
+def alike_tensor_names(model_name: str = "alike-t") -> list[str]:
+    v, lib = alike_check_model(model_name), load_library()
+    return [lib.imcui_hip_alike_tensor_name(v, i).decode() for i in range(lib.imcui_hip_alike_num_tensors(v))]
+
+
+def alike_tensor_shapes(model_name: str = "alike-t") -> dict:
+    """Upstream ALIKE's state-dict shapes (without the `num_batches_tracked` counters)."""
+    alike_check_model(model_name)
+    c1, c2, c3, c4, dim = ALIKE_CFG[model_name]
+    ch = [3, c1, c2, c3, c4]
+    shapes = {}
+    for b in range(1, 5):
+        cin, cout = ch[b - 1], ch[b]
+        for j in (1, 2):
+            shapes[f"block{b}.conv{j}.weight"] = (cout, cin if j == 1 else cout, 3, 3)
+            for k in ("weight", "bias", "running_mean", "running_var"):
+                shapes[f"block{b}.bn{j}.{k}"] = (cout,)
+        if b >= 2:
+            shapes[f"block{b}.downsample.weight"] = (cout, cin, 1, 1)
+            shapes[f"block{b}.downsample.bias"] = (cout,)
+    for i in range(1, 5):
+        shapes[f"conv{i}.weight"] = (dim // 4, ch[i], 1, 1)
+    shapes["convhead2.weight"] = (dim + 1, dim, 1, 1)
+    return shapes
+
+
+def pack_alike(state_dict: dict, model_name: str = "alike-t") -> torch.Tensor:
+    """Upstream ALIKE state dict -> packed float32 buffer (host); BatchNorm (eval) is folded into the convolutions by the packer.
+    Strict: `num_batches_tracked` counters are ignored, every other key is consumed exactly once, every shape checked."""
+    v = alike_check_model(model_name)
+    lib = load_library()
+    names, shapes = alike_tensor_names(model_name), alike_tensor_shapes(model_name)
+    sd = {k: t for k, t in state_dict.items() if not k.endswith("num_batches_tracked")}
+    missing = [n for n in names if n not in sd]
+    extra = sorted(set(sd) - set(names))
+    if missing or extra:
+        raise ImcuiHipError(f"ALIKE state dict does not match upstream's {model_name} layout: missing {missing[:4]}, unexpected {extra[:4]}")
+    arrs = []
+    for n in names:
+        a = _as_f32_host(sd[n])
+        if a.shape != shapes[n]:
+            raise ImcuiHipError(f"ALIKE state dict: '{n}' has shape {a.shape}, expected {shapes[n]}")
+        arrs.append(a)
+    packed = np.zeros(lib.imcui_hip_alike_packed_floats(v), dtype=np.float32)
+    tp = (C.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
+    rc = lib.imcui_hip_alike_pack_weights(v, tp, packed.ctypes.data)
+    if rc != 0:
+        raise ImcuiHipError(f"imcui_hip_alike_pack_weights failed ({rc})")
+    return torch.from_numpy(packed)
+
+
+def alike_check_args(image_shape, model_name: str = "alike-t") -> None:
+    """Refusals raised before anything is launched."""
+    alike_check_model(model_name)
+    if len(image_shape) != 4 or image_shape[1] != 3:  # (the reference fails its `three == 3` assertion on gray input)
+        raise ValueError(f"ALIKE expects an RGB image [B,3,H,W], got shape {tuple(image_shape)}")
+    if image_shape[2] < 32 or image_shape[3] < 32:
+        raise ValueError(f"ALIKE needs images of at least 32 x 32, got {tuple(image_shape[2:])}")
+
+
+class AlikeHIP:
+    def __init__(self, model_name: str = "alike-t"):
+        self.variant = alike_check_model(model_name)
+        self.model_name = model_name
+        self.dims = ALIKE_CFG[model_name]
+        self._ws = _Workspace()
+
+    def forward(self, packed: torch.Tensor, image: torch.Tensor, conf: dict, want_maps: bool = False, kcap: int | None = None):
+        """image [B,3,H,W] float32 on the GPU -> fixed-stride outputs, no host synchronisation: keypoints [B,K,2] (pixels), scores [B,K],
+        descriptors [B,K,dim], num_keypoints [B] int32, status [1] int32 (bit 1: `kcap` too small).  Order: row-major, or descending score
+        for the top_k route and after an n_limit cut.  want_maps adds score_map [B,H,W], x4 [B,Hp/32,Wp/32,c4 stored] and the branch maps
+        f2 / f3 / f4 [B,Hp/2^s,Wp/2^s,dim/4].  K = min(top_k, n_limit, the NMS bound)."""
+        alike_check_args(tuple(image.shape), self.model_name)
+        hd = get_handle(image.device)
+        if packed.device != image.device:
+            raise ImcuiHipError("packed weights and image live on different devices")
+        lib, v = hd.lib, self.variant
+        image = image.contiguous().float()
+        B, _, H, W = image.shape
+        top_k, n_limit = int(conf["top_k"]), int(conf["max_keypoints"])
+        dim = self.dims[4]
+        if kcap is None:
+            kcap = lib.imcui_hip_alike_max_keypoints_bound(H, W)
+            for lim in (top_k, n_limit):
+                if lim > 0:
+                    kcap = min(kcap, lim)
+        kcap = max(1, min(int(kcap), H * W))
+        dev = image.device
+        f32 = dict(dtype=torch.float32, device=dev)
+        kpts = torch.empty((B, kcap, 2), **f32)
+        scores = torch.empty((B, kcap), **f32)
+        desc = torch.empty((B, kcap, dim), **f32)
+        nk = torch.empty((B,), dtype=torch.int32, device=dev)
+        status = torch.empty((1,), dtype=torch.int32, device=dev)
+        Hp, Wp = (H + 31) // 32 * 32, (W + 31) // 32 * 32
+        maps = {}
+        if want_maps:
+            c4p = (self.dims[3] + 31) // 32 * 32
+            maps = dict(score_map=torch.empty((B, H, W), **f32), x4=torch.empty((B, Hp // 32, Wp // 32, c4p), **f32),
+                        f2=torch.empty((B, Hp // 2, Wp // 2, dim // 4), **f32), f3=torch.empty((B, Hp // 8, Wp // 8, dim // 4), **f32),
+                        f4=torch.empty((B, Hp // 32, Wp // 32, dim // 4), **f32))  # fmt: skip
+        with self._ws.use(lib.imcui_hip_alike_workspace_bytes(v, B, H, W), dev) as ws:
+            hd.launch(
+                lib.imcui_hip_alike_forward, v, _ptr(packed), _ptr(image), B, H, W, float(conf["detection_threshold"]), top_k, n_limit,
+                int(bool(conf.get("sub_pixel", False))), kcap, _ptr(kpts), _ptr(scores), _ptr(desc), _ptr(nk), _ptr(status), _ptr(maps.get("score_map")),
+                _ptr(maps.get("x4")), _ptr(maps.get("f2")), _ptr(maps.get("f3")), _ptr(maps.get("f4")), _ptr(ws), ws.numel(),
+            )  # fmt: skip
+        out = {"keypoints": kpts, "scores": scores, "descriptors": desc, "num_keypoints": nk, "status": status}
+        out.update(maps)
+        return out
+
+    def desc_probe(self, packed: torch.Tensor, image: torch.Tensor, xy: torch.Tensor) -> torch.Tensor:
+        """Test entry: the sparse descriptor head at integer pixels xy [n,2] (x, y) of ONE image [1,3,H,W] -> [n,dim]."""
+        alike_check_args(tuple(image.shape), self.model_name)
+        hd = get_handle(image.device)
+        lib, v = hd.lib, self.variant
+        image = image.contiguous().float()
+        _, _, H, W = image.shape
+        xy = xy.to(device=image.device, dtype=torch.int32).contiguous()
+        n = xy.shape[0]
+        if n == 0 or int(xy[:, 0].min()) < 0 or int(xy[:, 0].max()) >= W or int(xy[:, 1].min()) < 0 or int(xy[:, 1].max()) >= H:
+            raise ValueError("desc_probe: pixels outside the image (or none)")
+        desc = torch.empty((n, self.dims[4]), dtype=torch.float32, device=image.device)
+        with self._ws.use(lib.imcui_hip_alike_workspace_bytes(v, 1, H, W), image.device) as ws:
+            hd.launch(lib.imcui_hip_alike_desc_probe, v, _ptr(packed), _ptr(image[:1]), H, W, _ptr(xy), n, _ptr(desc), _ptr(ws), ws.numel())
+        return desc
+
+
 # ------------------------------------------------------------------ SIFT
 SIFT_LAYERS = (3, 4, 5)  # nOctaveLayers (the wrapper's `num_octaves`) csrc/sift.hip is written for: blur radius at most 13
 

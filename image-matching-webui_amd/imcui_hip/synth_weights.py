@@ -619,6 +619,72 @@ def aliked_state_dict(seed: int = 0, score_gain: float = 4.0, score_shift: float
     return sd
 
 
+ALIKE_CFG = {"alike-t": (8, 16, 32, 64, 64), "alike-s": (8, 16, 48, 96, 96), "alike-n": (16, 32, 64, 128, 128)}  # (c1, c2, c3, c4, dim)
+
+
+# logit shift that centres the NMS survivors of the seed-0 networks on the 0.5 threshold at score_gain 3 (measured with the restatement
+# on the seeded test images: the survivors' median logit at gain 1 is about -0.85 / -1.3 / +1.0)
+ALIKE_SCORE_SHIFT = {"alike-t": 2.5, "alike-s": 3.9, "alike-n": -3.0}
+
+
+def alike_state_dict(variant: str = "alike-t", seed: int = 0, score_gain: float = 3.0, score_shift: float | None = None, fallback: bool = False) -> dict:
+    """Seeded ALIKE weights (upstream's key names; the `num_batches_tracked` counters of the BatchNorms included, a loader has to skip
+    them).  Convolutions are Kaiming-scaled (ReLU), BatchNorm running statistics are NOT the identity, the shortcuts carry a bias.
+    convhead2 has no bias and sees ReLU outputs, all positive, so a plain draw leaves the score logits far from zero (alike-t below,
+    alike-n above): the score row is centred over the channels of each branch and carries `score_gain`, and one channel is a constant
+    all the way -- x1[c1 - 1] = ReLU(block1.bn2.bias) = 1 behind an all-zero filter, passed on by a one-hot row of conv1 -- which the
+    score row weighs with `score_shift` (the descriptor rows with zero), so that every logit is shifted by exactly that.  With the
+    defaults (`score_shift=None`: ALIKE_SCORE_SHIFT) the 0.5 threshold falls inside the distribution of the NMS survivors;
+    `fallback=True` lowers the shift by 8, which keeps every score below it (the mean fallback).  tests/test_alike_cpu.py asserts both."""
+    c1, c2, c3, c4, dim = ALIKE_CFG[variant]
+    if score_shift is None:
+        score_shift = ALIKE_SCORE_SHIFT[variant]
+    if fallback:
+        score_shift -= 8.0
+    g = torch.Generator().manual_seed(seed)
+    sd = {}
+
+    def rn(*shape, scale=1.0):
+        return torch.randn(*shape, generator=g) * scale
+
+    def conv(name, cout, cin, k, gain=math.sqrt(2.0)):
+        sd[name] = rn(cout, cin, k, k, scale=gain / math.sqrt(cin * k * k))
+
+    def bn(name, c):
+        sd[f"{name}.weight"] = 1.0 + 0.2 * rn(c)
+        sd[f"{name}.bias"] = 0.1 * rn(c)
+        sd[f"{name}.running_mean"] = 0.2 * rn(c)
+        sd[f"{name}.running_var"] = 0.5 + torch.rand(c, generator=g)
+        sd[f"{name}.num_batches_tracked"] = torch.tensor(1000, dtype=torch.long)
+
+    ch = [3, c1, c2, c3, c4]
+    for b in range(1, 5):
+        cin, cout = ch[b - 1], ch[b]
+        for j in (1, 2):
+            conv(f"block{b}.conv{j}.weight", cout, cin if j == 1 else cout, 3, gain=2.0 * math.sqrt(2.0) if b == 1 and j == 1 else math.sqrt(2.0))
+            bn(f"block{b}.bn{j}", cout)
+        if b >= 2:
+            conv(f"block{b}.downsample.weight", cout, cin, 1, gain=1.0)
+            sd[f"block{b}.downsample.bias"] = 0.1 * rn(cout)
+    dq = dim // 4
+    for i in range(1, 5):
+        conv(f"conv{i}.weight", dq, ch[i], 1)
+    head = rn(dim + 1, dim, 1, 1, scale=1.0 / math.sqrt(dim))
+    row = head[dim, :, 0, 0].reshape(4, dq)
+    row = (row - row.mean(dim=1, keepdim=True)) * score_gain
+    head[dim, :, 0, 0] = row.reshape(-1)
+    # the constant channel (see above)
+    sd["block1.conv2.weight"][c1 - 1] = 0.0
+    for k, v in (("weight", 1.0), ("bias", 1.0), ("running_mean", 0.0), ("running_var", 1.0)):
+        sd[f"block1.bn2.{k}"][c1 - 1] = v
+    sd["conv1.weight"][dq - 1] = 0.0
+    sd["conv1.weight"][dq - 1, c1 - 1, 0, 0] = 1.0
+    head[:dim, dq - 1] = 0.0
+    head[dim, dq - 1, 0, 0] = score_shift
+    sd["convhead2.weight"] = head
+    return sd
+
+
 # XFeat (verlab/accelerated_features XFeatModel): (state-dict block, [(cin, cout, kernel)] of its BasicLayers, final plain convolution)
 XFEAT_BLOCKS = [
     ("block1", [(1, 4, 3), (4, 8, 3), (8, 8, 3), (8, 24, 3)], None),

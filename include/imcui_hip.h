@@ -183,6 +183,46 @@ int imcui_hip_aliked_forward(imcui_hip_t* h, const float* packed, const float* i
                              int max_keypoints, int kcap, float* keypoints, float* scores, float* descriptors, int* num_keypoints, int* status,
                              float* score_map, float* keypoints_norm, float* dbg_x3, float* dbg_x4, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- ALIKE (zoo entry alike = `feature: alike` + NN-mutual; imcui/hloc/extractors/alike.py) ------------------------------- */
+/* variant: 0 alike-t (c1..c4, dim = 8,16,32,64, 64), 1 alike-s (8,16,48,96, 96), 2 alike-n (16,32,64,128, 128); DKD radius 2.  alike-l
+ * (a second head layer behind a ReLU) is not served: every entry refuses other values (0 / NULL / IMCUI_ERR_UNSUPPORTED).
+ * Weight packing runs on the HOST (replaces the `ALike(**configs[...])` construction of alike.py:31-45): tensor i is the state-dict
+ * entry named imcui_hip_alike_tensor_name(variant, i) (block{1..4}.conv{1,2}.weight, .bn{1,2}.{weight,bias,running_mean,running_var},
+ * block{2..4}.downsample.{weight,bias}, conv{1..4}.weight, convhead2.weight; no `num_batches_tracked` counters); BatchNorm (eval,
+ * eps 1e-5) is folded into the convolution before it.  `packed` receives imcui_hip_alike_packed_floats(variant) floats; it begins with
+ * block1.conv1 folded with block1.bn1 as [9 taps][3][c1] floats followed (from the next multiple of 64 floats) by the c1 folded biases. */
+size_t imcui_hip_alike_packed_floats(int variant);
+int imcui_hip_alike_num_tensors(int variant);
+const char* imcui_hip_alike_tensor_name(int variant, int i);
+int imcui_hip_alike_pack_weights(int variant, const float* const* tensors, float* packed);
+/* Scratch of imcui_hip_alike_forward for B images of H x W (independent of the selection arguments and kcap). */
+size_t imcui_hip_alike_workspace_bytes(int variant, int B, int H, int W);
+/* Bound on the key-points of an H x W image whose scores do not tie exactly: simple_nms survivors are more than 2 pixels apart. */
+int imcui_hip_alike_max_keypoints_bound(int H, int W);
+/* alike.py:47-61 `self.net(image, sub_pixel)`: image [dev, B,3,H,W] RGB in [0,1], H, W >= 32, read as (x * 255) / 255 in float32 (the
+ * wrapper's and upstream's scaling), zero-padded at the bottom and right to multiples of 32; encoder, head, DKD (radius 2):
+ * simple_nms, rows / columns [0, 2] and the last 2 zeroed; top_k > 0: the top_k highest positive NMS scores in descending order; else
+ * threshold > 0: nms > threshold, or nms > mean(score map) when an image has none (per image); else nms > mean; survivors in row-major
+ * order; more than n_limit (> 0) of them: the n_limit highest scores, then in DESCENDING score order.  Ties go to the lower flat index.
+ * sub_pixel == 0: n = idx / (W - 1, H - 1) * 2 - 1 in float32, score = bilinear sample of the score map at n, descriptor = the head at
+ * pixel trunc((n + 1) / 2 * (W - 1, H - 1)) (upstream's round trip: sometimes the pixel before), key-point = (n + 1) / 2 * (W - 1, H - 1).
+ * sub_pixel != 0: n from the soft-argmax (temperature 0.1, 5x5 patch of the raw score map), descriptor = bilinear sample of the
+ * normalised descriptor map at n.  Descriptors are normalised again.
+ * Outputs, fixed stride `kcap` per image, first num_keypoints[b] entries valid, the rest zero:
+ *   keypoints [dev, B,kcap,2] (x, y) in pixels;  scores [dev, B,kcap];  descriptors [dev, B,kcap,dim];  num_keypoints [dev, B] int32
+ *   status [dev, 1] int32 optional: 0 = fine, bit 1 = more key-points than kcap (the first kcap of the output order are returned)
+ *   score_map [dev, B,H,W] optional;  dbg_x4 [dev, B,Hp/32,Wp/32,c4 stored as a multiple of 32] optional: block 4's output (NHWC);
+ *   dbg_f2 / dbg_f3 / dbg_f4 [dev, B,Hp/2^s,Wp/2^s,dim/4] (s = 1, 3, 5) optional: the branch maps ReLU(conv_i x_i) before up-sampling
+ * Zero key-points is a valid result.  No host synchronisation. */
+int imcui_hip_alike_forward(imcui_hip_t* h, int variant, const float* packed, const float* image, int B, int H, int W, float threshold, int top_k,
+                            int n_limit, int sub_pixel, int kcap, float* keypoints, float* scores, float* descriptors, int* num_keypoints,
+                            int* status, float* score_map, float* dbg_x4, float* dbg_f2, float* dbg_f3, float* dbg_f4, void* ws, size_t ws_bytes,
+                            void* stream);
+/* Test entry: the sparse descriptor head at n integer pixels xy [dev, n,2] int32 (x, y) of ONE image [dev, 3,H,W] -> descriptors
+ * [dev, n,dim] = F.normalize(descriptor_map)[:, y, x].  ws: imcui_hip_alike_workspace_bytes(variant, 1, H, W). */
+int imcui_hip_alike_desc_probe(imcui_hip_t* h, int variant, const float* packed, const float* image, int H, int W, const int* xy, int n,
+                               float* descriptors, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- SIFT (zoo entry sift-lightglue, and `sift` + NN; imcui/hloc/extractors/sift.py, backend "opencv") ------------------- */
 /* OpenCV 4.x SIFT_create(contrastThreshold, nfeatures, edgeThreshold, nOctaveLayers = `layers`; sigma 1.6, first octave -1, float
  * pipeline) -> detectAndCompute (sift.py:61-78), then `filter_dog_point` (:19-52), the score top-k (:188-193) and
