@@ -1,8 +1,10 @@
 // Kernels and helpers that ALIKED (aliked.hip) and its predecessor ALIKE (alike.hip) both use: the 3x3 convolution on the VALU (LDS
-// tiles), the align_corners=True tap of a bilinear up-sampling, the mean / threshold kernels of DKD and its candidate predicate.
+// tiles), the pooling kernel, the align_corners=True tap of a bilinear up-sampling and the candidate stage of DKD (mean / threshold
+// kernels, the candidate predicate, the count / scan / compact sequence with its mean fallback).
 // Device code and launch helpers only; what a network does with them stays in its own file.
 #pragma once
 #include "common.h"
+#include "select.h"
 
 namespace {  // internal linkage: two translation units include these kernels
 
@@ -96,6 +98,49 @@ __global__ __launch_bounds__(256) void ak_conv3_kernel(AkConvP p) {
     }
 }
 
+// ------------------------------------------------------------------ avg_pool2d(k) / max_pool2d(k) of an NHWC map: C channels of
+// [n, k ho, k wo, lds] -> [n, ho, wo, ldd]; channels [C, ldd) are written as zero (the implicit GEMM's channel padding).  C, lds, ldd
+// multiples of 4.  Average: row-major window sum from zero, then / k^2.  Maximum: starts from the window's first element.
+template <bool MAX>
+__global__ __launch_bounds__(256) void ak_pool_kernel(const float* __restrict__ src, int lds, int C, float* __restrict__ dst, int ldd, int k, int ho,
+                                                      int wo, long n4) {
+    const int D4 = ldd >> 2;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
+        const int c = (int)(i % D4) * 4;
+        long t = i / D4;
+        const int x = (int)(t % wo);
+        t /= wo;
+        const int y = (int)(t % ho);
+        const long b = t / ho;
+        float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (c < C) {
+            const int wi = k * wo;
+            const float* s = src + ((b * k * ho + (long)k * y) * wi + (long)k * x) * lds + c;
+            if (MAX) o = *reinterpret_cast<const float4*>(s);
+            for (int dy = 0; dy < k; ++dy)
+                for (int dx = 0; dx < k; ++dx) {
+                    const float4 v = *reinterpret_cast<const float4*>(s + ((long)dy * wi + dx) * lds);
+                    if (MAX) {
+                        o.x = fmaxf(o.x, v.x);
+                        o.y = fmaxf(o.y, v.y);
+                        o.z = fmaxf(o.z, v.z);
+                        o.w = fmaxf(o.w, v.w);
+                    } else {
+                        o.x += v.x;
+                        o.y += v.y;
+                        o.z += v.z;
+                        o.w += v.w;
+                    }
+                }
+            if (!MAX) {
+                const float d = (float)(k * k);
+                o = make_float4(o.x / d, o.y / d, o.z / d, o.w / d);
+            }
+        }
+        *reinterpret_cast<float4*>(dst + i * 4) = o;
+    }
+}
+
 // ------------------------------------------------------------------ bilinear up-sampling, align_corners=True (ATen's index rule)
 struct AkTap {
     int i0, i1;
@@ -157,5 +202,36 @@ static void ak_conv3(const AkConvP& p, int B, hipStream_t stream) {
     hipLaunchKernelGGL((ak_conv3_kernel<COUT, CC, ACT>), dim3(cdiv(p.W, 16), cdiv(p.H, 16), B), dim3(256), 0, stream, p);
 }
 
+// The candidate stage of DKD on the NMS map `nms` of the score map `smap` [B, H, W]: per-image threshold (the given one; 0 on the top-k
+// route; the image's mean when threshold <= 0 without top-k), candidates = nms > threshold inside rows / columns
+// [band_lo, size - band_hi), and where an image has no candidate above a given threshold its mean takes the threshold's place.  The
+// candidates leave in row-major order in cscore / cidx [B][H W], their counts in ncand [B].  *status is zeroed first.
+struct AkDkdWs {
+    float *mean, *thr;
+    int *blkcnt, *blkoff, *ncand;
+    float* cscore;
+    int* cidx;
+};
+static int ak_dkd_candidates(imcui_hip_s* h, const float* smap, const float* nms, int H, int W, int B, int band_lo, int band_hi, float threshold, bool topk,
+                             const AkDkdWs& s, int* status, hipStream_t stream) {
+    hipMemsetAsync(status, 0, sizeof(int), stream);
+    const int nchunk = cdiv(H * W, SEL_CHUNK), ccap = H * W;
+    hipLaunchKernelGGL(ak_mean_kernel, dim3(B), dim3(1024), 0, stream, smap, H * W, s.mean);
+    hipLaunchKernelGGL(ak_thr_kernel, dim3(1), dim3(1024), 0, stream, s.thr, s.mean, s.ncand, topk ? 0.0f : threshold, (topk || threshold > 0.0f) ? 0 : 1, B);
+    const AkIsCand is_cand{H, W, band_lo, band_hi, s.thr};
+    auto count = [&]() {
+        hipLaunchKernelGGL(cand_count_kernel<AkIsCand>, dim3(nchunk, B), dim3(256), 0, stream, nms, H * W, is_cand, s.blkcnt, nchunk);
+        hipLaunchKernelGGL(exclusive_scan_kernel<int>, dim3(B), dim3(1024), 0, stream, s.blkcnt, s.blkoff, s.ncand, (const int*)nullptr, nchunk, (long)nchunk);
+    };
+    count();
+    if (!topk && threshold > 0.0f) {  // no candidate above the threshold: the mean of the score map takes its place (per image)
+        hipLaunchKernelGGL(ak_thr_kernel, dim3(1), dim3(1024), 0, stream, s.thr, s.mean, s.ncand, 0.0f, 2, B);
+        count();
+    }
+    hipLaunchKernelGGL((cand_compact_kernel<AkIsCand, EmitScoreIndex>), dim3(nchunk, B), dim3(256), 0, stream, nms, H * W, is_cand, s.blkoff, nchunk, ccap,
+                       EmitScoreIndex{s.cscore, s.cidx, ccap});
+    IMCUI_CHECK_LAUNCH(h);
+    return IMCUI_OK;
+}
 
 }  // namespace

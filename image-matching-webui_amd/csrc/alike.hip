@@ -5,7 +5,7 @@
 // Data flow (NHWC maps; Hp x Wp = the image zero-padded at the bottom and right to multiples of 32; c2..c4 are STORED padded to
 // multiples of 32 -- P2, P3, P4 -- with zero weights and biases in the padding, so padded channels are exactly 0 after every ReLU):
 //   block1 3 -> c1 -> c1 at 1/1            fp32 FMA on the VALU, LDS tiles (ak_shared.h); the input is read as (x * 255) / 255
-//   max-pool 2 / 4 / 4                      al_maxpool_kernel
+//   max-pool 2 / 4 / 4                      ak_pool_kernel<true> (ak_shared.h)
 //   block2..4 at 1/2, 1/8, 1/32             implicit-GEMM 3x3 (gemm.hip, both arithmetic modes), ReLU in its epilogue; the 1x1 shortcut
 //                                           (with bias) is written first and enters conv2's epilogue as the residual
 //   f_i = ReLU(conv_i x_i), dim/4 channels, and g_i = w_score[slice i] . f_i, ONE float per branch pixel, at 1/2, 1/8, 1/32
@@ -22,10 +22,9 @@
 #include <string>
 #include <vector>
 
-#include "gemm.h"
-#include "imcui_hip.h"
-#include "select.h"
 #include "ak_shared.h"
+#include "imcui_hip.h"
+#include "netpack.h"
 
 #define AL_R 2      // DKD radius of every variant
 #define AL_KB 32    // key-points per workgroup step of al_desc_kernel (one 32-row MFMA tile)
@@ -41,49 +40,34 @@ static const AlVar AL_VARS[AL_NVAR] = {{"alike-t", {3, 8, 16, 32, 64}, 64}, {"al
 static const AlVar* al_var(int v) { return (v < 0 || v >= AL_NVAR) ? nullptr : &AL_VARS[v]; }
 static int al_pad(int c) { return (c + 31) / 32 * 32; }
 
-struct AlTensor {
-    std::string name;
-    size_t n;
-};
-static const std::vector<AlTensor>& al_tensors(int variant) {
-    static std::vector<AlTensor> built[AL_NVAR];
+static const TensorTable& al_tensors(int variant) {
+    static TensorTable built[AL_NVAR];
     static bool done = [] {
         for (int v = 0; v < AL_NVAR; ++v) {
             const AlVar& a = AL_VARS[v];
-            std::vector<AlTensor>& t = built[v];
+            TensorTable& t = built[v];
             for (int b = 1; b <= 4; ++b) {
                 const int cin = a.c[b - 1], cout = a.c[b];
                 const std::string p = "block" + std::to_string(b);
                 for (int j = 1; j <= 2; ++j) {
-                    t.push_back({p + ".conv" + std::to_string(j) + ".weight", (size_t)cout * (j == 1 ? cin : cout) * 9});
-                    for (const char* s : {"weight", "bias", "running_mean", "running_var"}) t.push_back({p + ".bn" + std::to_string(j) + "." + s, (size_t)cout});
+                    t.add(p + ".conv" + std::to_string(j) + ".weight", (size_t)cout * (j == 1 ? cin : cout) * 9);
+                    for (const char* s : {"weight", "bias", "running_mean", "running_var"}) t.add(p + ".bn" + std::to_string(j) + "." + s, (size_t)cout);
                 }
                 if (b >= 2) {
-                    t.push_back({p + ".downsample.weight", (size_t)cout * cin});
-                    t.push_back({p + ".downsample.bias", (size_t)cout});
+                    t.add(p + ".downsample.weight", (size_t)cout * cin);
+                    t.add(p + ".downsample.bias", (size_t)cout);
                 }
             }
-            for (int i = 1; i <= 4; ++i) t.push_back({"conv" + std::to_string(i) + ".weight", (size_t)(a.dim / 4) * a.c[i]});
-            t.push_back({"convhead2.weight", (size_t)(a.dim + 1) * a.dim});
+            for (int i = 1; i <= 4; ++i) t.add("conv" + std::to_string(i) + ".weight", (size_t)(a.dim / 4) * a.c[i]);
+            t.add("convhead2.weight", (size_t)(a.dim + 1) * a.dim);
         }
         return true;
     }();
     (void)done;
     return built[variant];
 }
-static int al_find(int variant, const char* name) {
-    const auto& t = al_tensors(variant);
-    for (size_t i = 0; i < t.size(); ++i)
-        if (t[i].name == name) return (int)i;
-    return -1;
-}
-
-extern "C" int imcui_hip_alike_num_tensors(int variant) { return al_var(variant) ? (int)al_tensors(variant).size() : 0; }
-extern "C" const char* imcui_hip_alike_tensor_name(int variant, int i) {
-    if (!al_var(variant)) return nullptr;
-    const auto& t = al_tensors(variant);
-    return (i < 0 || i >= (int)t.size()) ? nullptr : t[i].name.c_str();
-}
+extern "C" int imcui_hip_alike_num_tensors(int variant) { return al_var(variant) ? al_tensors(variant).size() : 0; }
+extern "C" const char* imcui_hip_alike_tensor_name(int variant, int i) { return al_var(variant) ? al_tensors(variant).name(i) : nullptr; }
 
 // ------------------------------------------------------------------ packed weight layout
 // vw / vb: block 1's two layers, [tap][cin][c1] + [c1].  GEMM layers [N][9 cin_stored]: block2.conv1 / conv2, block3.conv1 / conv2,
@@ -115,40 +99,28 @@ static AlDims al_dims(const AlVar& a) {
 }
 struct AlLayout {
     size_t vw[2], vb[2];
-    size_t gw[AL_NG], gb[AL_NG], gh[AL_NG], gl[AL_NG], gs[AL_NG];
+    GemmLayerOff g[AL_NG];
     size_t dw[3], db[3];
     size_t cw[4], sw, wdt;
     size_t total;
 };
 static AlLayout al_layout(const AlDims& d) {
     AlLayout l;
-    size_t off = 0;
-    auto get = [&](size_t n) {
-        const size_t o = off;
-        off += align_up(n, 64);
-        return o;
-    };
-    l.vw[0] = get((size_t)9 * 3 * d.c1);  // (block1.conv1 first: offset 0 of the packed buffer, see imcui_hip.h)
-    l.vb[0] = get(d.c1);
-    l.vw[1] = get((size_t)9 * d.c1 * d.c1);
-    l.vb[1] = get(d.c1);
-    for (int g = 0; g < AL_NG; ++g) {
-        const size_t K = (size_t)9 * d.gcin[g];
-        l.gw[g] = get(d.gn[g] * K);
-        l.gb[g] = get(d.gn[g]);
-        l.gh[g] = get(d.gn[g] * K / 2);
-        l.gl[g] = get(d.gn[g] * K / 2);
-        l.gs[g] = get(1);
-    }
+    PackCursor c;
+    l.vw[0] = c.get((size_t)9 * 3 * d.c1);  // (block1.conv1 first: offset 0 of the packed buffer, see imcui_hip.h)
+    l.vb[0] = c.get(d.c1);
+    l.vw[1] = c.get((size_t)9 * d.c1 * d.c1);
+    l.vb[1] = c.get(d.c1);
+    for (int g = 0; g < AL_NG; ++g) l.g[g].place(c, d.gn[g], 9 * d.gcin[g]);
     for (int i = 0; i < 3; ++i) {
-        l.dw[i] = get((size_t)d.P[i + 1] * d.P[i + 2]);
-        l.db[i] = get(d.P[i + 2]);
+        l.dw[i] = c.get((size_t)d.P[i + 1] * d.P[i + 2]);
+        l.db[i] = c.get(d.P[i + 2]);
     }
-    l.cw[0] = get((size_t)d.c1 * d.dq);
-    for (int i = 1; i < 4; ++i) l.cw[i] = get((size_t)d.P[i + 1] * d.dq);
-    l.sw = get(d.dim);
-    l.wdt = get((size_t)d.dim * d.dim);
-    l.total = off;
+    l.cw[0] = c.get((size_t)d.c1 * d.dq);
+    for (int i = 1; i < 4; ++i) l.cw[i] = c.get((size_t)d.P[i + 1] * d.dq);
+    l.sw = c.get(d.dim);
+    l.wdt = c.get((size_t)d.dim * d.dim);
+    l.total = c.off;
     return l;
 }
 extern "C" size_t imcui_hip_alike_packed_floats(int variant) {
@@ -167,18 +139,11 @@ extern "C" int imcui_hip_alike_pack_weights(int variant, const float* const* t, 
     const AlDims d = al_dims(*a);
     const AlLayout l = al_layout(d);
     memset(packed, 0, l.total * sizeof(float));
-    auto T = [&](const std::string& name) { return t[al_find(variant, name.c_str())]; };
+    const TensorTable& names = al_tensors(variant);
+    auto T = [&](const std::string& name) { return t[names.find(name)]; };
     std::vector<float> sc, sh, tmp;
-    auto fold = [&](const std::string& bn, int cout) {
-        const int i = al_find(variant, (bn + ".weight").c_str());
-        sc.assign(cout, 1.0f);
-        sh.assign(cout, 0.0f);
-        for (int c = 0; c < cout; ++c) {
-            const float s = t[i][c] / sqrtf(t[i + 3][c] + 1e-5f);
-            sc[c] = s;
-            sh[c] = t[i + 1][c] - t[i + 2][c] * s;
-        }
-    };
+    // (the four tensors of a BatchNorm follow each other in the table)
+    auto fold = [&](const std::string& bn, int cout) { bn_fold_f32(t + names.find(bn + ".weight"), cout, sc, sh); };
     for (int v = 0; v < 2; ++v) {  // block 1: OIHW -> [tap][cin][cout]
         const int cin = v == 0 ? 3 : d.c1, cout = d.c1;
         const float* w = T("block1.conv" + std::to_string(v + 1) + ".weight");
@@ -197,10 +162,9 @@ extern "C" int imcui_hip_alike_pack_weights(int variant, const float* const* t, 
         pack_conv_gemm(T(p + ".conv" + std::to_string(j) + ".weight"), cout, d.acin[g], 3, d.gcin[g], tmp.data());
         for (int co = 0; co < cout; ++co)
             for (int k = 0; k < K; ++k) tmp[(size_t)co * K + k] *= sc[co];
-        memcpy(packed + l.gw[g], tmp.data(), (size_t)N * K * sizeof(float));
-        memcpy(packed + l.gb[g], sh.data(), cout * sizeof(float));
-        packed[l.gs[g]] = split_weights_frag_host(packed + l.gw[g], N, K, reinterpret_cast<unsigned short*>(packed + l.gh[g]),
-                                                  reinterpret_cast<unsigned short*>(packed + l.gl[g]));
+        memcpy(packed + l.g[g].w, tmp.data(), (size_t)N * K * sizeof(float));
+        memcpy(packed + l.g[g].b, sh.data(), cout * sizeof(float));
+        l.g[g].split_planes(packed, N, K);
     }
     for (int i = 0; i < 3; ++i) {  // shortcuts [cout][cin] -> [cin stored][cout stored]
         const int cin = a->c[i + 1], cout = a->c[i + 2], ldo = d.P[i + 2];
@@ -224,36 +188,6 @@ extern "C" int imcui_hip_alike_pack_weights(int variant, const float* const* t, 
 }
 
 namespace {
-
-// ------------------------------------------------------------------ max_pool2d(k) of an NHWC map: C channels of [n, k ho, k wo, lds] ->
-// [n, ho, wo, ldd]; channels [C, ldd) are written as zero (the implicit GEMM's channel padding).  C, lds, ldd multiples of 4.
-__global__ __launch_bounds__(256) void al_maxpool_kernel(const float* __restrict__ src, int lds, int C, float* __restrict__ dst, int ldd, int k, int ho,
-                                                         int wo, long n4) {
-    const int D4 = ldd >> 2;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
-        const int c = (int)(i % D4) * 4;
-        long t = i / D4;
-        const int x = (int)(t % wo);
-        t /= wo;
-        const int y = (int)(t % ho);
-        const long b = t / ho;
-        float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (c < C) {
-            const int wi = k * wo;
-            const float* s = src + ((b * k * ho + (long)k * y) * wi + (long)k * x) * lds + c;
-            o = *reinterpret_cast<const float4*>(s);
-            for (int dy = 0; dy < k; ++dy)
-                for (int dx = 0; dx < k; ++dx) {
-                    const float4 v = *reinterpret_cast<const float4*>(s + ((long)dy * wi + dx) * lds);
-                    o.x = fmaxf(o.x, v.x);
-                    o.y = fmaxf(o.y, v.y);
-                    o.z = fmaxf(o.z, v.z);
-                    o.w = fmaxf(o.w, v.w);
-                }
-        }
-        *reinterpret_cast<float4*>(dst + i * 4) = o;
-    }
-}
 
 // 1x1 convolution with bias on the VALU (the shortcut of a ResBlock): out[p][co] = bias[co] + sum_ci in[p][ci] wt[ci][co], one thread
 // per (pixel, stored output channel), channels summed in ascending order
@@ -703,33 +637,14 @@ static int al_dense(imcui_hip_t* h, const AlDims& d, const AlLayout& l, const fl
     const int Hp = ak_pad32(H), Wp = ak_pad32(W);
     const bool split = h->precision == 1;
     int rc;
-#define ALRUN(x)                       \
-    do {                               \
-        rc = (x);                      \
-        if (rc != IMCUI_OK) return rc; \
-    } while (0)
     auto px = [&](int sh) { return (long)(Hp >> sh) * (Wp >> sh); };
     // implicit-GEMM 3x3 convolution (pad 1) of the NHWC map `in` + folded-BatchNorm bias (+ resid), ReLU
     auto conv_gemm = [&](int L, const float* in, int sh, float* out, const float* resid) -> int {
         GemmP g;
         g.epi = EPI_CONV;
         g.A = in;
-        g.W = P + l.gw[L];
-        g.ldw = 9 * d.gcin[L];
-        if (split) {
-            g.Wh = reinterpret_cast<const unsigned short*>(P + l.gh[L]);
-            g.Wl = reinterpret_cast<const unsigned short*>(P + l.gl[L]);
-            g.wscale = P + l.gs[L];
-        }
-        g.N = d.gn[L];
-        g.K = 9 * d.gcin[L];
-        g.bias = P + l.gb[L];
-        g.conv_k = 3;
-        g.conv_stride = 1;
-        g.conv_pad = 1;
-        g.conv_hin = g.conv_hout = Hp >> sh;
-        g.conv_win = g.conv_wout = Wp >> sh;
-        g.conv_cin = d.gcin[L];
+        gemm_set_weights(g, P, l.g[L], d.gn[L], 9 * d.gcin[L], split);
+        gemm_set_conv(g, 3, 1, 1, Hp >> sh, Wp >> sh, Hp >> sh, Wp >> sh, d.gcin[L]);
         g.M = (int)(B * px(sh));
         g.C = out;
         g.ldc = d.gn[L];
@@ -740,12 +655,12 @@ static int al_dense(imcui_hip_t* h, const AlDims& d, const AlLayout& l, const fl
     };
     auto pool = [&](const float* src, int lds, int C, float* dst, int ldd, int k, int sh_out) {
         const long n4 = (long)B * px(sh_out) * ldd / 4;
-        hipLaunchKernelGGL(al_maxpool_kernel, dim3(ak_grid(n4)), dim3(256), 0, stream, src, lds, C, dst, ldd, k, Hp >> sh_out, Wp >> sh_out, n4);
+        hipLaunchKernelGGL(ak_pool_kernel<true>, dim3(ak_grid(n4)), dim3(256), 0, stream, src, lds, C, dst, ldd, k, Hp >> sh_out, Wp >> sh_out, n4);
     };
     // a ResBlock at 1 / 2^sh: t = ReLU(bn1(conv1 x)); out = downsample(x) + bias; out = ReLU(bn2(conv2 t) + out)
     auto resblock = [&](int blk, const float* x, int sh, float* t, float* out) -> int {
         const int L = 2 * (blk - 2), cin = d.P[blk - 1], cout = d.P[blk];
-        ALRUN(conv_gemm(L, x, sh, t, nullptr));
+        IMCUI_RUN(conv_gemm(L, x, sh, t, nullptr));
         const long n = B * px(sh) * cout;
         hipLaunchKernelGGL(al_pw_kernel, dim3(ak_grid(n)), dim3(256), 0, stream, x, cin, cin, P + l.dw[blk - 2], P + l.db[blk - 2], out, cout, n);
         return conv_gemm(L + 1, t, sh, out, out);
@@ -776,11 +691,11 @@ static int al_dense(imcui_hip_t* h, const AlDims& d, const AlLayout& l, const fl
     }
     // ---- blocks 2..4
     pool(s.x1, d.c1, d.c1, s.p1, d.P[1], 2, 1);
-    ALRUN(resblock(2, s.p1, 1, s.t2, s.x2));
+    IMCUI_RUN(resblock(2, s.p1, 1, s.t2, s.x2));
     pool(s.x2, d.P[2], d.P[2], s.p2, d.P[2], 4, 3);
-    ALRUN(resblock(3, s.p2, 3, s.t3, s.x3));
+    IMCUI_RUN(resblock(3, s.p2, 3, s.t3, s.x3));
     pool(s.x3, d.P[3], d.P[3], s.p3, d.P[3], 4, 5);
-    ALRUN(resblock(4, s.p3, 5, s.t4, s.x4));
+    IMCUI_RUN(resblock(4, s.p3, 5, s.t4, s.x4));
     // ---- f_i and the score slices at the branch's resolution (f1 only ever in registers)
     head(1, s.x2, 1, s.f2, s.g2);
     head(2, s.x3, 3, s.f3, s.g3);
@@ -798,7 +713,6 @@ static int al_dense(imcui_hip_t* h, const AlDims& d, const AlLayout& l, const fl
             hipLaunchKernelGGL((al_score_kernel<16, 32>), grid, dim3(256), 0, stream, s.x1, c1t, ws1, s.g2, s.g3, s.g4, smap, H, W, Hp, Wp, np);
     }
     IMCUI_CHECK_LAUNCH(h);
-#undef ALRUN
     return IMCUI_OK;
 }
 
@@ -842,27 +756,16 @@ extern "C" int imcui_hip_alike_forward(imcui_hip_t* h, int variant, const float*
     const int rc1 = imcui_hip_simple_nms(h, smap, s.nms, B, H, W, AL_R, stream);
     if (rc1 != IMCUI_OK) return rc1;
     int* st = status ? status : s.status;
-    hipMemsetAsync(st, 0, sizeof(int), stream);
     const bool topk = top_k > 0;
-    const int nchunk = cdiv(H * W, SEL_CHUNK), ccap = H * W;
+    const int ccap = H * W;
     // the cut: top_k first, then n_limit (the smaller one decides; both keep the highest scores); 0 or less = no cut
     int limit = ccap;
     if (topk) limit = min(limit, top_k);
     if (n_limit > 0) limit = min(limit, n_limit);
-    hipLaunchKernelGGL(ak_mean_kernel, dim3(B), dim3(1024), 0, stream, smap, H * W, s.mean);
-    hipLaunchKernelGGL(ak_thr_kernel, dim3(1), dim3(1024), 0, stream, s.thr, s.mean, s.ncand, topk ? 0.0f : threshold, (topk || threshold > 0.0f) ? 0 : 1, B);
-    const AkIsCand is_cand{H, W, AL_R + 1, AL_R, s.thr};  // rows / columns [0, r] and [h - r, h) are zeroed
-    auto count = [&]() {
-        hipLaunchKernelGGL(cand_count_kernel<AkIsCand>, dim3(nchunk, B), dim3(256), 0, stream, s.nms, H * W, is_cand, s.blkcnt, nchunk);
-        hipLaunchKernelGGL(exclusive_scan_kernel<int>, dim3(B), dim3(1024), 0, stream, s.blkcnt, s.blkoff, s.ncand, (const int*)nullptr, nchunk, (long)nchunk);
-    };
-    count();
-    if (!topk && threshold > 0.0f) {  // no candidate above the threshold: the mean of the score map takes its place (per image)
-        hipLaunchKernelGGL(ak_thr_kernel, dim3(1), dim3(1024), 0, stream, s.thr, s.mean, s.ncand, 0.0f, 2, B);
-        count();
-    }
-    hipLaunchKernelGGL((cand_compact_kernel<AkIsCand, EmitScoreIndex>), dim3(nchunk, B), dim3(256), 0, stream, s.nms, H * W, is_cand, s.blkoff, nchunk, ccap,
-                       EmitScoreIndex{s.cscore, s.cidx, ccap});
+    // (the band: rows / columns [0, r] and [h - r, h) are zeroed)
+    const AkDkdWs cw{s.mean, s.thr, s.blkcnt, s.blkoff, s.ncand, s.cscore, s.cidx};
+    const int rc2 = ak_dkd_candidates(h, smap, s.nms, H, W, B, AL_R + 1, AL_R, threshold, topk, cw, st, stream);
+    if (rc2 != IMCUI_OK) return rc2;
     hipLaunchKernelGGL(al_cut_kernel, dim3(B), dim3(1024), 0, stream, s.cscore, s.cidx, ccap, s.ncand, limit, topk ? 1 : 0, s.kscore, s.kidx, s.nkept, s.sorted);
     hipLaunchKernelGGL(al_emit_kernel, dim3(cdiv(limit, 256), B), dim3(256), 0, stream, s.kscore, s.kidx, ccap, s.nkept, s.sorted, kcap, smap, H, W,
                        sub_pixel ? 1 : 0, keypoints, s.knorm, scores, num_keypoints, st);

@@ -23,10 +23,9 @@
 #include <string>
 #include <vector>
 
-#include "gemm.h"
-#include "imcui_hip.h"
-#include "select.h"
 #include "ak_shared.h"
+#include "imcui_hip.h"
+#include "netpack.h"
 
 #define AK_M 16          // SDDH sample positions
 #define AK_KB0 8         // key-points per workgroup step of ak_sddh_offsets_kernel
@@ -34,16 +33,9 @@
 #define AK_NLIMIT 20000  // upstream's n_limit_max
 
 // ------------------------------------------------------------------ tensor table (upstream state-dict order)
-struct AkTensor {
-    std::string name;
-    size_t n;
-};
-static void ak_bn(std::vector<AkTensor>& t, const std::string& p, int c) {
-    for (const char* s : {"weight", "bias", "running_mean", "running_var"}) t.push_back({p + "." + s, (size_t)c});
-}
-static const std::vector<AkTensor>& ak_tensors() {
-    static const std::vector<AkTensor> table = [] {
-        std::vector<AkTensor> t;
+static const TensorTable& ak_tensors() {
+    static const TensorTable table = [] {
+        TensorTable t;
         const int ch[5] = {3, 16, 32, 64, 128};
         for (int b = 1; b <= 4; ++b) {
             const int cin = ch[b - 1], cout = ch[b];
@@ -52,43 +44,33 @@ static const std::vector<AkTensor>& ak_tensors() {
                 const int ci = j == 1 ? cin : cout;
                 const std::string c = p + ".conv" + std::to_string(j);
                 if (b >= 3) {
-                    t.push_back({c + ".offset_conv.weight", (size_t)18 * ci * 9});
-                    t.push_back({c + ".offset_conv.bias", 18});
-                    t.push_back({c + ".regular_conv.weight", (size_t)cout * ci * 9});
+                    t.add(c + ".offset_conv.weight", (size_t)18 * ci * 9);
+                    t.add(c + ".offset_conv.bias", 18);
+                    t.add(c + ".regular_conv.weight", (size_t)cout * ci * 9);
                 } else {
-                    t.push_back({c + ".weight", (size_t)cout * ci * 9});
+                    t.add(c + ".weight", (size_t)cout * ci * 9);
                 }
-                ak_bn(t, p + ".bn" + std::to_string(j), cout);
+                for (const char* s : {"weight", "bias", "running_mean", "running_var"}) t.add(p + ".bn" + std::to_string(j) + "." + s, cout);
             }
-            if (b >= 2) t.push_back({p + ".downsample.weight", (size_t)cout * cin});
+            if (b >= 2) t.add(p + ".downsample.weight", (size_t)cout * cin);
         }
-        for (int i = 1; i <= 4; ++i) t.push_back({"conv" + std::to_string(i) + ".weight", (size_t)32 * ch[i]});
-        t.push_back({"score_head.0.weight", 8 * 128});
-        t.push_back({"score_head.2.weight", 4 * 8 * 9});
-        t.push_back({"score_head.4.weight", 4 * 4 * 9});
-        t.push_back({"score_head.6.weight", 1 * 4 * 9});
-        t.push_back({"desc_head.agg_weights", (size_t)AK_M * 128 * 128});  // (a parameter of the head itself: before its sub-modules)
-        t.push_back({"desc_head.offset_conv.0.weight", (size_t)32 * 128 * 9});
-        t.push_back({"desc_head.offset_conv.0.bias", 32});
-        t.push_back({"desc_head.offset_conv.2.weight", 32 * 32});
-        t.push_back({"desc_head.offset_conv.2.bias", 32});
-        t.push_back({"desc_head.sf_conv.weight", 128 * 128});
+        for (int i = 1; i <= 4; ++i) t.add("conv" + std::to_string(i) + ".weight", (size_t)32 * ch[i]);
+        t.add("score_head.0.weight", 8 * 128);
+        t.add("score_head.2.weight", 4 * 8 * 9);
+        t.add("score_head.4.weight", 4 * 4 * 9);
+        t.add("score_head.6.weight", 1 * 4 * 9);
+        t.add("desc_head.agg_weights", (size_t)AK_M * 128 * 128);  // (a parameter of the head itself: before its sub-modules)
+        t.add("desc_head.offset_conv.0.weight", (size_t)32 * 128 * 9);
+        t.add("desc_head.offset_conv.0.bias", 32);
+        t.add("desc_head.offset_conv.2.weight", 32 * 32);
+        t.add("desc_head.offset_conv.2.bias", 32);
+        t.add("desc_head.sf_conv.weight", 128 * 128);
         return t;
     }();
     return table;
 }
-static int ak_find(const char* name) {
-    const auto& t = ak_tensors();
-    for (size_t i = 0; i < t.size(); ++i)
-        if (t[i].name == name) return (int)i;
-    return -1;
-}
-
-extern "C" int imcui_hip_aliked_num_tensors(void) { return (int)ak_tensors().size(); }
-extern "C" const char* imcui_hip_aliked_tensor_name(int i) {
-    const auto& t = ak_tensors();
-    return (i < 0 || i >= (int)t.size()) ? nullptr : t[i].name.c_str();
-}
+extern "C" int imcui_hip_aliked_num_tensors(void) { return ak_tensors().size(); }
+extern "C" const char* imcui_hip_aliked_tensor_name(int i) { return ak_tensors().name(i); }
 
 // ------------------------------------------------------------------ packed weight layout
 // VALU 3x3 layers: w [tap][cin][cout], bias [cout].  0 / 1: block 1; 2..5: the offset convolutions of block3.conv1 / conv2,
@@ -108,7 +90,7 @@ static const int AK_PCOUT[AK_NP] = {32, 64, 128, 32, 32, 32, 32, 8, 8, 8, 8, 32}
 
 struct AkLayout {
     size_t vw[AK_NV], vb[AK_NV];
-    size_t gw[AK_NG], gb[AK_NG], gh[AK_NG], gl[AK_NG], gs[AK_NG];
+    GemmLayerOff g[AK_NG];
     size_t pw[AK_NP], pb;
     // descriptor head, f32, K-major: dh0t [9 taps x 128][32] + dh0b [32] (offset_conv.0), sft [128 k][128 n] (sf_conv), agg [16][128 c][128 d]
     size_t dh0t, dh0b, sft, agg;
@@ -116,46 +98,22 @@ struct AkLayout {
 };
 static AkLayout ak_layout() {
     AkLayout l;
-    size_t off = 0;
-    auto get = [&](size_t n) {
-        const size_t o = off;
-        off += align_up(n, 64);
-        return o;
-    };
+    PackCursor c;
     for (int i = 0; i < AK_NV; ++i) {  // (block1.conv1 first: offset 0 of the packed buffer, see imcui_hip.h)
-        l.vw[i] = get((size_t)9 * AK_VCIN[i] * AK_VCOUT[i]);
-        l.vb[i] = get(AK_VCOUT[i]);
+        l.vw[i] = c.get((size_t)9 * AK_VCIN[i] * AK_VCOUT[i]);
+        l.vb[i] = c.get(AK_VCOUT[i]);
     }
-    for (int i = 0; i < AK_NG; ++i) {
-        const size_t np = align_up(AK_GN[i], 32);
-        l.gw[i] = get((size_t)AK_GN[i] * AK_GK[i]);
-        l.gb[i] = get(AK_GN[i]);
-        l.gh[i] = get(np * AK_GK[i] / 2);
-        l.gl[i] = get(np * AK_GK[i] / 2);
-        l.gs[i] = get(1);
-    }
-    for (int i = 0; i < AK_NP; ++i) l.pw[i] = get((size_t)AK_PCIN[i] * AK_PCOUT[i]);
-    l.pb = get(32);
-    l.dh0t = get((size_t)1152 * 32);
-    l.dh0b = get(32);
-    l.sft = get((size_t)128 * 128);
-    l.agg = get((size_t)AK_M * 128 * 128);
-    l.total = off;
+    for (int i = 0; i < AK_NG; ++i) l.g[i].place(c, AK_GN[i], AK_GK[i]);
+    for (int i = 0; i < AK_NP; ++i) l.pw[i] = c.get((size_t)AK_PCIN[i] * AK_PCOUT[i]);
+    l.pb = c.get(32);
+    l.dh0t = c.get((size_t)1152 * 32);
+    l.dh0b = c.get(32);
+    l.sft = c.get((size_t)128 * 128);
+    l.agg = c.get((size_t)AK_M * 128 * 128);
+    l.total = c.off;
     return l;
 }
 extern "C" size_t imcui_hip_aliked_packed_floats(void) { return ak_layout().total; }
-
-// BatchNorm2d (eval, eps 1e-5) folded into the convolution before it: w' = w * g / sqrt(var + eps), b' = beta - mean * g / sqrt(var + eps)
-static void ak_fold(const float* const* t, const char* bn, int cout, std::vector<float>& scale, std::vector<float>& shift) {
-    const int i = ak_find((std::string(bn) + ".weight").c_str());
-    scale.assign(cout, 1.0f);
-    shift.assign(cout, 0.0f);
-    for (int c = 0; c < cout; ++c) {
-        const float s = t[i][c] / sqrtf(t[i + 3][c] + 1e-5f);
-        scale[c] = s;
-        shift[c] = t[i + 1][c] - t[i + 2][c] * s;
-    }
-}
 
 // t: host pointers of the tensors in imcui_hip_aliked_tensor_name order (shapes checked by the caller)
 extern "C" int imcui_hip_aliked_pack_weights(const float* const* t, float* packed) {
@@ -165,8 +123,10 @@ extern "C" int imcui_hip_aliked_pack_weights(const float* const* t, float* packe
         if (!t[i]) return IMCUI_ERR_ARG;
     const AkLayout l = ak_layout();
     memset(packed, 0, l.total * sizeof(float));
-    auto T = [&](const char* name) { return t[ak_find(name)]; };
+    auto T = [&](const char* name) { return t[ak_tensors().find(name)]; };
     std::vector<float> sc, sh, tmp;
+    // (the four tensors of a BatchNorm follow each other in the table)
+    auto fold = [&](const std::string& bn, int cout) { bn_fold_f32(t + ak_tensors().find(bn + ".weight"), cout, sc, sh); };
     // OIHW 3x3 -> [tap][cin][cout] with a per-output scale
     auto pack_valu = [&](int v, const float* w, const float* scale, const float* bias) {
         const int cin = AK_VCIN[v], cout = AK_VCOUT[v];
@@ -176,14 +136,13 @@ extern "C" int imcui_hip_aliked_pack_weights(const float* const* t, float* packe
         if (bias) memcpy(packed + l.vb[v], bias, cout * sizeof(float));
     };
     auto pack_gemm = [&](int g, const float* w_nk, const float* bias) {  // w_nk already [N][K]
-        memcpy(packed + l.gw[g], w_nk, (size_t)AK_GN[g] * AK_GK[g] * sizeof(float));
-        if (bias) memcpy(packed + l.gb[g], bias, AK_GN[g] * sizeof(float));
-        packed[l.gs[g]] = split_weights_frag_host(packed + l.gw[g], AK_GN[g], AK_GK[g], reinterpret_cast<unsigned short*>(packed + l.gh[g]),
-                                                  reinterpret_cast<unsigned short*>(packed + l.gl[g]));
+        memcpy(packed + l.g[g].w, w_nk, (size_t)AK_GN[g] * AK_GK[g] * sizeof(float));
+        if (bias) memcpy(packed + l.g[g].b, bias, AK_GN[g] * sizeof(float));
+        l.g[g].split_planes(packed, AK_GN[g], AK_GK[g]);
     };
     // a 3x3 convolution followed by a folded BatchNorm as a GEMM layer (cin stored as cpad channels)
     auto pack_conv_bn = [&](int g, const float* w, int cout, int cin, int cpad, const char* bn) {
-        ak_fold(t, bn, cout, sc, sh);
+        fold(bn, cout);
         tmp.assign((size_t)cout * 9 * cpad, 0.0f);
         pack_conv_gemm(w, cout, cin, 3, cpad, tmp.data());
         for (int co = 0; co < cout; ++co)
@@ -194,9 +153,9 @@ extern "C" int imcui_hip_aliked_pack_weights(const float* const* t, float* packe
         for (int co = 0; co < AK_PCOUT[p]; ++co)
             for (int ci = 0; ci < AK_PCIN[p]; ++ci) packed[l.pw[p] + (size_t)ci * AK_PCOUT[p] + co] = w[(size_t)co * ldw + col0 + ci];
     };
-    ak_fold(t, "block1.bn1", 16, sc, sh);
+    fold("block1.bn1", 16);
     pack_valu(0, T("block1.conv1.weight"), sc.data(), sh.data());
-    ak_fold(t, "block1.bn2", 16, sc, sh);
+    fold("block1.bn2", 16);
     pack_valu(1, T("block1.conv2.weight"), sc.data(), sh.data());
     pack_conv_bn(0, T("block2.conv1.weight"), 32, 16, 32, "block2.bn1");
     pack_conv_bn(1, T("block2.conv2.weight"), 32, 32, 32, "block2.bn2");
@@ -237,37 +196,6 @@ extern "C" int imcui_hip_aliked_pack_weights(const float* const* t, float* packe
     pack_pw(11, T("desc_head.offset_conv.2.weight"), 32, 0);
     memcpy(packed + l.pb, T("desc_head.offset_conv.2.bias"), 32 * sizeof(float));
     return IMCUI_OK;
-}
-
-// ------------------------------------------------------------------ avg_pool2d(k) of an NHWC map: C channels of [n, k ho, k wo, lds] ->
-// [n, ho, wo, ldd]; channels [C, ldd) are written as zero (the implicit GEMM's channel padding).  Row-major window sum, then / k^2.
-__global__ __launch_bounds__(256) void ak_pool_kernel(const float* __restrict__ src, int lds, int C, float* __restrict__ dst, int ldd, int k, int ho,
-                                                      int wo, long n4) {
-    const int D4 = ldd >> 2;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
-        const int c = (int)(i % D4) * 4;
-        long t = i / D4;
-        const int x = (int)(t % wo);
-        t /= wo;
-        const int y = (int)(t % ho);
-        const long b = t / ho;
-        float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (c < C) {
-            const int wi = k * wo;
-            const float* s = src + ((b * k * ho + (long)k * y) * wi + (long)k * x) * lds + c;
-            for (int dy = 0; dy < k; ++dy)
-                for (int dx = 0; dx < k; ++dx) {
-                    const float4 v = *reinterpret_cast<const float4*>(s + ((long)dy * wi + dx) * lds);
-                    o.x += v.x;
-                    o.y += v.y;
-                    o.z += v.z;
-                    o.w += v.w;
-                }
-            const float d = (float)(k * k);
-            o = make_float4(o.x / d, o.y / d, o.z / d, o.w / d);
-        }
-        *reinterpret_cast<float4*>(dst + i * 4) = o;
-    }
 }
 
 // in-place SELU of a contiguous buffer
@@ -753,40 +681,21 @@ extern "C" int imcui_hip_aliked_forward(imcui_hip_t* h, const float* packed, con
     const float* P = packed;
     const bool split = h->precision == 1;
     int rc;
-#define AKRUN(x)                       \
-    do {                               \
-        rc = (x);                      \
-        if (rc != IMCUI_OK) return rc; \
-    } while (0)
     auto px = [&](int sh) { return (long)(Hp >> sh) * (Wp >> sh); };
-    auto gemm_w = [&](GemmP& g, int L) {
-        g.W = P + l.gw[L];
-        g.ldw = AK_GK[L];
-        if (split) {
-            g.Wh = reinterpret_cast<const unsigned short*>(P + l.gh[L]);
-            g.Wl = reinterpret_cast<const unsigned short*>(P + l.gl[L]);
-            g.wscale = P + l.gs[L];
-        }
-        g.N = AK_GN[L];
-        g.K = AK_GK[L];
-    };
-    // implicit-GEMM 3x3 convolution (pad 1) of the NHWC map `in` [B, Hp >> sh, Wp >> sh, 32] + folded-BatchNorm bias
-    auto conv_gemm = [&](int L, const float* in, int sh, float* out) -> int {
+    // GEMM layer L (+ folded-BatchNorm bias) on the rows of A -> out [M, N]; cin > 0: A is the NHWC map [B, Hp >> sh, Wp >> sh, cin] and
+    // the layer its implicit 3x3 convolution (pad 1), else A holds the gathered rows [M, K]
+    auto gemm = [&](int L, const float* A, int sh, int cin, float* out) -> int {
         GemmP g;
         g.epi = EPI_CONV;
-        g.A = in;
-        gemm_w(g, L);
-        g.bias = P + l.gb[L];
-        g.conv_k = 3;
-        g.conv_stride = 1;
-        g.conv_pad = 1;
-        g.conv_hin = g.conv_hout = Hp >> sh;
-        g.conv_win = g.conv_wout = Wp >> sh;
-        g.conv_cin = 32;
+        g.A = A;
+        gemm_set_weights(g, P, l.g[L], AK_GN[L], AK_GK[L], split);
+        if (cin > 0)
+            gemm_set_conv(g, 3, 1, 1, Hp >> sh, Wp >> sh, Hp >> sh, Wp >> sh, cin);
+        else
+            g.lda = AK_GK[L];
         g.M = (int)(B * px(sh));
         g.C = out;
         g.ldc = AK_GN[L];
-        g.act = 0;
         return gemm_launch(h, g, stream);
     };
     auto selu = [&](float* x, long n) { hipLaunchKernelGGL(ak_selu_kernel, dim3(ak_grid(n / 4)), dim3(256), 0, stream, x, n / 4); };
@@ -797,7 +706,7 @@ extern "C" int imcui_hip_aliked_forward(imcui_hip_t* h, const float* packed, con
     };
     auto pool = [&](const float* src, int C, float* dst, int ldd, int k, int sh_out) {
         const long n4 = (long)B * px(sh_out) * ldd / 4;
-        hipLaunchKernelGGL(ak_pool_kernel, dim3(ak_grid(n4)), dim3(256), 0, stream, src, C, C, dst, ldd, k, Hp >> sh_out, Wp >> sh_out, n4);
+        hipLaunchKernelGGL(ak_pool_kernel<false>, dim3(ak_grid(n4)), dim3(256), 0, stream, src, C, C, dst, ldd, k, Hp >> sh_out, Wp >> sh_out, n4);
     };
     // deformable 3x3 (+ folded BatchNorm bias) of x [B, hl, wl, cin]: offsets (VALU layer V), gather, GEMM layer L -> out [.., N]
     auto deform = [&](int V, int L, const float* x, int cin, int sh, float* offb, float* A, float* out) -> int {
@@ -807,17 +716,7 @@ extern "C" int imcui_hip_aliked_forward(imcui_hip_t* h, const float* packed, con
         const long n4 = (long)B * px(sh) * 9 * cin / 4;
         hipLaunchKernelGGL(ak_deform_kernel, dim3(ak_grid(n4)), dim3(256), 0, stream, x, offb, A, hl, wl, cin, (float)max(hl, wl) / 4.0f, n4);
         IMCUI_CHECK_LAUNCH(h);
-        GemmP g;
-        g.epi = EPI_CONV;
-        g.A = A;
-        g.lda = 9 * cin;
-        gemm_w(g, L);
-        g.bias = P + l.gb[L];
-        g.M = (int)(B * px(sh));
-        g.C = out;
-        g.ldc = AK_GN[L];
-        g.act = 0;
-        return gemm_launch(h, g, stream);
+        return gemm(L, A, sh, 0, out);
     };
     // ---- block 1 (full resolution, VALU)
     {
@@ -829,21 +728,21 @@ extern "C" int imcui_hip_aliked_forward(imcui_hip_t* h, const float* packed, con
     }
     // ---- block 2 (1/2): x2 = SELU(bn2(conv2(SELU(bn1(conv1(p1))))) + downsample(p1))
     pool(s.x1, 16, s.p1, 32, 2, 1);
-    AKRUN(conv_gemm(0, s.p1, 1, s.t2));
+    IMCUI_RUN(gemm(0, s.p1, 1, 32, s.t2));
     selu(s.t2, B * px(1) * 32);
-    AKRUN(conv_gemm(1, s.t2, 1, s.x2));
+    IMCUI_RUN(gemm(1, s.t2, 1, 32, s.x2));
     pw(0, s.p1, 32, s.x2, s.x2, B * px(1), 1);
     // ---- block 3 (1/8, deformable)
     pool(s.x2, 32, s.p2, 32, 4, 3);
-    AKRUN(deform(2, 2, s.p2, 32, 3, s.off3, s.A3, s.t3));
+    IMCUI_RUN(deform(2, 2, s.p2, 32, 3, s.off3, s.A3, s.t3));
     selu(s.t3, B * px(3) * 64);
-    AKRUN(deform(3, 3, s.t3, 64, 3, s.off3, s.A3, s.x3));
+    IMCUI_RUN(deform(3, 3, s.t3, 64, 3, s.off3, s.A3, s.x3));
     pw(1, s.p2, 32, s.x3, s.x3, B * px(3), 1);
     // ---- block 4 (1/32, deformable)
     pool(s.x3, 64, s.p3, 64, 4, 5);
-    AKRUN(deform(4, 4, s.p3, 64, 5, s.off4, s.A4, s.t4));
+    IMCUI_RUN(deform(4, 4, s.p3, 64, 5, s.off4, s.A4, s.t4));
     selu(s.t4, B * px(5) * 128);
-    AKRUN(deform(5, 5, s.t4, 128, 5, s.off4, s.A4, s.x4));
+    IMCUI_RUN(deform(5, 5, s.t4, 128, 5, s.off4, s.A4, s.x4));
     pw(2, s.p3, 64, s.x4, s.x4, B * px(5), 1);
     IMCUI_CHECK_LAUNCH(h);
     if (dbg_x3) hipMemcpyAsync(dbg_x3, s.x3, (size_t)B * px(3) * 64 * sizeof(float), hipMemcpyDeviceToDevice, stream);
@@ -874,26 +773,13 @@ extern "C" int imcui_hip_aliked_forward(imcui_hip_t* h, const float* packed, con
     }
     // ---- DKD
     const int r = nms_radius;
-    AKRUN(imcui_hip_simple_nms(h, smap, s.nms, B, H, W, r, stream));
+    IMCUI_RUN(imcui_hip_simple_nms(h, smap, s.nms, B, H, W, r, stream));
     int* st = status ? status : s.status;
-    hipMemsetAsync(st, 0, sizeof(int), stream);
     const bool topk = !(threshold > 0.0f) && max_keypoints > 0;
     const int limit = max_keypoints > 0 ? max_keypoints : AK_NLIMIT;
-    const int nchunk = cdiv(H * W, SEL_CHUNK), ccap = H * W;
-    hipLaunchKernelGGL(ak_mean_kernel, dim3(B), dim3(1024), 0, stream, smap, H * W, s.mean);
-    hipLaunchKernelGGL(ak_thr_kernel, dim3(1), dim3(1024), 0, stream, s.thr, s.mean, s.ncand, topk ? 0.0f : threshold, (topk || threshold > 0.0f) ? 0 : 1, B);
-    const AkIsCand is_cand{H, W, r, r, s.thr};
-    auto count = [&]() {
-        hipLaunchKernelGGL(cand_count_kernel<AkIsCand>, dim3(nchunk, B), dim3(256), 0, stream, s.nms, H * W, is_cand, s.blkcnt, nchunk);
-        hipLaunchKernelGGL(exclusive_scan_kernel<int>, dim3(B), dim3(1024), 0, stream, s.blkcnt, s.blkoff, s.ncand, (const int*)nullptr, nchunk, (long)nchunk);
-    };
-    count();
-    if (!topk && threshold > 0.0f) {  // no candidate above the threshold: the mean of the score map takes its place (per image)
-        hipLaunchKernelGGL(ak_thr_kernel, dim3(1), dim3(1024), 0, stream, s.thr, s.mean, s.ncand, 0.0f, 2, B);
-        count();
-    }
-    hipLaunchKernelGGL((cand_compact_kernel<AkIsCand, EmitScoreIndex>), dim3(nchunk, B), dim3(256), 0, stream, s.nms, H * W, is_cand, s.blkoff, nchunk, ccap,
-                       EmitScoreIndex{s.cscore, s.cidx, ccap});
+    const int ccap = H * W;
+    const AkDkdWs cw{s.mean, s.thr, s.blkcnt, s.blkoff, s.ncand, s.cscore, s.cidx};
+    IMCUI_RUN(ak_dkd_candidates(h, smap, s.nms, H, W, B, r, r, threshold, topk, cw, st, stream));
     float* kn = keypoints_norm ? keypoints_norm : s.knorm;
     hipLaunchKernelGGL(ak_select_kernel, dim3(B), dim3(1024), 0, stream, s.cscore, s.cidx, ccap, s.ncand, limit, kcap, smap, H, W, r, keypoints, kn, scores,
                        num_keypoints, st);
@@ -906,6 +792,5 @@ extern "C" int imcui_hip_aliked_forward(imcui_hip_t* h, const float* packed, con
     hipLaunchKernelGGL(ak_sddh_desc_kernel, dim3(min(cdiv(kcap, AK_KB1), 1024), B), dim3(256), 0, stream, m, kn, num_keypoints, kcap, P + l.sft,
                        P + l.agg, descriptors);
     IMCUI_CHECK_LAUNCH(h);
-#undef AKRUN
     return IMCUI_OK;
 }

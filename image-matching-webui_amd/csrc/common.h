@@ -228,6 +228,13 @@ int imcui_set_err(imcui_hip_s* h, int code, const char* fmt, ...);
             return imcui_set_err(h, IMCUI_ERR_HIP, "%s:%d: %s", __FILE__, __LINE__, hipGetErrorString(e__)); \
     } while (0)
 
+// return the status of a failed step; the function declares `int rc;` itself
+#define IMCUI_RUN(x)                   \
+    do {                               \
+        rc = (x);                      \
+        if (rc != IMCUI_OK) return rc; \
+    } while (0)
+
 // bump allocator over the caller-provided workspace
 struct WsAlloc {
     char* base;

@@ -19,6 +19,7 @@
 
 #include "gemm.h"
 #include "imcui_hip.h"
+#include "netpack.h"
 #include "select.h"
 
 // ------------------------------------------------------------------ packed weight layout
@@ -33,33 +34,23 @@ static const int DK_COUT[DK_NL] = {32, 64, 64, 64, 64, 64, 64, 128};
 struct DkLayout {
     size_t w0, b0;  // first convolution [16][3][5][5], bias [16]
     size_t slope[DK_NL];
-    size_t w[DK_NL], b[DK_NL], wh[DK_NL], wl[DK_NL], ws[DK_NL];
+    GemmLayerOff g[DK_NL];
     size_t hw, hb;  // heatmap row of the last convolution: [80 channels][25 taps], bias [1]
     size_t total;
 };
 
 static DkLayout dk_layout() {
     DkLayout l;
-    size_t off = 0;
-    auto get = [&](size_t n) {
-        const size_t o = off;
-        off += align_up(n, 64);
-        return o;
-    };
-    l.w0 = get(16 * 3 * 25);
-    l.b0 = get(16);
+    PackCursor c;
+    l.w0 = c.get(16 * 3 * 25);
+    l.b0 = c.get(16);
     for (int i = 0; i < DK_NL; ++i) {
-        const size_t K = (size_t)25 * DK_CPAD[i], np = (size_t)align_up(DK_COUT[i], 32);
-        l.slope[i] = get(DK_CIN[i]);
-        l.w[i] = get((size_t)DK_COUT[i] * K);
-        l.b[i] = get(DK_COUT[i]);
-        l.wh[i] = get(np * K / 2);
-        l.wl[i] = get(np * K / 2);
-        l.ws[i] = get(1);
+        l.slope[i] = c.get(DK_CIN[i]);
+        l.g[i].place(c, DK_COUT[i], 25 * DK_CPAD[i]);
     }
-    l.hw = get(80 * 25);
-    l.hb = get(1);
-    l.total = off;
+    l.hw = c.get(80 * 25);
+    l.hb = c.get(1);
+    l.total = c.off;
     return l;
 }
 
@@ -95,10 +86,9 @@ extern "C" int imcui_hip_disk_pack_weights(const float* const* t, float* packed)
         const float* b = t[4 + 3 * i];
         const int K = 25 * DK_CPAD[i];
         memcpy(packed + l.slope[i], slope, DK_CIN[i] * sizeof(float));
-        pack_conv_gemm(w, DK_COUT[i], DK_CIN[i], 5, DK_CPAD[i], packed + l.w[i]);
-        memcpy(packed + l.b[i], b, DK_COUT[i] * sizeof(float));
-        packed[l.ws[i]] = split_weights_frag_host(packed + l.w[i], DK_COUT[i], K, reinterpret_cast<unsigned short*>(packed + l.wh[i]),
-                                                  reinterpret_cast<unsigned short*>(packed + l.wl[i]));
+        pack_conv_gemm(w, DK_COUT[i], DK_CIN[i], 5, DK_CPAD[i], packed + l.g[i].w);
+        memcpy(packed + l.g[i].b, b, DK_COUT[i] * sizeof(float));
+        l.g[i].split_planes(packed, DK_COUT[i], K);
         if (i == DK_NL - 1) {  // output channel 128: the heatmap
             memcpy(packed + l.hw, w + (size_t)128 * 80 * 25, 80 * 25 * sizeof(float));
             packed[l.hb] = b[128];
@@ -525,11 +515,6 @@ extern "C" int imcui_hip_disk_forward(imcui_hip_t* h, const float* packed, const
     const float* P = packed;
     const bool split = h->precision == 1;
     int rc;
-#define DKRUN(x)                       \
-    do {                               \
-        rc = (x);                      \
-        if (rc != IMCUI_OK) return rc; \
-    } while (0)
     auto px = [&](int lev) { return (long)(Hp >> lev) * (Wp >> lev); };
     // InstanceNorm statistics of the contiguous map x [B, px(lev), C], then X = prelu(norm(x)) with Cpad channels
     auto norm = [&](int L, const float* x, int lev) -> int {
@@ -548,26 +533,11 @@ extern "C" int imcui_hip_disk_forward(imcui_hip_t* h, const float* packed, const
         GemmP g;
         g.epi = EPI_CONV;
         g.A = s.X;
-        g.W = P + l.w[L];
-        g.ldw = 25 * DK_CPAD[L];
-        if (split) {
-            g.Wh = reinterpret_cast<const unsigned short*>(P + l.wh[L]);
-            g.Wl = reinterpret_cast<const unsigned short*>(P + l.wl[L]);
-            g.wscale = P + l.ws[L];
-        }
-        g.bias = P + l.b[L];
-        g.N = DK_COUT[L];
-        g.K = 25 * DK_CPAD[L];
-        g.conv_k = 5;
-        g.conv_stride = 1;
-        g.conv_pad = 2;
-        g.conv_hin = g.conv_hout = Hp >> lev;
-        g.conv_win = g.conv_wout = Wp >> lev;
-        g.conv_cin = DK_CPAD[L];
+        gemm_set_weights(g, P, l.g[L], DK_COUT[L], 25 * DK_CPAD[L], split);
+        gemm_set_conv(g, 5, 1, 2, Hp >> lev, Wp >> lev, Hp >> lev, Wp >> lev, DK_CPAD[L]);
         g.M = (int)(B * px(lev));
         g.C = out;
         g.ldc = ldo;
-        g.act = 0;
         return gemm_launch(h, g, stream);
     };
     auto pool = [&](const float* src, int lds, int soff, int lev_out, int C) {
@@ -586,29 +556,29 @@ extern "C" int imcui_hip_disk_forward(imcui_hip_t* h, const float* packed, const
         IMCUI_CHECK_LAUNCH(h);
     }
     pool(s.cat3, 80, 64, 1, 16);
-    DKRUN(norm(0, s.pool, 1));
-    DKRUN(conv(0, 1, s.cat2 + 64, 96));
+    IMCUI_RUN(norm(0, s.pool, 1));
+    IMCUI_RUN(conv(0, 1, s.cat2 + 64, 96));
     pool(s.cat2, 96, 64, 2, 32);
-    DKRUN(norm(1, s.pool, 2));
-    DKRUN(conv(1, 2, s.cat1 + 64, 128));
+    IMCUI_RUN(norm(1, s.pool, 2));
+    IMCUI_RUN(conv(1, 2, s.cat1 + 64, 128));
     pool(s.cat1, 128, 64, 3, 64);
-    DKRUN(norm(2, s.pool, 3));
-    DKRUN(conv(2, 3, s.cat0 + 64, 128));
+    IMCUI_RUN(norm(2, s.pool, 3));
+    IMCUI_RUN(conv(2, 3, s.cat0 + 64, 128));
     pool(s.cat0, 128, 64, 4, 64);
-    DKRUN(norm(3, s.pool, 4));
-    DKRUN(conv(3, 4, s.f5, 64));
+    IMCUI_RUN(norm(3, s.pool, 4));
+    IMCUI_RUN(conv(3, 4, s.f5, 64));
     // ---- up path: [bilinear x2 of the bottom map | skip]
     up(s.f5, 4, s.cat0, 128);
-    DKRUN(norm(4, s.cat0, 3));
-    DKRUN(conv(4, 3, s.u0, 64));
+    IMCUI_RUN(norm(4, s.cat0, 3));
+    IMCUI_RUN(conv(4, 3, s.u0, 64));
     up(s.u0, 3, s.cat1, 128);
-    DKRUN(norm(5, s.cat1, 2));
-    DKRUN(conv(5, 2, s.u1, 64));
+    IMCUI_RUN(norm(5, s.cat1, 2));
+    IMCUI_RUN(conv(5, 2, s.u1, 64));
     up(s.u1, 2, s.cat2, 96);
-    DKRUN(norm(6, s.cat2, 1));
-    DKRUN(conv(6, 1, s.u2, 64));
+    IMCUI_RUN(norm(6, s.cat2, 1));
+    IMCUI_RUN(conv(6, 1, s.u2, 64));
     up(s.u2, 1, s.cat3, 80);
-    DKRUN(norm(7, s.cat3, 0));
+    IMCUI_RUN(norm(7, s.cat3, 0));
     // ---- heatmap (cropped to H x W), detection
     float* heat = heatmap ? heatmap : s.heat;
     hipLaunchKernelGGL(dk_heat_kernel, dim3(cdiv(W, DK_HT), cdiv(H, DK_HT), B), dim3(256), 0, stream, s.X, P + l.hw, P + l.hb, heat, H, W, Hp, Wp);
@@ -635,27 +605,17 @@ extern "C" int imcui_hip_disk_forward(imcui_hip_t* h, const float* packed, const
         g.A = s.gA;
         g.lda = 25 * 96;
         g.a_bs = (long)DK_DESC_ROWS * 25 * 96;
-        g.W = P + l.w[L];
-        g.ldw = 25 * 96;
-        if (split) {
-            g.Wh = reinterpret_cast<const unsigned short*>(P + l.wh[L]);
-            g.Wl = reinterpret_cast<const unsigned short*>(P + l.wl[L]);
-            g.wscale = P + l.ws[L];
-        }
-        g.bias = P + l.b[L];
+        gemm_set_weights(g, P, l.g[L], 128, 25 * 96, split);
         g.C = descriptors + (size_t)r0 * 128;
         g.ldc = 128;
         g.c_bs = (long)kcap * 128;
         g.M = DK_DESC_ROWS;
-        g.N = 128;
-        g.K = 25 * 96;
         g.batch = B;
         g.mcnt = s.rows;
         g.cnt_stride = 1;
-        DKRUN(gemm_launch(h, g, stream));
+        IMCUI_RUN(gemm_launch(h, g, stream));
     }
     hipLaunchKernelGGL(dk_l2norm_kernel, dim3(cdiv(kcap, 4), B), dim3(256), 0, stream, descriptors, num_keypoints, kcap);
     IMCUI_CHECK_LAUNCH(h);
-#undef DKRUN
     return IMCUI_OK;
 }

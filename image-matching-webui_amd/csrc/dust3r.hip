@@ -414,11 +414,6 @@ static int du_forward_impl(imcui_hip_t* h, const DuCfg& c, const float* packed, 
     const int H = geo.H[0], W = geo.W[0], hg = H / 16, wg = W / 16, T = hg * wg;  // THE grid of a one-size call (mixed: class 0 only)
     const dim3 blk(256);
     int rc;
-#define DURUN(x)                       \
-    do {                               \
-        rc = (x);                      \
-        if (rc != IMCUI_OK) return rc; \
-    } while (0)
     auto blocks = [](long n) { return dim3((unsigned)(n < 256 ? 1 : (n + 255) / 256 > 65536 * 16 ? 65536 * 16 : (n + 255) / 256)); };
     size_t dump_off = 0;
     bool dump_ok = true;
@@ -761,27 +756,27 @@ static int du_forward_impl(imcui_hip_t* h, const DuCfg& c, const float* packed, 
             }
         }
         IMCUI_CHECK_LAUNCH(h);
-        DURUN(lin(0, w.A0, w.x, NI, nullptr, 0));
+        IMCUI_RUN(lin(0, w.A0, w.x, NI, nullptr, 0));
         dump_copy(w.x, (size_t)me * E);
     }
     for (int i = 0; i < c.enc_depth; ++i) {
         const float* xin = ln_input(w.x, me, E);  // norm1 (affine part inside attn.qkv)
         bool fused;
-        DURUN(proj_planes(du_l_enc(c, i, 0), -1, false, xin, E, NI, 0, 3, w.qp, w.kp, w.vp, &fused));
+        IMCUI_RUN(proj_planes(du_l_enc(c, i, 0), -1, false, xin, E, NI, 0, 3, w.qp, w.kp, w.vp, &fused));
         if (!fused) {
-            DURUN(lin(du_l_enc(c, i, 0), xin, w.qkv, NI, nullptr, 0));
+            IMCUI_RUN(lin(du_l_enc(c, i, 0), xin, w.qkv, NI, nullptr, 0));
             rope_split(w.qkv, 3 * E, 0, E, NI, w.qp, NI, 0, q_alpha);
             rope_split(w.qkv, 3 * E, E, E, NI, w.kp, NI, 0, 1.0f);
             vt_split(w.qkv, 3 * E, 2 * E, E, NI, w.vp, NI, 0);
         }
         cur_ln = nullptr;
         IMCUI_CHECK_LAUNCH(h);
-        DURUN(attend(w.qp, w.kp, w.vp, w.att, NI, E, 0));
-        DURUN(lin(du_l_enc(c, i, 1), w.att, w.x, NI, w.x, 0));
+        IMCUI_RUN(attend(w.qp, w.kp, w.vp, w.att, NI, E, 0));
+        IMCUI_RUN(lin(du_l_enc(c, i, 1), w.att, w.x, NI, w.x, 0));
         xin = ln_input(w.x, me, E);  // norm2 (inside mlp.fc1)
-        DURUN(lin(du_l_enc(c, i, 2), xin, w.hid, NI, nullptr, 3));
+        IMCUI_RUN(lin(du_l_enc(c, i, 2), xin, w.hid, NI, nullptr, 3));
         cur_ln = nullptr;
-        DURUN(lin(du_l_enc(c, i, 3), w.hid, w.x, NI, w.x, 0));
+        IMCUI_RUN(lin(du_l_enc(c, i, 3), w.hid, w.x, NI, w.x, 0));
         dump_copy(w.x, (size_t)me * E);
     }
     layernorm(w.x, du_v_encn(c), w.fenc, me, E);
@@ -789,7 +784,7 @@ static int du_forward_impl(imcui_hip_t* h, const DuCfg& c, const float* packed, 
 
     // ---- decoder
     const long md = (long)2 * P * R, ms = (long)P * R;  // rows of all streams / of one side
-    DURUN(lin(du_l_demb(c), w.fenc, w.g, NI, nullptr, 0));
+    IMCUI_RUN(lin(du_l_demb(c), w.fenc, w.g, NI, nullptr, 0));
     cur_cnt = cnt_dec;
     cur_row0 = row0_dec;
     cur_T = T_dec;
@@ -822,40 +817,40 @@ static int du_forward_impl(imcui_hip_t* h, const DuCfg& c, const float* packed, 
         // of the block's input, for both sides at once
         const float* yin = ln_input(w.y, md, D);
         bool fused;
-        DURUN(proj_planes(du_l_dec(c, 0, i, 3), merged ? du_l_dec(c, 1, i, 3) : -2, true, yin, D, 2 * P, 1, 2, nullptr, w.kc, w.vc, &fused));
+        IMCUI_RUN(proj_planes(du_l_dec(c, 0, i, 3), merged ? du_l_dec(c, 1, i, 3) : -2, true, yin, D, 2 * P, 1, 2, nullptr, w.kc, w.vc, &fused));
         if (!fused) {
-            DURUN(lin2(i, 3, yin, D, w.qkv, 2 * D, nullptr, 0, true));
+            IMCUI_RUN(lin2(i, 3, yin, D, w.qkv, 2 * D, nullptr, 0, true));
             rope_split(w.qkv, 2 * D, 0, D, 2 * P, w.kc, 2 * P, 0, 1.0f);
             vt_split(w.qkv, 2 * D, D, D, 2 * P, w.vc, 2 * P, 0);
         }
         // self attention (w.xn still holds the normalised input of the block)
-        DURUN(proj_planes(du_l_dec(c, 0, i, 0), merged ? du_l_dec(c, 1, i, 0) : -2, false, yin, D, 2 * P, 0, 3, w.qp, w.kp, w.vp, &fused));
+        IMCUI_RUN(proj_planes(du_l_dec(c, 0, i, 0), merged ? du_l_dec(c, 1, i, 0) : -2, false, yin, D, 2 * P, 0, 3, w.qp, w.kp, w.vp, &fused));
         if (!fused) {
-            DURUN(lin2(i, 0, yin, D, w.qkv, 3 * D, nullptr, 0, false));
+            IMCUI_RUN(lin2(i, 0, yin, D, w.qkv, 3 * D, nullptr, 0, false));
             rope_split(w.qkv, 3 * D, 0, D, 2 * P, w.qp, 2 * P, 0, q_alpha);
             rope_split(w.qkv, 3 * D, D, D, 2 * P, w.kp, 2 * P, 0, 1.0f);
             vt_split(w.qkv, 3 * D, 2 * D, D, 2 * P, w.vp, 2 * P, 0);
         }
         cur_ln = nullptr;
         IMCUI_CHECK_LAUNCH(h);
-        DURUN(attend(w.qp, w.kp, w.vp, w.att, 2 * P, D, 0));
-        DURUN(lin2(i, 1, w.att, D, w.y, D, w.y, 0, false));
+        IMCUI_RUN(attend(w.qp, w.kp, w.vp, w.att, 2 * P, D, 0));
+        IMCUI_RUN(lin2(i, 1, w.att, D, w.y, D, w.y, 0, false));
         // cross attention
         yin = ln_input(w.y, md, D);  // norm2 (inside cross_attn.projq)
-        DURUN(proj_planes(du_l_dec(c, 0, i, 2), merged ? du_l_dec(c, 1, i, 2) : -2, false, yin, D, 2 * P, 0, 1, w.qp, nullptr, nullptr, &fused));
+        IMCUI_RUN(proj_planes(du_l_dec(c, 0, i, 2), merged ? du_l_dec(c, 1, i, 2) : -2, false, yin, D, 2 * P, 0, 1, w.qp, nullptr, nullptr, &fused));
         if (!fused) {
-            DURUN(lin2(i, 2, yin, D, w.qc, D, nullptr, 0, false));
+            IMCUI_RUN(lin2(i, 2, yin, D, w.qc, D, nullptr, 0, false));
             rope_split(w.qc, D, 0, D, 2 * P, w.qp, 2 * P, 0, q_alpha);
         }
         cur_ln = nullptr;
         IMCUI_CHECK_LAUNCH(h);
-        DURUN(attend(w.qp, w.kc, w.vc, w.att, 2 * P, D, 2));
-        DURUN(lin2(i, 4, w.att, D, w.y, D, w.y, 0, false));
+        IMCUI_RUN(attend(w.qp, w.kc, w.vc, w.att, 2 * P, D, 2));
+        IMCUI_RUN(lin2(i, 4, w.att, D, w.y, D, w.y, 0, false));
         // MLP
         yin = ln_input(w.y, md, D);  // norm3 (inside mlp.fc1)
-        DURUN(lin2(i, 5, yin, D, w.hid, 4 * D, nullptr, 3, false));
+        IMCUI_RUN(lin2(i, 5, yin, D, w.hid, 4 * D, nullptr, 3, false));
         cur_ln = nullptr;
-        DURUN(lin2(i, 6, w.hid, 4 * D, w.y, D, w.y, 0, false));
+        IMCUI_RUN(lin2(i, 6, w.hid, 4 * D, w.y, D, w.y, 0, false));
         dump_copy(w.y, (size_t)md * D);
         for (int k = 0; k < 2; ++k)
             if (i + 1 == hooks[k]) save_hook(w.y, k);
@@ -889,17 +884,17 @@ static int du_forward_impl(imcui_hip_t* h, const DuCfg& c, const float* packed, 
         // reassemble: 1/4, 1/8, 1/16, 1/32 (an odd token grid rounds the 1/32 level up: 3x3 stride 2 with padding 1; the x2 of the first
         // fusion block is then cropped back to the token grid, upstream's `[:, :, :layers[2].shape[2], :layers[2].shape[3]]`)
         const int h3 = (hg + 1) / 2, w3 = (wg + 1) / 2;
-        DURUN(lin_dense(L0 + 0, tok0, w.ta, pt));
-        DURUN(lin_dense(L0 + 1, w.ta, w.tb, pt));
+        IMCUI_RUN(lin_dense(L0 + 0, tok0, w.ta, pt));
+        IMCUI_RUN(lin_dense(L0 + 1, w.ta, w.tb, pt));
         shuffle(w.tb, w.tm, 4, 96);
-        DURUN(conv3(L0 + 7, w.tm, w.rn[0], 4 * hg, 4 * wg, 0, nullptr));
-        DURUN(lin_dense(L0 + 2, hk[0], w.ta, pt));
-        DURUN(lin_dense(L0 + 3, w.ta, w.tb, pt));
+        IMCUI_RUN(conv3(L0 + 7, w.tm, w.rn[0], 4 * hg, 4 * wg, 0, nullptr));
+        IMCUI_RUN(lin_dense(L0 + 2, hk[0], w.ta, pt));
+        IMCUI_RUN(lin_dense(L0 + 3, w.ta, w.tb, pt));
         shuffle(w.tb, w.tm, 2, 192);
-        DURUN(conv3(L0 + 8, w.tm, w.rn[1], 2 * hg, 2 * wg, 0, nullptr));
-        DURUN(lin_dense(L0 + 4, hk[1], w.ta, pt));
-        DURUN(conv3(L0 + 9, w.ta, w.rn[2], hg, wg, 0, nullptr));
-        DURUN(lin_dense(L0 + 5, hk[2], w.ta, pt));
+        IMCUI_RUN(conv3(L0 + 8, w.tm, w.rn[1], 2 * hg, 2 * wg, 0, nullptr));
+        IMCUI_RUN(lin_dense(L0 + 4, hk[1], w.ta, pt));
+        IMCUI_RUN(conv3(L0 + 9, w.ta, w.rn[2], hg, wg, 0, nullptr));
+        IMCUI_RUN(lin_dense(L0 + 5, hk[2], w.ta, pt));
         {
             int N, K, kind;
             du_shape(c, L0 + 6, &N, &K, &kind);
@@ -925,9 +920,9 @@ static int du_forward_impl(imcui_hip_t* h, const DuCfg& c, const float* packed, 
             g.C = w.tm;
             g.ldc = N;
             g.single = single;
-            DURUN(gemm_launch(h, g, stream));
+            IMCUI_RUN(gemm_launch(h, g, stream));
         }
-        DURUN(conv3(L0 + 10, w.tm, w.rn[3], h3, w3, 0, nullptr));
+        IMCUI_RUN(conv3(L0 + 10, w.tm, w.rn[3], h3, w3, 0, nullptr));
         const int rh[4] = {4 * hg, 2 * hg, hg, h3}, rw[4] = {4 * wg, 2 * wg, wg, w3};
         if (!mixed)
             for (int k = 0; k < 4; ++k) dump_copy(w.rn[k], (size_t)Pn * rh[k] * rw[k] * 256);
@@ -950,25 +945,25 @@ static int du_forward_impl(imcui_hip_t* h, const DuCfg& c, const float* packed, 
                     xres = w.rn[3];
                 } else {
                     hipLaunchKernelGGL(du_relu_kernel, blocks(n4), blk, 0, stream, w.rn[lv], w.s0, n4);
-                    DURUN(conv3(Lq + 0, w.s0, w.s1, hh, ww, 1, nullptr));
-                    DURUN(conv3(Lq + 1, w.s1, w.s0, hh, ww, 0, w.rn[lv]));
+                    IMCUI_RUN(conv3(Lq + 0, w.s0, w.s1, hh, ww, 1, nullptr));
+                    IMCUI_RUN(conv3(Lq + 1, w.s1, w.s0, hh, ww, 0, w.rn[lv]));
                     hipLaunchKernelGGL(du_add_relu_kernel, blocks(n4), blk, 0, stream, path, w.s0, w.s2, w.s1, n4);
                     xres = w.s2;
                 }
-                DURUN(conv3(Lq + 2, w.s1, w.s0, hh, ww, 1, nullptr));
-                DURUN(conv3(Lq + 3, w.s0, w.s1, hh, ww, 0, xres));
+                IMCUI_RUN(conv3(Lq + 2, w.s1, w.s0, hh, ww, 1, nullptr));
+                IMCUI_RUN(conv3(Lq + 3, w.s0, w.s1, hh, ww, 0, xres));
                 hipLaunchKernelGGL(du_upsample2_kernel, blocks(4 * n4), blk, 0, stream, w.s1, w.s3, hh, ww, 64, 4 * n4);
-                DURUN(lin_dense(Lq + 4, w.s3, out, (long)Pn * 4 * hh * ww));
+                IMCUI_RUN(lin_dense(Lq + 4, w.s3, out, (long)Pn * 4 * hh * ww));
             } else {
                 const float* x2 = w.rn[3];  // input of the second unit: rn[3] itself (refinenet4 has no skip), else path + RCU1(skip)
                 if (q > 0) {
-                    DURUN(conv3(Lq + 0, w.rn[lv], w.s1, hh, ww, 1 + 4, nullptr));
-                    DURUN(conv3(Lq + 1, w.s1, w.s2, hh, ww, 0, w.rn[lv], path));
+                    IMCUI_RUN(conv3(Lq + 0, w.rn[lv], w.s1, hh, ww, 1 + 4, nullptr));
+                    IMCUI_RUN(conv3(Lq + 1, w.s1, w.s2, hh, ww, 0, w.rn[lv], path));
                     x2 = w.s2;
                 }
-                DURUN(conv3(Lq + 2, x2, w.s0, hh, ww, 1 + 4, nullptr));
-                DURUN(conv3(Lq + 3, w.s0, w.s1, hh, ww, 0, x2));
-                DURUN(lin_dense(Lq + 4, w.s1, w.s3, (long)Pn * hh * ww));
+                IMCUI_RUN(conv3(Lq + 2, x2, w.s0, hh, ww, 1 + 4, nullptr));
+                IMCUI_RUN(conv3(Lq + 3, w.s0, w.s1, hh, ww, 0, x2));
+                IMCUI_RUN(lin_dense(Lq + 4, w.s1, w.s3, (long)Pn * hh * ww));
                 hipLaunchKernelGGL(du_upsample2_kernel, blocks(4 * n4), blk, 0, stream, w.s3, out, hh, ww, 64, 4 * n4);
             }
             path = out;
@@ -983,7 +978,7 @@ static int du_forward_impl(imcui_hip_t* h, const DuCfg& c, const float* packed, 
             if (!mixed) dump_copy(path, (size_t)Pn * ph * pw * 256);
         }
         // head: 3x3 256 -> 128 at 1/2, x2, 3x3 128 -> 128 + ReLU, 1x1 128 -> 4 + post-processing
-        DURUN(conv3(L0 + 31, path, w.hd0, Hh / 2, Wh / 2, 0, nullptr));
+        IMCUI_RUN(conv3(L0 + 31, path, w.hd0, Hh / 2, Wh / 2, 0, nullptr));
         {
             const long n4 = (long)Pn * Hh * Wh * 32;
             hipLaunchKernelGGL(du_upsample2_kernel, blocks(n4), blk, 0, stream, w.hd0, w.hd1, Hh / 2, Wh / 2, 32, n4);
@@ -1002,16 +997,16 @@ static int du_forward_impl(imcui_hip_t* h, const DuCfg& c, const float* packed, 
             hd.raw = dump_take((size_t)npix * 4);
             int N, K, kind;
             du_shape(c, L0 + 32, &N, &K, &kind);
-            DURUN(conv3x3_split_launch(h, w.hd1, reinterpret_cast<const unsigned short*>(Pk + l.wh[L0 + 32]), reinterpret_cast<const unsigned short*>(Pk + l.wl[L0 + 32]),
+            IMCUI_RUN(conv3x3_split_launch(h, w.hd1, reinterpret_cast<const unsigned short*>(Pk + l.wh[L0 + 32]), reinterpret_cast<const unsigned short*>(Pk + l.wl[L0 + 32]),
                                        Pk + l.ws[L0 + 32], Pk + l.b[L0 + 32], feat, Pn, Hh, Wh, K / 9, N, 1, 0, stream, nullptr, 0, 0, single, nullptr, &hd));
         } else if (!mixed) {
-            DURUN(conv3(L0 + 32, w.hd1, w.hd2, Hh, Wh, 1, nullptr));
+            IMCUI_RUN(conv3(L0 + 32, w.hd1, w.hd2, Hh, Wh, 1, nullptr));
             dump_copy(w.hd2, (size_t)npix * 128);
             float* raw = dump_take((size_t)npix * 4);
             hipLaunchKernelGGL(du_regress_kernel, blocks(npix * 32), blk, 0, stream, w.hd2, V(du_v_head(c, v)), V(du_v_head(c, v) + 1),
                                pts3d + (size_t)v * npix * 3, conf + (size_t)v * npix, raw, npix);
         } else {
-            DURUN(conv3(L0 + 32, w.hd1, w.hd2, Hh, Wh, 1, nullptr));
+            IMCUI_RUN(conv3(L0 + 32, w.hd1, w.hd2, Hh, Wh, 1, nullptr));
             for (int j = 0; j < Pn; ++j) {
                 const size_t o = geo.map_pix[streams[j]];
                 hipLaunchKernelGGL(du_regress_kernel, blocks(mpix * 32), blk, 0, stream, w.hd2 + (size_t)j * mpix * 128, V(du_v_head(c, v)),
@@ -1043,8 +1038,8 @@ static int du_forward_impl(imcui_hip_t* h, const DuCfg& c, const float* packed, 
             g.act = 3;
             g.single = single;
             g.M = (int)pt;
-            DURUN(gemm_launch(h, g, stream));
-            DURUN(lin_dense(L0 + 34, w.lfh, w.lfo, pt));
+            IMCUI_RUN(gemm_launch(h, g, stream));
+            IMCUI_RUN(lin_dense(L0 + 34, w.lfh, w.lfo, pt));
             if (!mixed) {
                 hipLaunchKernelGGL(du_desc_kernel, blocks(npix), blk, 0, stream, w.lfo, desc + (size_t)v * npix * c.desc, desc_conf + (size_t)v * npix, Hh,
                                    Wh, c.desc, npix);
@@ -1060,13 +1055,12 @@ static int du_forward_impl(imcui_hip_t* h, const DuCfg& c, const float* packed, 
         return IMCUI_OK;
     };
     if (!mixed) {
-        for (int v = 0; v < 2; ++v) DURUN(run_head(v, P, H, W, (size_t)v * P * T, nullptr));
+        for (int v = 0; v < 2; ++v) IMCUI_RUN(run_head(v, P, H, W, (size_t)v * P * T, nullptr));
     } else {
-        for (const Group& gr : groups) DURUN(run_head(gr.v, gr.n, geo.H[gr.k], geo.W[gr.k], gr.row0, hmap_host.data() + gr.first));
+        for (const Group& gr : groups) IMCUI_RUN(run_head(gr.v, gr.n, geo.H[gr.k], geo.W[gr.k], gr.row0, hmap_host.data() + gr.first));
     }
     if (!dump_ok) return imcui_set_err(h, IMCUI_ERR_ARG, "dust3r: dump buffer too small (%zu floats)", dump_floats);
     return IMCUI_OK;
-#undef DURUN
 }
 
 // ------------------------------------------------------------------ forward

@@ -290,11 +290,6 @@ extern "C" int imcui_hip_eloftr_forward_ex(imcui_hip_t* h, const float* packed, 
     const int cap = B * L;
     const dim3 blk(256);
     int rc;
-#define ELRUN(x)                       \
-    do {                               \
-        rc = (x);                      \
-        if (rc != IMCUI_OK) return rc; \
-    } while (0)
 
     auto wts = [&](GemmP& g, int li) {
         int N, K;
@@ -376,17 +371,17 @@ extern "C" int imcui_hip_eloftr_forward_ex(imcui_hip_t* h, const float* packed, 
         }
         IMCUI_CHECK_LAUNCH(h);
         // stage 1 (1/2, 64): 2 blocks; stage 2 (1/4, 128): 4; stage 3 (1/8, 256): 14
-        ELRUN(conv(EL_BB0 + 0, w.s0, w.s1a, 2, 64, 3, 1, nullptr, 1));
-        ELRUN(conv(EL_BB0 + 1, w.s1a, w.x1, 2, 64, 3, 1, nullptr, 1));
-        ELRUN(conv(EL_BB0 + 2, w.x1, w.s2a, 2, 64, 3, 2, nullptr, 1));
-        ELRUN(conv(EL_BB0 + 3, w.s2a, w.s2b, 4, 128, 3, 1, nullptr, 1));
-        ELRUN(conv(EL_BB0 + 4, w.s2b, w.s2a, 4, 128, 3, 1, nullptr, 1));
-        ELRUN(conv(EL_BB0 + 5, w.s2a, w.x2, 4, 128, 3, 1, nullptr, 1));
-        ELRUN(conv(EL_BB0 + 6, w.x2, w.s3a, 4, 128, 3, 2, nullptr, 1));
+        IMCUI_RUN(conv(EL_BB0 + 0, w.s0, w.s1a, 2, 64, 3, 1, nullptr, 1));
+        IMCUI_RUN(conv(EL_BB0 + 1, w.s1a, w.x1, 2, 64, 3, 1, nullptr, 1));
+        IMCUI_RUN(conv(EL_BB0 + 2, w.x1, w.s2a, 2, 64, 3, 2, nullptr, 1));
+        IMCUI_RUN(conv(EL_BB0 + 3, w.s2a, w.s2b, 4, 128, 3, 1, nullptr, 1));
+        IMCUI_RUN(conv(EL_BB0 + 4, w.s2b, w.s2a, 4, 128, 3, 1, nullptr, 1));
+        IMCUI_RUN(conv(EL_BB0 + 5, w.s2a, w.x2, 4, 128, 3, 1, nullptr, 1));
+        IMCUI_RUN(conv(EL_BB0 + 6, w.x2, w.s3a, 4, 128, 3, 2, nullptr, 1));
         const float* src = w.s3a;
         for (int i = 7; i < 20; ++i) {
             float* dst = (i == 19) ? w.fc : (src == w.s3a ? w.s3b : w.s3a);
-            ELRUN(conv(EL_BB0 + i, src, dst, 8, 256, 3, 1, nullptr, 1));
+            IMCUI_RUN(conv(EL_BB0 + i, src, dst, 8, 256, 3, 1, nullptr, 1));
             src = dst;
         }
     }
@@ -459,19 +454,19 @@ extern "C" int imcui_hip_eloftr_forward_ex(imcui_hip_t* h, const float* packed, 
     };
     for (int layer = 0; layer < 4; ++layer) {
         if (same) {
-            ELRUN(block(layer * 2 + 0, 0, 0, 0, 0, 2 * B, true));  // self attention on all 2B maps
+            IMCUI_RUN(block(layer * 2 + 0, 0, 0, 0, 0, 2 * B, true));  // self attention on all 2B maps
         } else {
-            ELRUN(block(layer * 2 + 0, 0, 0, 0, 0, B, true));
-            ELRUN(block(layer * 2 + 0, tok1, 1, tok1, 1, B, true));
+            IMCUI_RUN(block(layer * 2 + 0, 0, 0, 0, 0, B, true));
+            IMCUI_RUN(block(layer * 2 + 0, tok1, 1, tok1, 1, B, true));
         }
-        ELRUN(block(layer * 2 + 1, 0, 0, tok1, 1, B, false));  // images 0 <- images 1
-        ELRUN(block(layer * 2 + 1, tok1, 1, 0, 0, B, false));  // images 1 <- UPDATED images 0
+        IMCUI_RUN(block(layer * 2 + 1, 0, 0, tok1, 1, B, false));  // images 0 <- images 1
+        IMCUI_RUN(block(layer * 2 + 1, tok1, 1, 0, 0, B, false));  // images 1 <- UPDATED images 0
     }
     IMCUI_CHECK_LAUNCH(h);
 
     // ---- dual soft-max coarse matching: sim = (f0 / 16) . (f1 / 16)^T / 0.1 is never stored (simred.hip: statistics pass, then the
     // confidences of the tiles that can exceed the threshold)
-    ELRUN(simred_dual_softmax(h, w.ds, w.fc, 256, (long)L * 256, w.fc + tok1 * 256, 256, (long)S * 256, B, L, S, 256, 0.00390625f / 0.1f, (float)match_threshold,
+    IMCUI_RUN(simred_dual_softmax(h, w.ds, w.fc, 256, (long)L * 256, w.fc + tok1 * 256, 256, (long)S * 256, B, L, S, 256, 0.00390625f / 0.1f, (float)match_threshold,
                               w.rmax, w.rsum, w.cmax, w.csum, w.best, w.bestj, w.cbest, stream));
     hipLaunchKernelGGL(lf_decide_kernel, dim3(cdiv(cap, 256)), blk, 0, stream, w.best, w.bestj, w.cbest, L, S, wcs[0], hcs[0], wcs[1], hcs[1], 2,
                        (float)match_threshold, w.flag, (long)cap);
@@ -488,25 +483,25 @@ extern "C" int imcui_hip_eloftr_forward_ex(imcui_hip_t* h, const float* packed, 
                                in + (s ? (size_t)B * npx(0, div) * C : 0), out + (s ? (size_t)B * npx(0, div / 2) * C : 0), hh, ww, C, 2, n4);
         }
     };
-    ELRUN(conv(EL_OUT, w.fc, w.f8, 8, 256, 1, 1, nullptr, 0));
+    IMCUI_RUN(conv(EL_OUT, w.fc, w.f8, 8, 256, 1, 1, nullptr, 0));
     static const bool up_unfused = getenv("IMCUI_UPSAMPLE_UNFUSED") != nullptr;  // A/B switch: materialise the up-sampled maps
     const bool upf = split && !up_unfused;
     if (upf) {
-        ELRUN(conv(EL_F0_C1, w.x2, w.a4, 4, 128, 1, 1, w.f8, 0, true));  // + bilinear x2 of out_conv's map, in the epilogue
+        IMCUI_RUN(conv(EL_F0_C1, w.x2, w.a4, 4, 128, 1, 1, w.f8, 0, true));  // + bilinear x2 of out_conv's map, in the epilogue
     } else {
         upsample2(w.f8, w.u4, 8, 256);
-        ELRUN(conv(EL_F0_C1, w.x2, w.a4, 4, 128, 1, 1, w.u4, 0));
+        IMCUI_RUN(conv(EL_F0_C1, w.x2, w.a4, 4, 128, 1, 1, w.u4, 0));
     }
-    ELRUN(conv(EL_F0_C2, w.a4, w.b4, 4, 256, 3, 1, nullptr, 2));
-    ELRUN(conv(EL_F0_C3, w.b4, w.r4, 4, 256, 3, 1, nullptr, 0));
+    IMCUI_RUN(conv(EL_F0_C2, w.a4, w.b4, 4, 256, 3, 1, nullptr, 2));
+    IMCUI_RUN(conv(EL_F0_C3, w.b4, w.r4, 4, 256, 3, 1, nullptr, 0));
     if (upf) {
-        ELRUN(conv(EL_F1_C1, w.x1, w.a2, 2, 64, 1, 1, w.r4, 0, true));
+        IMCUI_RUN(conv(EL_F1_C1, w.x1, w.a2, 2, 64, 1, 1, w.r4, 0, true));
     } else {
         upsample2(w.r4, w.u2, 4, 128);
-        ELRUN(conv(EL_F1_C1, w.x1, w.a2, 2, 64, 1, 1, w.u2, 0));
+        IMCUI_RUN(conv(EL_F1_C1, w.x1, w.a2, 2, 64, 1, 1, w.u2, 0));
     }
-    ELRUN(conv(EL_F1_C2, w.a2, w.b2, 2, 128, 3, 1, nullptr, 2));
-    ELRUN(conv(EL_F1_C3, w.b2, w.r2, 2, 128, 3, 1, nullptr, 0));
+    IMCUI_RUN(conv(EL_F1_C2, w.a2, w.b2, 2, 128, 3, 1, nullptr, 2));
+    IMCUI_RUN(conv(EL_F1_C3, w.b2, w.r2, 2, 128, 3, 1, nullptr, 0));
 
     // ---- two-stage fine matching on the windows of the matches
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(el_fine_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)EL_FINE_SMEM);
@@ -516,6 +511,5 @@ extern "C" int imcui_hip_eloftr_forward_ex(imcui_hip_t* h, const float* packed, 
     hipMemcpyAsync(batch_indexes, w.mb, (size_t)cap * sizeof(int), hipMemcpyDeviceToDevice, stream);
     hipMemcpyAsync(num_matches, w.nmatch, sizeof(int), hipMemcpyDeviceToDevice, stream);
     IMCUI_CHECK_LAUNCH(h);
-#undef ELRUN
     return IMCUI_OK;
 }

@@ -721,11 +721,6 @@ extern "C" int imcui_hip_lightglue_forward(imcui_hip_t* h, const float* packed, 
     const float filt_f = (float)filter_threshold;
     const dim3 rowgrid(R / 4, S), blk(256);
     int rc;
-#define LGRUN(x)                       \
-    do {                               \
-        rc = (x);                      \
-        if (rc != IMCUI_OK) return rc; \
-    } while (0)
 
     int* cnt_cur = w.cntA;
     int* cnt_next = w.cntB;
@@ -857,7 +852,7 @@ extern "C" int imcui_hip_lightglue_forward(imcui_hip_t* h, const float* packed, 
             g.rope_sin = w.sn;
             g.alpha = 0.125f * 1.44269504088896340736f;  // 1/sqrt(64) and log2(e) folded into q: the attention kernels work in base 2
             g.heads = LG_HEADS;
-            LGRUN(gemm_launch(h, g, stream));
+            IMCUI_RUN(gemm_launch(h, g, stream));
             AttnP a;
             a.Q = w.q;
             a.K = w.k;
@@ -873,8 +868,8 @@ extern "C" int imcui_hip_lightglue_forward(imcui_hip_t* h, const float* packed, 
             a.V6 = w.v6;
             a.part = w.apart;
             if (h->opt[OPT_ATTN_SELF] >= 0 && ((h->opt[OPT_ATTN_MIX_LAYERS] >> layer) & 1)) a.variant = h->opt[OPT_ATTN_SELF];  // (per-block arithmetic mix: audit tool)
-            LGRUN(attention_launch(h, a, stream));
-            LGRUN(ffn(w.ctx, o.w1s, o.s1s, o.b1s, o.gs, o.bs, o.w2s, o.s2s, o.s2sp, o.b2s));
+            IMCUI_RUN(attention_launch(h, a, stream));
+            IMCUI_RUN(ffn(w.ctx, o.w1s, o.s1s, o.b1s, o.gs, o.bs, o.w2s, o.s2s, o.s2sp, o.b2s));
         }
         // ---- CrossBlock
         {
@@ -895,7 +890,7 @@ extern "C" int imcui_hip_lightglue_forward(imcui_hip_t* h, const float* packed, 
             g.V = w.v;
             g.alpha = (float)(0.35355339059327373 * 1.2011224087864498);  // (64 ** -0.5) ** 0.5 and sqrt(log2 e), applied to both sides
             g.heads = LG_HEADS;
-            LGRUN(gemm_launch(h, g, stream));
+            IMCUI_RUN(gemm_launch(h, g, stream));
             AttnP a;
             a.Q = w.q;
             a.K = w.q;
@@ -914,8 +909,8 @@ extern "C" int imcui_hip_lightglue_forward(imcui_hip_t* h, const float* packed, 
                 const int cv = h->opt[OPT_ATTN_CROSS] == -2 ? (h->opt[OPT_ATTN_VARIANT] == 8 ? 7 : -1) : h->opt[OPT_ATTN_CROSS];
                 if (cv >= 0 && ((h->opt[OPT_ATTN_MIX_LAYERS] >> layer) & 1)) a.variant = cv;
             }
-            LGRUN(attention_launch(h, a, stream));
-            LGRUN(ffn(w.ctx, o.w1c, o.s1c, o.b1c, o.gc, o.bc, o.w2c, o.s2c, o.s2cp, o.b2c));
+            IMCUI_RUN(attention_launch(h, a, stream));
+            IMCUI_RUN(ffn(w.ctx, o.w1c, o.s1c, o.b1c, o.gc, o.bc, o.w2c, o.s2c, o.s2cp, o.b2c));
         }
         if (h->lg_dump) {  // parity-test hook: token states after this layer (rows in their current, pruned order)
             const size_t nf = (size_t)S * R * 256;
@@ -969,7 +964,7 @@ extern "C" int imcui_hip_lightglue_forward(imcui_hip_t* h, const float* packed, 
         g.alpha = 0.25f;
         g.C = w.md;
         g.ldc = 256;
-        LGRUN(gemm_launch(h, g, stream));
+        IMCUI_RUN(gemm_launch(h, g, stream));
     }
     hipLaunchKernelGGL(lg_match_logit_kernel, rowgrid, blk, 0, stream, w.x, P + l.wmatch, P + l.bmatch, stop, cnt_cur, R,
                        w.ls);
@@ -990,19 +985,18 @@ extern "C" int imcui_hip_lightglue_forward(imcui_hip_t* h, const float* packed, 
         sp.nchunk = nchunk;
         sp.r0 = w.rpm, sp.r1 = w.rps, sp.ri = w.rpj, sp.r_pitch = R;
         sp.c0 = w.cpm, sp.c1 = w.cps, sp.ci = w.cpi, sp.c_pitch = R;
-        LGRUN(simred_launch(h, sp, stream));
+        IMCUI_RUN(simred_launch(h, sp, stream));
         const dim3 mg(cdiv(R, 256), B, 2);
         hipLaunchKernelGGL(lg_stat_merge_kernel, mg, blk, 0, stream, w.rpm, w.rps, w.cpm, w.cps, cnt_cur, R, nchunk, nrb, tpc * 128, 128, 128, w.rmax, w.rls, w.cmax,
                            w.cls);
         sp.mode = SR_LGBEST;
         sp.rmax = w.rmax, sp.rsum = w.rls, sp.cmax = w.cmax, sp.csum = w.cls;
         sp.l0 = w.ls, sp.l1 = w.ls + R, sp.l0_bs = sp.l1_bs = (long)2 * R;
-        LGRUN(simred_launch(h, sp, stream));
+        IMCUI_RUN(simred_launch(h, sp, stream));
         hipLaunchKernelGGL(lg_best_merge_kernel, mg, blk, 0, stream, w.rpm, w.rpj, w.cpm, w.cpi, cnt_cur, R, nchunk, nrb, tpc * 128, 128, w.max0, w.m0, w.m1);
     }
     hipLaunchKernelGGL(lg_filter_kernel, dim3(B), blk, 0, stream, cnt_cur, w.norig, R, ncap, w.m0, w.m1, w.max0, w.ind,
                        w.prune, w.ms0, w.valid0, filt_f, matches0, matches1, mscores0, mscores1, prune0, prune1);
     IMCUI_CHECK_LAUNCH(h);
-#undef LGRUN
     return IMCUI_OK;
 }

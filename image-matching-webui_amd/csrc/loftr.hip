@@ -315,11 +315,6 @@ extern "C" int imcui_hip_loftr_forward(imcui_hip_t* h, const float* packed, cons
     const int L = Ls[0], S = Ls[1];
     const int cap = B * L;
     int rc;
-#define LFRUN(x)                       \
-    do {                               \
-        rc = (x);                      \
-        if (rc != IMCUI_OK) return rc; \
-    } while (0)
 
     auto wts = [&](GemmP& g, int li) {
         int N, K;
@@ -401,21 +396,21 @@ extern "C" int imcui_hip_loftr_forward(imcui_hip_t* h, const float* packed, cons
                            P + l.conv1_b, w.x0 + (s ? (size_t)B * npx(0, 2) * 128 : 0), Hs[s], Ws[s], H2s, W2s, npix);
     }
     IMCUI_CHECK_LAUNCH(h);
-    LFRUN(conv(LF_L1_0_C1, w.x0, w.t1, 2, 128, 3, 1, nullptr, 1));
-    LFRUN(conv(LF_L1_0_C2, w.t1, w.x1a, 2, 128, 3, 1, w.x0, 1));
-    LFRUN(conv(LF_L1_1_C1, w.x1a, w.t1, 2, 128, 3, 1, nullptr, 1));
-    LFRUN(conv(LF_L1_1_C2, w.t1, w.x1, 2, 128, 3, 1, w.x1a, 1));
-    LFRUN(conv(LF_L2_0_C1, w.x1, w.t2, 2, 128, 3, 2, nullptr, 1));
-    LFRUN(conv(LF_L2_0_DS, w.x1, w.ds2, 2, 128, 1, 2, nullptr, 0));
-    LFRUN(conv(LF_L2_0_C2, w.t2, w.x2a, 4, CP, 3, 1, w.ds2, 1));
-    LFRUN(conv(LF_L2_1_C1, w.x2a, w.t2, 4, CP, 3, 1, nullptr, 1));
-    LFRUN(conv(LF_L2_1_C2, w.t2, w.x2, 4, CP, 3, 1, w.x2a, 1));
-    LFRUN(conv(LF_L3_0_C1, w.x2, w.t3, 4, CP, 3, 2, nullptr, 1));
-    LFRUN(conv(LF_L3_0_DS, w.x2, w.ds3, 4, CP, 1, 2, nullptr, 0));
-    LFRUN(conv(LF_L3_0_C2, w.t3, w.x3a, 8, 256, 3, 1, w.ds3, 1));
-    LFRUN(conv(LF_L3_1_C1, w.x3a, w.t3, 8, 256, 3, 1, nullptr, 1));
-    LFRUN(conv(LF_L3_1_C2, w.t3, w.x3, 8, 256, 3, 1, w.x3a, 1));
-    LFRUN(conv(LF_OUT3, w.x3, w.fc, 8, 256, 1, 1, nullptr, 0));
+    IMCUI_RUN(conv(LF_L1_0_C1, w.x0, w.t1, 2, 128, 3, 1, nullptr, 1));
+    IMCUI_RUN(conv(LF_L1_0_C2, w.t1, w.x1a, 2, 128, 3, 1, w.x0, 1));
+    IMCUI_RUN(conv(LF_L1_1_C1, w.x1a, w.t1, 2, 128, 3, 1, nullptr, 1));
+    IMCUI_RUN(conv(LF_L1_1_C2, w.t1, w.x1, 2, 128, 3, 1, w.x1a, 1));
+    IMCUI_RUN(conv(LF_L2_0_C1, w.x1, w.t2, 2, 128, 3, 2, nullptr, 1));
+    IMCUI_RUN(conv(LF_L2_0_DS, w.x1, w.ds2, 2, 128, 1, 2, nullptr, 0));
+    IMCUI_RUN(conv(LF_L2_0_C2, w.t2, w.x2a, 4, CP, 3, 1, w.ds2, 1));
+    IMCUI_RUN(conv(LF_L2_1_C1, w.x2a, w.t2, 4, CP, 3, 1, nullptr, 1));
+    IMCUI_RUN(conv(LF_L2_1_C2, w.t2, w.x2, 4, CP, 3, 1, w.x2a, 1));
+    IMCUI_RUN(conv(LF_L3_0_C1, w.x2, w.t3, 4, CP, 3, 2, nullptr, 1));
+    IMCUI_RUN(conv(LF_L3_0_DS, w.x2, w.ds3, 4, CP, 1, 2, nullptr, 0));
+    IMCUI_RUN(conv(LF_L3_0_C2, w.t3, w.x3a, 8, 256, 3, 1, w.ds3, 1));
+    IMCUI_RUN(conv(LF_L3_1_C1, w.x3a, w.t3, 8, 256, 3, 1, nullptr, 1));
+    IMCUI_RUN(conv(LF_L3_1_C2, w.t3, w.x3, 8, 256, 3, 1, w.x3a, 1));
+    IMCUI_RUN(conv(LF_OUT3, w.x3, w.fc, 8, 256, 1, 1, nullptr, 0));
     // bilinear x2 (align_corners=True) of the maps at resolution 1/div with C channels, per side
     auto upsample = [&](const float* in, float* out, int div, int C) {
         for (int s = 0; s < (same ? 1 : 2); ++s) {
@@ -428,25 +423,25 @@ extern "C" int imcui_hip_loftr_forward(imcui_hip_t* h, const float* packed, cons
     static const bool up_unfused = getenv("IMCUI_UPSAMPLE_UNFUSED") != nullptr;  // A/B switch: materialise the up-sampled maps
     const bool upf = split && !up_unfused;
     if (upf) {
-        LFRUN(conv(LF_OUT2, w.x2, w.x2o, 4, CP, 1, 1, w.fc, 0, true));  // + bilinear x2 of layer3_outconv's map, in the epilogue
+        IMCUI_RUN(conv(LF_OUT2, w.x2, w.x2o, 4, CP, 1, 1, w.fc, 0, true));  // + bilinear x2 of layer3_outconv's map, in the epilogue
     } else {
         upsample(w.fc, w.up3, 8, 256);
-        LFRUN(conv(LF_OUT2, w.x2, w.x2o, 4, CP, 1, 1, w.up3, 0));
+        IMCUI_RUN(conv(LF_OUT2, w.x2, w.x2o, 4, CP, 1, 1, w.up3, 0));
     }
-    LFRUN(conv(LF_OUT2B_0, w.x2o, w.y2, 4, 256, 3, 1, nullptr, 2));
-    LFRUN(conv(LF_OUT2B_3, w.y2, w.x2out, 4, 256, 3, 1, nullptr, 0));
+    IMCUI_RUN(conv(LF_OUT2B_0, w.x2o, w.y2, 4, 256, 3, 1, nullptr, 2));
+    IMCUI_RUN(conv(LF_OUT2B_3, w.y2, w.x2out, 4, 256, 3, 1, nullptr, 0));
     // The last FPN stage (1/2 resolution: layer1_outconv + layer1_outconv2 -> the 128-channel fine map `ff`) is only ever read through the
     // 5x5 windows of the matched cells.  Option loftr_fine_sparse (default 1): it is deferred until the matches are known and evaluated on
     // the windows alone when that is the cheaper way (few matches; `sparse_fine_stage` below); 0 = always the dense maps, here, as before.
     auto dense_fine_stage = [&]() -> int {
         if (upf) {
-            LFRUN(conv(LF_OUT1, w.x1, w.x1o, 2, 128, 1, 1, w.x2out, 0, true));
+            IMCUI_RUN(conv(LF_OUT1, w.x1, w.x1o, 2, 128, 1, 1, w.x2out, 0, true));
         } else {
             upsample(w.x2out, w.up2, 4, CP);
-            LFRUN(conv(LF_OUT1, w.x1, w.x1o, 2, 128, 1, 1, w.up2, 0));
+            IMCUI_RUN(conv(LF_OUT1, w.x1, w.x1o, 2, 128, 1, 1, w.up2, 0));
         }
-        LFRUN(conv(LF_OUT1B_0, w.x1o, w.y1, 2, CP, 3, 1, nullptr, 2));
-        LFRUN(conv(LF_OUT1B_3, w.y1, w.ff, 2, CP, 3, 1, nullptr, 0));
+        IMCUI_RUN(conv(LF_OUT1B_0, w.x1o, w.y1, 2, CP, 3, 1, nullptr, 2));
+        IMCUI_RUN(conv(LF_OUT1B_3, w.y1, w.ff, 2, CP, 3, 1, nullptr, 0));
         return IMCUI_OK;
     };
     h->loftr_fine_mode = 0;
@@ -456,7 +451,7 @@ extern "C" int imcui_hip_loftr_forward(imcui_hip_t* h, const float* packed, cons
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
         if (hipStreamIsCapturing(stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) fine_deferred = false;
     }
-    if (!fine_deferred) LFRUN(dense_fine_stage());
+    if (!fine_deferred) IMCUI_RUN(dense_fine_stage());
 
     // ---- a14: positional encoding + coarse LocalFeatureTransformer (linear attention)
     const size_t tok1 = (size_t)B * L;  // first token row of side 1
@@ -536,14 +531,14 @@ extern "C" int imcui_hip_loftr_forward(imcui_hip_t* h, const float* packed, cons
     for (int layer = 0; layer < 8; ++layer) {
         if ((layer & 1) == 0) {  // self: every image attends to itself
             if (same) {
-                LFRUN(coarse_layer(layer, 0, 0, 2 * B, L, L, 0));
+                IMCUI_RUN(coarse_layer(layer, 0, 0, 2 * B, L, L, 0));
             } else {
-                LFRUN(coarse_layer(layer, 0, 0, B, L, L, 0));
-                LFRUN(coarse_layer(layer, tok1, tok1, B, S, S, B));
+                IMCUI_RUN(coarse_layer(layer, 0, 0, B, L, L, 0));
+                IMCUI_RUN(coarse_layer(layer, tok1, tok1, B, S, S, B));
             }
         } else {
-            LFRUN(coarse_layer(layer, 0, tok1, B, L, S, B));  // feat0 <- layer(feat0, feat1)
-            LFRUN(coarse_layer(layer, tok1, 0, B, S, L, 0));  // feat1 <- layer(feat1, updated feat0)
+            IMCUI_RUN(coarse_layer(layer, 0, tok1, B, L, S, B));  // feat0 <- layer(feat0, feat1)
+            IMCUI_RUN(coarse_layer(layer, tok1, 0, B, S, L, 0));  // feat1 <- layer(feat1, updated feat0)
         }
     }
     IMCUI_CHECK_LAUNCH(h);
@@ -552,7 +547,7 @@ extern "C" int imcui_hip_loftr_forward(imcui_hip_t* h, const float* packed, cons
     // stored: simred.hip computes it tile by tile twice, once for the soft-max statistics of both directions and once
     // more, only where a confidence can exceed the threshold, for conf = softmax_i * softmax_j, its row maxima (first column) and its
     // column maxima.  (Rounds 2-4 wrote the matrix and read it back two to four times: 51.6 GB of HBM traffic per 16-pair step.)
-    LFRUN(simred_dual_softmax(h, w.ds, w.fc, 256, (long)L * 256, w.fc + tok1 * 256, 256, (long)S * 256, B, L, S, 256, 0.00390625f / 0.1f, (float)match_threshold,
+    IMCUI_RUN(simred_dual_softmax(h, w.ds, w.fc, 256, (long)L * 256, w.fc + tok1 * 256, 256, (long)S * 256, B, L, S, 256, 0.00390625f / 0.1f, (float)match_threshold,
                               w.rmax, w.rsum, w.cmax, w.csum, w.best, w.bestj, w.cbest, stream));
     const dim3 blk(256);
     hipLaunchKernelGGL(lf_decide_kernel, dim3(cdiv(cap, 256)), blk, 0, stream, w.best, w.bestj, w.cbest, L, S, wcs[0], hcs[0], wcs[1], hcs[1],
@@ -607,7 +602,7 @@ extern "C" int imcui_hip_loftr_forward(imcui_hip_t* h, const float* packed, cons
                         g.resid = T;
                         g.ldr = g.N;
                         g.act = 0;
-                        LFRUN(gemm_launch(h, g, stream));
+                        IMCUI_RUN(gemm_launch(h, g, stream));
                         hipLaunchKernelGGL(lf_win_mask_kernel, dim3(mgrid), blk, 0, stream, T, V, n, 9, 0, (long)CP, CP);
                     }
                     auto wconv = [&](int li, const float* in, int side_in, float* out, long ldc, int act) -> int {
@@ -627,10 +622,10 @@ extern "C" int imcui_hip_loftr_forward(imcui_hip_t* h, const float* packed, cons
                         g.act = act;
                         return gemm_launch(h, g, stream);
                     };
-                    LFRUN(wconv(LF_OUT1B_0, T, 9, Y1, CP, 2));
+                    IMCUI_RUN(wconv(LF_OUT1B_0, T, 9, Y1, CP, 2));
                     hipLaunchKernelGGL(lf_win_mask_kernel, dim3(mgrid), blk, 0, stream, Y1, V, n, 7, 1, (long)CP, CP);
                     float* Xs = w.X + ((size_t)s * cap + m0) * 25 * 256;  // the window rows of these matches: [25][fine 128 | coarse 128]
-                    LFRUN(wconv(LF_OUT1B_3, Y1, 7, Xs, 256, 0));
+                    IMCUI_RUN(wconv(LF_OUT1B_3, Y1, 7, Xs, 256, 0));
                     hipLaunchKernelGGL(lf_win_mask_kernel, dim3(mgrid), blk, 0, stream, Xs, V, n, 5, 2, (long)256, 128);
                     IMCUI_CHECK_LAUNCH(h);
                 }
@@ -638,7 +633,7 @@ extern "C" int imcui_hip_loftr_forward(imcui_hip_t* h, const float* packed, cons
             sparse_done = true;
             h->loftr_fine_mode = 1;
         } else {
-            LFRUN(dense_fine_stage());
+            IMCUI_RUN(dense_fine_stage());
         }
     }
     hipLaunchKernelGGL(lf_fine_gather_kernel, dim3(gcap, 2), blk, 0, stream, sparse_done ? (const float*)nullptr : w.ff, w.fc, w.mb, w.mi, w.mj, w.nmatch, B, cap,
@@ -668,10 +663,10 @@ extern "C" int imcui_hip_loftr_forward(imcui_hip_t* h, const float* packed, cons
         g.cnt_stride = 0;
         return gemm_launch(h, g, stream);
     };
-    LFRUN(lin_b(LF_DOWN, w.CG, 256, nullptr, w.CW, cap, 0, 0, 0, 2, true));
+    IMCUI_RUN(lin_b(LF_DOWN, w.CG, 256, nullptr, w.CW, cap, 0, 0, 0, 2, true));
     hipLaunchKernelGGL(lf_fine_fill_kernel, dim3(gcap, 2), blk, 0, stream, w.CW, w.nmatch, cap, w.X);
     const long wcap = (long)cap * 25;
-    LFRUN(lin_b(LF_MERGEF, w.X, 256, nullptr, w.F, wcap, 0, 1, 0, 2, true));
+    IMCUI_RUN(lin_b(LF_MERGEF, w.X, 256, nullptr, w.F, wcap, 0, 1, 0, 2, true));
     auto fine_layer = [&](int layer, int side0, int nsides, int cross) -> int {
         const int base = LF_FINE0 + layer * 6;
         const int src0 = cross ? 1 - side0 : side0;
@@ -697,9 +692,9 @@ extern "C" int imcui_hip_loftr_forward(imcui_hip_t* h, const float* packed, cons
                            P + l.norm[nl + 3], f0, f0, rows, 1, w.cnt2 + 1, wcap);
         return IMCUI_OK;
     };
-    LFRUN(fine_layer(0, 0, 2, 0));  // self on both windows
-    LFRUN(fine_layer(1, 0, 1, 1));  // cross: window0 <- (window0, window1)
-    LFRUN(fine_layer(1, 1, 1, 1));  //        window1 <- (window1, updated window0)
+    IMCUI_RUN(fine_layer(0, 0, 2, 0));  // self on both windows
+    IMCUI_RUN(fine_layer(1, 0, 1, 1));  // cross: window0 <- (window0, window1)
+    IMCUI_RUN(fine_layer(1, 1, 1, 1));  //        window1 <- (window1, updated window0)
     // kornia: scale = hw0_i[0] / hw0_c[0] (= 8) for BOTH images' coarse key-points, fine offsets scaled by hw0_i[0] / hw0_f[0] (= 2)
     hipLaunchKernelGGL(lf_fine_match_kernel, dim3(cdiv(gcap, 4)), blk, 0, stream, w.F, w.mi, w.mj, w.nmatch, cap, wcs[0], wcs[1],
                        (float)H0 / (float)hcs[0], (float)H0 / (float)(H0 / 2), keypoints0, keypoints1);
@@ -707,6 +702,5 @@ extern "C" int imcui_hip_loftr_forward(imcui_hip_t* h, const float* packed, cons
     hipLaunchKernelGGL(lf_copy_int_kernel, dim3(cdiv(cap, 256)), blk, 0, stream, w.mb, batch_indexes, cap);
     hipLaunchKernelGGL(lf_copy_int_kernel, dim3(1), dim3(64), 0, stream, w.nmatch, num_matches, 1);
     IMCUI_CHECK_LAUNCH(h);
-#undef LFRUN
     return IMCUI_OK;
 }

@@ -801,11 +801,6 @@ extern "C" int imcui_hip_superglue_forward(imcui_hip_t* h, const float* packed, 
     const int S = 2 * B;
     const dim3 rowgrid(R / 4, S), blk(256);
     int rc;
-#define SGRUN(x)                       \
-    do {                               \
-        rc = (x);                      \
-        if (rc != IMCUI_OK) return rc; \
-    } while (0)
 
     hipLaunchKernelGGL(sg_init_pairs_kernel, dim3(cdiv(B, 64)), dim3(64), 0, stream, n0, n1, B, w.cnt, w.active);
     hipLaunchKernelGGL(sg_init_kernel, rowgrid, blk, 0, stream, keypoints0, keypoints1, scores0, scores1, descriptors0, descriptors1,
@@ -847,7 +842,7 @@ extern "C" int imcui_hip_superglue_forward(imcui_hip_t* h, const float* packed, 
             g.bias = P + l.kb[i];
             g.C = (i < 3) ? bufs[i & 1] : w.x;
             g.ldc = (i < 3) ? N : 256;
-            SGRUN(gemm_launch(h, g, stream));
+            IMCUI_RUN(gemm_launch(h, g, stream));
             src = bufs[i & 1];
         }
     }
@@ -874,7 +869,7 @@ extern "C" int imcui_hip_superglue_forward(imcui_hip_t* h, const float* packed, 
         g.rope_sin = w.zero;
         g.alpha = 0.125f * 1.44269504088896340736f;  // scores / 64 ** .5 and log2(e) folded into q: the attention kernels work in base 2
         g.heads = SG_HEADS;
-        SGRUN(gemm_launch(h, g, stream));
+        IMCUI_RUN(gemm_launch(h, g, stream));
         AttnP a;
         a.Q = w.q;
         a.K = w.k;
@@ -887,7 +882,7 @@ extern "C" int imcui_hip_superglue_forward(imcui_hip_t* h, const float* packed, 
         a.rows_per_seq = R;
         a.cross = layer & 1;
         a.log2_domain = 1;
-        SGRUN(attention_launch(h, a, stream));
+        IMCUI_RUN(attention_launch(h, a, stream));
         if (split && !ffn_unfused) {
             // x += mlp.3(relu(bn(mlp.0(cat[x, merge(ctx)])))) as one kernel (ffn.hip; merge and bn folded into mlp.0)
             FfnP f;
@@ -907,7 +902,7 @@ extern "C" int imcui_hip_superglue_forward(imcui_hip_t* h, const float* packed, 
             f.cnt = w.cnt;
             f.active = w.active;
             f.rows_per_seq = R;
-            SGRUN(ffn_launch(h, f, stream));
+            IMCUI_RUN(ffn_launch(h, f, stream));
             continue;
         }
         GemmP f1;  // relu(bn(mlp.0(cat[x, merge(ctx)]))) with merge and bn folded into the weights
@@ -925,7 +920,7 @@ extern "C" int imcui_hip_superglue_forward(imcui_hip_t* h, const float* packed, 
         f1.bias = P + o.b1;
         f1.C = w.hbuf;
         f1.ldc = 512;
-        SGRUN(gemm_launch(h, f1, stream));
+        IMCUI_RUN(gemm_launch(h, f1, stream));
         GemmP f2;  // x += mlp.3(h)
         base(f2);
         f2.epi = EPI_RESID;
@@ -938,7 +933,7 @@ extern "C" int imcui_hip_superglue_forward(imcui_hip_t* h, const float* packed, 
         f2.bias = P + o.b2;
         f2.C = w.x;
         f2.ldc = 256;
-        SGRUN(gemm_launch(h, f2, stream));
+        IMCUI_RUN(gemm_launch(h, f2, stream));
     }
     {
         GemmP g;  // md = final_proj(x) / 256^(1/4): md0 . md1 = scores / 256 ** .5 (exact power of two)
@@ -954,7 +949,7 @@ extern "C" int imcui_hip_superglue_forward(imcui_hip_t* h, const float* packed, 
         g.alpha = 0.25f;
         g.C = w.md;
         g.ldc = 256;
-        SGRUN(gemm_launch(h, g, stream));
+        IMCUI_RUN(gemm_launch(h, g, stream));
     }
     {
         GemmP g;  // sim[b] = md0[b] . md1[b]^T
@@ -975,7 +970,7 @@ extern "C" int imcui_hip_superglue_forward(imcui_hip_t* h, const float* packed, 
         g.mcnt = w.cnt;
         g.ncnt = w.cnt + 1;
         g.cnt_stride = 2;
-        SGRUN(gemm_launch(h, g, stream));
+        IMCUI_RUN(gemm_launch(h, g, stream));
     }
     // ---- log-domain Sinkhorn with dust-bins, then mutual arg-max + threshold
     // (Running the rounds chunk-wise so that a chunk's matrices fit the 256 MB memory-side cache measured slower
@@ -996,6 +991,5 @@ extern "C" int imcui_hip_superglue_forward(imcui_hip_t* h, const float* packed, 
     hipLaunchKernelGGL(sg_filter_kernel, dim3(B), blk, 0, stream, w.cnt, w.active, R, ncap, w.m0, w.m1, w.max0, (float)match_threshold,
                        matches0, matches1, mscores0, mscores1);
     IMCUI_CHECK_LAUNCH(h);
-#undef SGRUN
     return IMCUI_OK;
 }

@@ -514,11 +514,6 @@ extern "C" int imcui_hip_superpoint_forward(imcui_hip_t* h, const float* packed,
     const SpLayout l = sp_layout();
     const float* P = packed;
     int rc;
-#define SPRUN(x)              \
-    do {                      \
-        rc = (x);             \
-        if (rc != IMCUI_OK) return rc; \
-    } while (0)
     const int Hc = H / 8, Wc = W / 8;
     const bool split = h->precision == 1;
     auto conv = [&](int L, const float* src, float* dst, int hh, int ww, int pool) -> int {
@@ -552,30 +547,30 @@ extern "C" int imcui_hip_superpoint_forward(imcui_hip_t* h, const float* packed,
     if (split) {
         // conv1a is evaluated inside conv1b's patch staging: its 64-channel full-resolution output
         // (79 MB / image) never reaches HBM
-        SPRUN(conv1ab_fused_split_launch(h, image, P + l.w[L1A], P + l.b[L1A],
+        IMCUI_RUN(conv1ab_fused_split_launch(h, image, P + l.w[L1A], P + l.b[L1A],
                                          reinterpret_cast<const unsigned short*>(P + l.wh[L1B]),
                                          reinterpret_cast<const unsigned short*>(P + l.wl[L1B]), P + l.ws[L1B], P + l.b[L1B],
                                          s.p1, B, H, W, 1, stream));
     } else {
-        SPRUN(conv1a_launch(h, image, P + l.w[L1A], P + l.b[L1A], s.a1a, B, H, W, stream));
-        SPRUN(conv(L1B, s.a1a, s.p1, H, W, 1));
+        IMCUI_RUN(conv1a_launch(h, image, P + l.w[L1A], P + l.b[L1A], s.a1a, B, H, W, stream));
+        IMCUI_RUN(conv(L1B, s.a1a, s.p1, H, W, 1));
     }
-    SPRUN(conv(L2A, s.p1, s.a2a, H / 2, W / 2, 0));
-    SPRUN(conv(L2B, s.a2a, s.p2, H / 2, W / 2, 1));
-    SPRUN(conv(L3A, s.p2, s.a3a, H / 4, W / 4, 0));
-    SPRUN(conv(L3B, s.a3a, s.p3, H / 4, W / 4, 1));
-    SPRUN(conv(L4A, s.p3, s.a4a, Hc, Wc, 0));
-    SPRUN(conv(L4B, s.a4a, s.feat, Hc, Wc, 0));
+    IMCUI_RUN(conv(L2A, s.p1, s.a2a, H / 2, W / 2, 0));
+    IMCUI_RUN(conv(L2B, s.a2a, s.p2, H / 2, W / 2, 1));
+    IMCUI_RUN(conv(L3A, s.p2, s.a3a, H / 4, W / 4, 0));
+    IMCUI_RUN(conv(L3B, s.a3a, s.p3, H / 4, W / 4, 1));
+    IMCUI_RUN(conv(L4A, s.p3, s.a4a, Hc, Wc, 0));
+    IMCUI_RUN(conv(L4B, s.a4a, s.feat, Hc, Wc, 0));
     // a3: detector head -> dense score map
-    SPRUN(conv(LPA, s.feat, s.head, Hc, Wc, 0));
+    IMCUI_RUN(conv(LPA, s.feat, s.head, Hc, Wc, 0));
     const long ncell = (long)B * Hc * Wc;
-    SPRUN(lin(LPB, s.head, s.logits, 65));
+    IMCUI_RUN(lin(LPB, s.head, s.logits, 65));
     float* dense = score_map ? score_map : s.dense;
     hipLaunchKernelGGL(sp_softmax_kernel, dim3((unsigned)((ncell + 3) / 4)), dim3(256), 0, stream, s.logits, 65, dense, Hc,
                        Wc, ncell);
     IMCUI_CHECK_LAUNCH(h);
     // a4: NMS ; a5: select
-    SPRUN(nms_launch(h, dense, s.nms, B, H, W, nms_radius, stream));
+    IMCUI_RUN(nms_launch(h, dense, s.nms, B, H, W, nms_radius, stream));
     const int nchunk = cdiv(H * W, SEL_CHUNK);
     int* st = status ? status : s.status;
     hipMemsetAsync(st, 0, sizeof(int), stream);
@@ -596,12 +591,11 @@ extern "C" int imcui_hip_superpoint_forward(imcui_hip_t* h, const float* packed,
     }
     IMCUI_CHECK_LAUNCH(h);
     // a6: descriptor head + sampling
-    SPRUN(conv(LDA, s.feat, s.head, Hc, Wc, 0));
-    SPRUN(lin(LDB, s.head, s.ddesc, 256));
+    IMCUI_RUN(conv(LDA, s.feat, s.head, Hc, Wc, 0));
+    IMCUI_RUN(lin(LDB, s.head, s.ddesc, 256));
     hipLaunchKernelGGL(sp_sample_kernel, dim3(cdiv(kcap, 4), B), dim3(256), 0, stream, s.ddesc, keypoints, num_keypoints,
                        kcap, Hc, Wc, fix_sampling, descriptors);
     IMCUI_CHECK_LAUNCH(h);
-#undef SPRUN
     return IMCUI_OK;
 }
 

@@ -26,6 +26,7 @@
 
 #include "gemm.h"
 #include "imcui_hip.h"
+#include "netpack.h"
 #include "select.h"
 
 // ------------------------------------------------------------------ layer table and packed weight layout
@@ -56,37 +57,26 @@ static bool xf_is_gemm(int i) { return i >= XF_NSTEM && i != XF_L_HEAT; }
 
 // The buffer begins with block1.0 folded with its BatchNorm as [9 taps][1][4] floats, followed (from float 64) by its 4 folded biases.
 struct XfLayout {
-    size_t w[XF_NL], b[XF_NL], wh[XF_NL], wl[XF_NL], ws[XF_NL];  // stem / heat: w = [tap][cin][cout]; GEMM: [npad][tap][cpad] + f16 planes
-    size_t skw, skb;                                             // skip1.1: weight [24], bias [24]
+    GemmLayerOff g[XF_NL];  // stem / heat: w = [tap][cin][cout] and b only; GEMM: [npad][tap][cpad] + f16 planes
+    size_t skw, skb;        // skip1.1: weight [24], bias [24]
     size_t total;
 };
 
 static XfLayout xf_layout() {
     XfLayout l;
-    size_t off = 0;
-    auto get = [&](size_t n) {
-        const size_t o = off;
-        off += align_up(n, 64);
-        return o;
-    };
+    PackCursor c;
     for (int i = 0; i < XF_NL; ++i) {
         const XfLayer& L = XF_LAYERS[i];
-        l.wh[i] = l.wl[i] = l.ws[i] = 0;
         if (!xf_is_gemm(i)) {
-            l.w[i] = get((size_t)L.k * L.k * L.cin * L.cout);
-            l.b[i] = get(L.cout);
+            l.g[i].w = c.get((size_t)L.k * L.k * L.cin * L.cout);
+            l.g[i].b = c.get(L.cout);
         } else {
-            const size_t K = (size_t)L.k * L.k * L.cpad, np = align_up(L.npad, 32);
-            l.w[i] = get((size_t)L.npad * K);
-            l.b[i] = get(L.npad);
-            l.wh[i] = get(np * K / 2);
-            l.wl[i] = get(np * K / 2);
-            l.ws[i] = get(1);
+            l.g[i].place(c, L.npad, L.k * L.k * L.cpad);
         }
     }
-    l.skw = get(24);
-    l.skb = get(24);
-    l.total = off;
+    l.skw = c.get(24);
+    l.skb = c.get(24);
+    l.total = c.off;
     return l;
 }
 
@@ -147,14 +137,13 @@ extern "C" int imcui_hip_xfeat_pack_weights(const float* const* t, float* packed
         if (!xf_is_gemm(i)) {  // [tap][cin][cout]
             for (int co = 0; co < L.cout; ++co)
                 for (int ci = 0; ci < L.cin; ++ci)
-                    for (int tap = 0; tap < kk; ++tap) packed[l.w[i] + ((size_t)tap * L.cin + ci) * L.cout + co] = wf[((size_t)co * L.cin + ci) * kk + tap];
-            memcpy(packed + l.b[i], bf.data(), L.cout * sizeof(float));
+                    for (int tap = 0; tap < kk; ++tap) packed[l.g[i].w + ((size_t)tap * L.cin + ci) * L.cout + co] = wf[((size_t)co * L.cin + ci) * kk + tap];
+            memcpy(packed + l.g[i].b, bf.data(), L.cout * sizeof(float));
         } else {  // rows cout .. npad - 1 (the zero channels of the 24-channel maps) stay zero
             const int K = kk * L.cpad;
-            pack_conv_gemm(wf.data(), L.cout, L.cin, L.k, L.cpad, packed + l.w[i]);
-            memcpy(packed + l.b[i], bf.data(), L.cout * sizeof(float));
-            packed[l.ws[i]] = split_weights_frag_host(packed + l.w[i], L.npad, K, reinterpret_cast<unsigned short*>(packed + l.wh[i]),
-                                                      reinterpret_cast<unsigned short*>(packed + l.wl[i]));
+            pack_conv_gemm(wf.data(), L.cout, L.cin, L.k, L.cpad, packed + l.g[i].w);
+            memcpy(packed + l.g[i].b, bf.data(), L.cout * sizeof(float));
+            l.g[i].split_planes(packed, L.npad, K);
         }
     }
     return IMCUI_OK;
@@ -684,11 +673,6 @@ extern "C" int imcui_hip_xfeat_forward(imcui_hip_t* h, const float* packed, cons
     const float* P = packed;
     const bool split = h->precision == 1;
     int rc;
-#define XFRUN(x)                       \
-    do {                               \
-        rc = (x);                      \
-        if (rc != IMCUI_OK) return rc; \
-    } while (0)
     auto px = [&](int lev) { return (long)(Hr >> lev) * (Wr >> lev); };
     // layer L on the map `in` at level lev_in (pixel stride = the layer's stored input channels) -> `out` (pixel stride ldo)
     auto layer = [&](int L, const float* in, int lev_in, float* out, int ldo) -> int {
@@ -697,32 +681,15 @@ extern "C" int imcui_hip_xfeat_forward(imcui_hip_t* h, const float* packed, cons
         GemmP g;
         g.epi = EPI_CONV;
         g.A = in;
-        g.W = P + l.w[L];
-        g.K = X.k * X.k * X.cpad;
-        g.ldw = g.K;
-        if (split) {
-            g.Wh = reinterpret_cast<const unsigned short*>(P + l.wh[L]);
-            g.Wl = reinterpret_cast<const unsigned short*>(P + l.wl[L]);
-            g.wscale = P + l.ws[L];
-        }
-        g.bias = P + l.b[L];
-        g.N = X.npad;
+        gemm_set_weights(g, P, l.g[L], X.npad, X.k * X.k * X.cpad, split);
         g.M = (int)(B * px(lev_out));
         g.C = out;
         g.ldc = ldo;
         g.act = X.bn ? 1 : 0;
-        if (X.k == 3) {
-            g.conv_k = 3;
-            g.conv_stride = X.stride;
-            g.conv_pad = 1;
-            g.conv_hin = Hr >> lev_in;
-            g.conv_win = Wr >> lev_in;
-            g.conv_hout = Hr >> lev_out;
-            g.conv_wout = Wr >> lev_out;
-            g.conv_cin = X.cpad;
-        } else {
+        if (X.k == 3)
+            gemm_set_conv(g, 3, X.stride, 1, Hr >> lev_in, Wr >> lev_in, Hr >> lev_out, Wr >> lev_out, X.cpad);
+        else
             g.lda = X.cpad;
-        }
         return gemm_launch(h, g, stream);
     };
     // ---- input stage
@@ -735,49 +702,49 @@ extern "C" int imcui_hip_xfeat_forward(imcui_hip_t* h, const float* packed, cons
     IMCUI_CHECK_LAUNCH(h);
     // ---- block1 + skip1 (VALU)
     const float* nul = nullptr;
-    hipLaunchKernelGGL((xf_stem_kernel<1, 4, 4, 1, true, false>), dim3(xf_grid(np0)), dim3(256), 0, stream, s.gray, P + l.w[0], P + l.b[0], s.s1, Hr, Wr, Hr,
+    hipLaunchKernelGGL((xf_stem_kernel<1, 4, 4, 1, true, false>), dim3(xf_grid(np0)), dim3(256), 0, stream, s.gray, P + l.g[0].w, P + l.g[0].b, s.s1, Hr, Wr, Hr,
                        Wr, np0, s.norm, nul, nul, nul);
-    hipLaunchKernelGGL((xf_stem_kernel<4, 8, 8, 2, false, false>), dim3(xf_grid(B * px(1))), dim3(256), 0, stream, s.s1, P + l.w[1], P + l.b[1], s.s2, Hr, Wr,
+    hipLaunchKernelGGL((xf_stem_kernel<4, 8, 8, 2, false, false>), dim3(xf_grid(B * px(1))), dim3(256), 0, stream, s.s1, P + l.g[1].w, P + l.g[1].b, s.s2, Hr, Wr,
                        Hr / 2, Wr / 2, B * px(1), nul, nul, nul, nul);
-    hipLaunchKernelGGL((xf_stem_kernel<8, 8, 8, 1, false, false>), dim3(xf_grid(B * px(1))), dim3(256), 0, stream, s.s2, P + l.w[2], P + l.b[2], s.s3, Hr / 2,
+    hipLaunchKernelGGL((xf_stem_kernel<8, 8, 8, 1, false, false>), dim3(xf_grid(B * px(1))), dim3(256), 0, stream, s.s2, P + l.g[2].w, P + l.g[2].b, s.s3, Hr / 2,
                        Wr / 2, Hr / 2, Wr / 2, B * px(1), nul, nul, nul, nul);
-    hipLaunchKernelGGL((xf_stem_kernel<8, 24, 32, 2, false, true>), dim3(xf_grid(B * px(2))), dim3(256), 0, stream, s.s3, P + l.w[3], P + l.b[3], s.q0, Hr / 2,
+    hipLaunchKernelGGL((xf_stem_kernel<8, 24, 32, 2, false, true>), dim3(xf_grid(B * px(2))), dim3(256), 0, stream, s.s3, P + l.g[3].w, P + l.g[3].b, s.q0, Hr / 2,
                        Wr / 2, Hr / 4, Wr / 4, B * px(2), s.norm, s.gray, P + l.skw, P + l.skb);
     IMCUI_CHECK_LAUNCH(h);
     // ---- block2 .. block5
-    XFRUN(layer(4, s.q0, 2, s.q1, 32));
-    XFRUN(layer(5, s.q1, 2, s.q2, 32));
-    XFRUN(layer(6, s.q2, 2, s.e0, 64));
-    XFRUN(layer(7, s.e0, 3, s.e1, 64));
-    XFRUN(layer(8, s.e1, 3, s.e0, 64));  // x3 = e0
-    XFRUN(layer(9, s.e0, 3, s.x4a, 64));
-    XFRUN(layer(10, s.x4a, 4, s.x4b, 64));
-    XFRUN(layer(11, s.x4b, 4, s.x4a, 64));  // x4 = x4a
-    XFRUN(layer(12, s.x4a, 4, s.x5a, 128));
-    XFRUN(layer(13, s.x5a, 5, s.x5b, 128));
-    XFRUN(layer(14, s.x5b, 5, s.x5a, 128));
-    XFRUN(layer(15, s.x5a, 5, s.x5c, 64));  // x5 = x5c
+    IMCUI_RUN(layer(4, s.q0, 2, s.q1, 32));
+    IMCUI_RUN(layer(5, s.q1, 2, s.q2, 32));
+    IMCUI_RUN(layer(6, s.q2, 2, s.e0, 64));
+    IMCUI_RUN(layer(7, s.e0, 3, s.e1, 64));
+    IMCUI_RUN(layer(8, s.e1, 3, s.e0, 64));  // x3 = e0
+    IMCUI_RUN(layer(9, s.e0, 3, s.x4a, 64));
+    IMCUI_RUN(layer(10, s.x4a, 4, s.x4b, 64));
+    IMCUI_RUN(layer(11, s.x4b, 4, s.x4a, 64));  // x4 = x4a
+    IMCUI_RUN(layer(12, s.x4a, 4, s.x5a, 128));
+    IMCUI_RUN(layer(13, s.x5a, 5, s.x5b, 128));
+    IMCUI_RUN(layer(14, s.x5b, 5, s.x5a, 128));
+    IMCUI_RUN(layer(15, s.x5a, 5, s.x5c, 64));  // x5 = x5c
     // ---- fusion, heads
     const int h8 = Hr / 8, w8 = Wr / 8;
     const long np3 = (long)B * px(3);
     hipLaunchKernelGGL(xf_fuse_kernel, dim3(xf_grid(np3 * 16)), dim3(256), 0, stream, s.e0, s.x4a, s.x5c, s.e1, h8, w8, np3 * 16);
     IMCUI_CHECK_LAUNCH(h);
-    XFRUN(layer(16, s.e1, 3, s.e2, 64));
-    XFRUN(layer(17, s.e2, 3, s.e1, 64));
-    XFRUN(layer(18, s.e1, 3, s.e3, 64));  // feats = e3
-    XFRUN(layer(19, s.e3, 3, s.e1, 64));
-    XFRUN(layer(20, s.e1, 3, s.e2, 64));
+    IMCUI_RUN(layer(16, s.e1, 3, s.e2, 64));
+    IMCUI_RUN(layer(17, s.e2, 3, s.e1, 64));
+    IMCUI_RUN(layer(18, s.e1, 3, s.e3, 64));  // feats = e3
+    IMCUI_RUN(layer(19, s.e3, 3, s.e1, 64));
+    IMCUI_RUN(layer(20, s.e1, 3, s.e2, 64));
     float* m1 = feats_norm ? feats_norm : s.m1;
     float* rel = reliability ? reliability : s.rel;
     float* k1h = kpt_heat ? kpt_heat : s.k1h;
-    hipLaunchKernelGGL(xf_heads_kernel, dim3((unsigned)((np3 + 3) / 4)), dim3(256), 0, stream, s.e3, s.e2, P + l.w[XF_L_HEAT], P + l.b[XF_L_HEAT], m1, rel,
+    hipLaunchKernelGGL(xf_heads_kernel, dim3((unsigned)((np3 + 3) / 4)), dim3(256), 0, stream, s.e3, s.e2, P + l.g[XF_L_HEAT].w, P + l.g[XF_L_HEAT].b, m1, rel,
                        np3);
     hipLaunchKernelGGL(xf_unfold_kernel, dim3(xf_grid(np3 * 16)), dim3(256), 0, stream, s.gray, s.norm, s.e0, h8, w8, np3 * 16);
     IMCUI_CHECK_LAUNCH(h);
-    XFRUN(layer(22, s.e0, 3, s.e1, 64));
-    XFRUN(layer(23, s.e1, 3, s.e2, 64));
-    XFRUN(layer(24, s.e2, 3, s.e1, 64));
-    XFRUN(layer(25, s.e1, 3, s.logits, 65));
+    IMCUI_RUN(layer(22, s.e0, 3, s.e1, 64));
+    IMCUI_RUN(layer(23, s.e1, 3, s.e2, 64));
+    IMCUI_RUN(layer(24, s.e2, 3, s.e1, 64));
+    IMCUI_RUN(layer(25, s.e1, 3, s.logits, 65));
     hipLaunchKernelGGL(xf_softmax_kernel, dim3((unsigned)((np3 + 3) / 4)), dim3(256), 0, stream, s.logits, k1h, h8, w8, np3);
     IMCUI_CHECK_LAUNCH(h);
     // ---- selection
@@ -798,7 +765,6 @@ extern "C" int imcui_hip_xfeat_forward(imcui_hip_t* h, const float* packed, cons
                        num_keypoints, st);
     hipLaunchKernelGGL(xf_desc_kernel, dim3(min(cdiv(ccap, 4), 1024), B), dim3(256), 0, stream, m1, s.cidx, s.crank, s.ncand, ccap, kcap, Hr, Wr, descriptors);
     IMCUI_CHECK_LAUNCH(h);
-#undef XFRUN
     return IMCUI_OK;
 }
 

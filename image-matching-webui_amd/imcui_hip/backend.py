@@ -82,6 +82,44 @@ def _pad_rows(t: torch.Tensor, n: int, device: torch.device) -> torch.Tensor:
     return o
 
 
+def _pack_named(kind: str, layout_name: str, names: list, shapes: dict, state_dict: dict, n_floats: int, pack_call, *lead) -> torch.Tensor:
+    """The strict packer of a network whose library entry takes its tensors by name order: `state_dict` (already without the keys the
+    caller ignores) must hold exactly `names`, each with its shape in `shapes`; `pack_call(*lead, tensor pointers, packed)` fills the
+    float32 buffer (host) that is returned."""
+    missing = [n for n in names if n not in state_dict]
+    extra = sorted(set(state_dict) - set(names))
+    if missing or extra:
+        raise ImcuiHipError(f"{kind} state dict does not match {layout_name} layout: missing {missing[:4]}, unexpected {extra[:4]}")
+    arrs = []
+    for n in names:
+        a = _as_f32_host(state_dict[n])
+        if a.shape != shapes[n]:
+            raise ImcuiHipError(f"{kind} state dict: '{n}' has shape {a.shape}, expected {shapes[n]}")
+        arrs.append(a)
+    packed = np.zeros(n_floats, dtype=np.float32)
+    tp = (C.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
+    rc = pack_call(*lead, tp, packed.ctypes.data)
+    if rc != 0:
+        raise ImcuiHipError(f"{pack_call.__name__} failed ({rc})")
+    return torch.from_numpy(packed)
+
+
+def _same_device(packed: torch.Tensor, image: torch.Tensor) -> None:
+    if packed.device != image.device:
+        raise ImcuiHipError("packed weights and image live on different devices")
+
+
+def _sparse_outputs(B: int, kcap: int, dim: int, dev: torch.device):
+    """The fixed-stride outputs of an extractor, uninitialised: keypoints [B,kcap,2], scores [B,kcap], descriptors [B,kcap,dim],
+    num_keypoints [B] int32, status [1] int32, and the dict that returns them."""
+    kpts = torch.empty((B, kcap, 2), dtype=torch.float32, device=dev)
+    scores = torch.empty((B, kcap), dtype=torch.float32, device=dev)
+    desc = torch.empty((B, kcap, dim), dtype=torch.float32, device=dev)
+    nk = torch.empty((B,), dtype=torch.int32, device=dev)
+    status = torch.empty((1,), dtype=torch.int32, device=dev)
+    return kpts, scores, desc, nk, status, {"keypoints": kpts, "scores": scores, "descriptors": desc, "num_keypoints": nk, "status": status}
+
+
 _owner = threading.local()
 
 
@@ -169,8 +207,7 @@ class SuperPointHIP:
         `kcap` was too small, which only max_keypoints = -1 with exactly tied scores can cause) -- callers that
         read `num_keypoints` on the host anyway (the ragged plugin path) read it in the same copy."""
         hd = get_handle(image.device)
-        if packed.device != image.device:
-            raise ImcuiHipError("packed weights and image live on different devices")
+        _same_device(packed, image)
         lib = hd.lib
         image = image.contiguous().float()
         B, Cc, H, W = image.shape
@@ -183,11 +220,7 @@ class SuperPointHIP:
         if kcap is None:
             kcap = lib.imcui_hip_superpoint_max_keypoints_bound(H, W, nms) if maxk < 0 else max(1, min(maxk, H * W))
         dev = image.device
-        kpts = torch.empty((B, kcap, 2), dtype=torch.float32, device=dev)
-        scores = torch.empty((B, kcap), dtype=torch.float32, device=dev)
-        desc = torch.empty((B, kcap, 256), dtype=torch.float32, device=dev)
-        nk = torch.empty((B,), dtype=torch.int32, device=dev)
-        status = torch.empty((1,), dtype=torch.int32, device=dev)
+        kpts, scores, desc, nk, status, out = _sparse_outputs(B, kcap, 256, dev)
         smap = torch.empty((B, H, W), dtype=torch.float32, device=dev) if want_score_map else None
         with self._ws.use(lib.imcui_hip_superpoint_workspace_bytes(B, H, W, nms), dev) as ws:
             hd.launch(
@@ -195,7 +228,6 @@ class SuperPointHIP:
                 int(conf["remove_borders"]), maxk, int(bool(conf.get("fix_sampling", False))), kcap,
                 _ptr(kpts), _ptr(scores), _ptr(desc), _ptr(nk), _ptr(status), _ptr(smap), _ptr(ws), ws.numel(),
             )  # fmt: skip
-        out = {"keypoints": kpts, "scores": scores, "descriptors": desc, "num_keypoints": nk, "status": status}
         if want_score_map:
             out["score_map"] = smap
         return out
@@ -225,24 +257,8 @@ def pack_disk(state_dict: dict) -> torch.Tensor:
     """kornia DISK state dict (the `["extractor"]` entry of a cvlab-epfl/disk checkpoint) -> packed float32 buffer (host).
     Strict: every key consumed exactly once, every shape checked."""
     lib = load_library()
-    names = disk_tensor_names()
-    shapes = disk_tensor_shapes()
-    missing = [n for n in names if n not in state_dict]
-    extra = sorted(set(state_dict) - set(names))
-    if missing or extra:
-        raise ImcuiHipError(f"DISK state dict does not match kornia's layout: missing {missing[:4]}, unexpected {extra[:4]}")
-    arrs = []
-    for n in names:
-        a = _as_f32_host(state_dict[n])
-        if a.shape != shapes[n]:
-            raise ImcuiHipError(f"DISK state dict: '{n}' has shape {a.shape}, expected {shapes[n]}")
-        arrs.append(a)
-    packed = np.zeros(lib.imcui_hip_disk_packed_floats(), dtype=np.float32)
-    tp = (C.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
-    rc = lib.imcui_hip_disk_pack_weights(tp, packed.ctypes.data)
-    if rc != 0:
-        raise ImcuiHipError(f"imcui_hip_disk_pack_weights failed ({rc})")
-    return torch.from_numpy(packed)
+    return _pack_named("DISK", "kornia's", disk_tensor_names(), disk_tensor_shapes(), state_dict, lib.imcui_hip_disk_packed_floats(),
+                       lib.imcui_hip_disk_pack_weights)
 
 
 def disk_check_args(image_shape, window: int, pad_if_not_divisible: bool) -> None:
@@ -267,8 +283,7 @@ class DiskHIP:
         window, pad = int(conf["nms_window_size"]), bool(conf["pad_if_not_divisible"])
         disk_check_args(tuple(image.shape), window, pad)
         hd = get_handle(image.device)
-        if packed.device != image.device:
-            raise ImcuiHipError("packed weights and image live on different devices")
+        _same_device(packed, image)
         lib = hd.lib
         image = image.contiguous().float()
         B, _, H, W = image.shape
@@ -278,18 +293,13 @@ class DiskHIP:
         if kcap is None:
             kcap = bound if maxk < 0 else max(1, min(maxk, bound))
         dev = image.device
-        kpts = torch.empty((B, kcap, 2), dtype=torch.float32, device=dev)
-        scores = torch.empty((B, kcap), dtype=torch.float32, device=dev)
-        desc = torch.empty((B, kcap, 128), dtype=torch.float32, device=dev)
-        nk = torch.empty((B,), dtype=torch.int32, device=dev)
-        status = torch.empty((1,), dtype=torch.int32, device=dev)
+        kpts, scores, desc, nk, status, out = _sparse_outputs(B, kcap, 128, dev)
         heat = torch.empty((B, H, W), dtype=torch.float32, device=dev) if want_heatmap else None
         with self._ws.use(lib.imcui_hip_disk_workspace_bytes(B, H, W), dev) as ws:
             hd.launch(
                 lib.imcui_hip_disk_forward, _ptr(packed), _ptr(image), B, H, W, int(pad), window, float(conf["detection_threshold"]), maxk, kcap,
                 _ptr(kpts), _ptr(scores), _ptr(desc), _ptr(nk), _ptr(status), _ptr(heat), _ptr(ws), ws.numel(),
             )  # fmt: skip
-        out = {"keypoints": kpts, "scores": scores, "descriptors": desc, "num_keypoints": nk, "status": status}
         if want_heatmap:
             out["heatmap"] = heat
         return out
@@ -333,25 +343,9 @@ def pack_xfeat(state_dict: dict) -> torch.Tensor:
     convolutions by the packer.  `fine_matcher.*` (the semi-dense refinement MLP) and the `num_batches_tracked` counters are accepted
     and ignored; every other key is consumed exactly once and every shape checked."""
     lib = load_library()
-    names = xfeat_tensor_names()
-    shapes = xfeat_tensor_shapes()
     own = {k: v for k, v in state_dict.items() if not k.startswith("fine_matcher.") and not k.endswith("num_batches_tracked")}
-    missing = [n for n in names if n not in own]
-    extra = sorted(set(own) - set(names))
-    if missing or extra:
-        raise ImcuiHipError(f"XFeat state dict does not match upstream's layout: missing {missing[:4]}, unexpected {extra[:4]}")
-    arrs = []
-    for n in names:
-        a = _as_f32_host(own[n])
-        if a.shape != shapes[n]:
-            raise ImcuiHipError(f"XFeat state dict: '{n}' has shape {a.shape}, expected {shapes[n]}")
-        arrs.append(a)
-    packed = np.zeros(lib.imcui_hip_xfeat_packed_floats(), dtype=np.float32)
-    tp = (C.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
-    rc = lib.imcui_hip_xfeat_pack_weights(tp, packed.ctypes.data)
-    if rc != 0:
-        raise ImcuiHipError(f"imcui_hip_xfeat_pack_weights failed ({rc})")
-    return torch.from_numpy(packed)
+    return _pack_named("XFeat", "upstream's", xfeat_tensor_names(), xfeat_tensor_shapes(), own, lib.imcui_hip_xfeat_packed_floats(),
+                       lib.imcui_hip_xfeat_pack_weights)
 
 
 def xfeat_check_args(image_shape) -> None:
@@ -374,8 +368,7 @@ class XFeatHIP:
         `[:top_k]` per image (-1 drops the lowest score); K = the NMS bound, cut to max_keypoints when that is not negative."""
         xfeat_check_args(tuple(image.shape))
         hd = get_handle(image.device)
-        if packed.device != image.device:
-            raise ImcuiHipError("packed weights and image live on different devices")
+        _same_device(packed, image)
         lib = hd.lib
         image = image.contiguous().float()
         B, Cc, H, W = image.shape
@@ -385,11 +378,7 @@ class XFeatHIP:
             kcap = bound if top_k < 0 else max(1, min(top_k, bound))
         dev = image.device
         Hr, Wr = H // 32 * 32, W // 32 * 32
-        kpts = torch.empty((B, kcap, 2), dtype=torch.float32, device=dev)
-        scores = torch.empty((B, kcap), dtype=torch.float32, device=dev)
-        desc = torch.empty((B, kcap, 64), dtype=torch.float32, device=dev)
-        nk = torch.empty((B,), dtype=torch.int32, device=dev)
-        status = torch.empty((1,), dtype=torch.int32, device=dev)
+        kpts, scores, desc, nk, status, out = _sparse_outputs(B, kcap, 64, dev)
         heat = torch.empty((B, Hr, Wr), dtype=torch.float32, device=dev) if want_dense else None
         rel = torch.empty((B, Hr // 8, Wr // 8), dtype=torch.float32, device=dev) if want_dense else None
         m1 = torch.empty((B, Hr // 8, Wr // 8, 64), dtype=torch.float32, device=dev) if want_dense else None
@@ -398,7 +387,6 @@ class XFeatHIP:
                 lib.imcui_hip_xfeat_forward, _ptr(packed), _ptr(image), B, Cc, H, W, float(threshold), top_k, kcap,
                 _ptr(kpts), _ptr(scores), _ptr(desc), _ptr(nk), _ptr(status), _ptr(heat), _ptr(rel), _ptr(m1), _ptr(ws), ws.numel(),
             )  # fmt: skip
-        out = {"keypoints": kpts, "scores": scores, "descriptors": desc, "num_keypoints": nk, "status": status}
         if want_dense:
             out.update(kpt_heat=heat, reliability=rel, feats_norm=m1)
         return out
@@ -468,25 +456,9 @@ def pack_aliked(state_dict: dict, model_name: str = "aliked-n16") -> torch.Tenso
     Strict: `num_batches_tracked` counters are ignored, every other key is consumed exactly once, every shape checked."""
     aliked_check_model(model_name)
     lib = load_library()
-    names = aliked_tensor_names()
-    shapes = aliked_tensor_shapes()
     sd = {k: v for k, v in state_dict.items() if not k.endswith("num_batches_tracked")}
-    missing = [n for n in names if n not in sd]
-    extra = sorted(set(sd) - set(names))
-    if missing or extra:
-        raise ImcuiHipError(f"ALIKED state dict does not match upstream's {model_name} layout: missing {missing[:4]}, unexpected {extra[:4]}")
-    arrs = []
-    for n in names:
-        a = _as_f32_host(sd[n])
-        if a.shape != shapes[n]:
-            raise ImcuiHipError(f"ALIKED state dict: '{n}' has shape {a.shape}, expected {shapes[n]}")
-        arrs.append(a)
-    packed = np.zeros(lib.imcui_hip_aliked_packed_floats(), dtype=np.float32)
-    tp = (C.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
-    rc = lib.imcui_hip_aliked_pack_weights(tp, packed.ctypes.data)
-    if rc != 0:
-        raise ImcuiHipError(f"imcui_hip_aliked_pack_weights failed ({rc})")
-    return torch.from_numpy(packed)
+    return _pack_named("ALIKED", f"upstream's {model_name}", aliked_tensor_names(), aliked_tensor_shapes(), sd, lib.imcui_hip_aliked_packed_floats(),
+                       lib.imcui_hip_aliked_pack_weights)
 
 
 def aliked_check_args(image_shape, nms_radius: int) -> None:
@@ -513,8 +485,7 @@ class AlikedHIP:
         r = int(conf["nms_radius"])
         aliked_check_args(tuple(image.shape), r)
         hd = get_handle(image.device)
-        if packed.device != image.device:
-            raise ImcuiHipError("packed weights and image live on different devices")
+        _same_device(packed, image)
         lib = hd.lib
         image = image.contiguous().float()
         B, _, H, W = image.shape
@@ -524,11 +495,7 @@ class AlikedHIP:
             kcap = max(1, min(limit, lib.imcui_hip_aliked_max_keypoints_bound(H, W, r)))
         dev = image.device
         f32 = dict(dtype=torch.float32, device=dev)
-        kpts = torch.empty((B, kcap, 2), **f32)
-        scores = torch.empty((B, kcap), **f32)
-        desc = torch.empty((B, kcap, 128), **f32)
-        nk = torch.empty((B,), dtype=torch.int32, device=dev)
-        status = torch.empty((1,), dtype=torch.int32, device=dev)
+        kpts, scores, desc, nk, status, out = _sparse_outputs(B, kcap, 128, dev)
         Hp, Wp = (H + 31) // 32 * 32, (W + 31) // 32 * 32
         smap = torch.empty((B, H, W), **f32) if want_maps else None
         kn = torch.empty((B, kcap, 2), **f32) if want_maps else None
@@ -539,7 +506,6 @@ class AlikedHIP:
                 lib.imcui_hip_aliked_forward, _ptr(packed), _ptr(image), B, H, W, r, float(conf["detection_threshold"]), maxk, kcap,
                 _ptr(kpts), _ptr(scores), _ptr(desc), _ptr(nk), _ptr(status), _ptr(smap), _ptr(kn), _ptr(x3), _ptr(x4), _ptr(ws), ws.numel(),
             )  # fmt: skip
-        out = {"keypoints": kpts, "scores": scores, "descriptors": desc, "num_keypoints": nk, "status": status}
         if want_maps:
             out.update(score_map=smap, keypoints_norm=kn, x3=x3, x4=x4)
         return out
@@ -589,24 +555,9 @@ def pack_alike(state_dict: dict, model_name: str = "alike-t") -> torch.Tensor:
     Strict: `num_batches_tracked` counters are ignored, every other key is consumed exactly once, every shape checked."""
     v = alike_check_model(model_name)
     lib = load_library()
-    names, shapes = alike_tensor_names(model_name), alike_tensor_shapes(model_name)
     sd = {k: t for k, t in state_dict.items() if not k.endswith("num_batches_tracked")}
-    missing = [n for n in names if n not in sd]
-    extra = sorted(set(sd) - set(names))
-    if missing or extra:
-        raise ImcuiHipError(f"ALIKE state dict does not match upstream's {model_name} layout: missing {missing[:4]}, unexpected {extra[:4]}")
-    arrs = []
-    for n in names:
-        a = _as_f32_host(sd[n])
-        if a.shape != shapes[n]:
-            raise ImcuiHipError(f"ALIKE state dict: '{n}' has shape {a.shape}, expected {shapes[n]}")
-        arrs.append(a)
-    packed = np.zeros(lib.imcui_hip_alike_packed_floats(v), dtype=np.float32)
-    tp = (C.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
-    rc = lib.imcui_hip_alike_pack_weights(v, tp, packed.ctypes.data)
-    if rc != 0:
-        raise ImcuiHipError(f"imcui_hip_alike_pack_weights failed ({rc})")
-    return torch.from_numpy(packed)
+    return _pack_named("ALIKE", f"upstream's {model_name}", alike_tensor_names(model_name), alike_tensor_shapes(model_name), sd,
+                       lib.imcui_hip_alike_packed_floats(v), lib.imcui_hip_alike_pack_weights, v)
 
 
 def alike_check_args(image_shape, model_name: str = "alike-t") -> None:
@@ -632,8 +583,7 @@ class AlikeHIP:
         f2 / f3 / f4 [B,Hp/2^s,Wp/2^s,dim/4].  K = min(top_k, n_limit, the NMS bound)."""
         alike_check_args(tuple(image.shape), self.model_name)
         hd = get_handle(image.device)
-        if packed.device != image.device:
-            raise ImcuiHipError("packed weights and image live on different devices")
+        _same_device(packed, image)
         lib, v = hd.lib, self.variant
         image = image.contiguous().float()
         B, _, H, W = image.shape
@@ -647,11 +597,7 @@ class AlikeHIP:
         kcap = max(1, min(int(kcap), H * W))
         dev = image.device
         f32 = dict(dtype=torch.float32, device=dev)
-        kpts = torch.empty((B, kcap, 2), **f32)
-        scores = torch.empty((B, kcap), **f32)
-        desc = torch.empty((B, kcap, dim), **f32)
-        nk = torch.empty((B,), dtype=torch.int32, device=dev)
-        status = torch.empty((1,), dtype=torch.int32, device=dev)
+        kpts, scores, desc, nk, status, out = _sparse_outputs(B, kcap, dim, dev)
         Hp, Wp = (H + 31) // 32 * 32, (W + 31) // 32 * 32
         maps = {}
         if want_maps:
@@ -665,7 +611,6 @@ class AlikeHIP:
                 int(bool(conf.get("sub_pixel", False))), kcap, _ptr(kpts), _ptr(scores), _ptr(desc), _ptr(nk), _ptr(status), _ptr(maps.get("score_map")),
                 _ptr(maps.get("x4")), _ptr(maps.get("f2")), _ptr(maps.get("f3")), _ptr(maps.get("f4")), _ptr(ws), ws.numel(),
             )  # fmt: skip
-        out = {"keypoints": kpts, "scores": scores, "descriptors": desc, "num_keypoints": nk, "status": status}
         out.update(maps)
         return out
 
