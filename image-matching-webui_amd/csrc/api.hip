@@ -277,6 +277,7 @@ extern "C" int imcui_hip_gemm_probe_f32(imcui_hip_t* h, const imcui_hip_gemm_des
     g.ln_stats = d->ln_stats;
     g.ln_rowsum = d->ln_rowsum;
     g.ln_stride = d->ln_stride;
+    g.conv_dil = d->conv_dil;
     return gemm_launch(h, g, (hipStream_t)stream);
 }
 extern "C" int imcui_hip_gemm_last_route(const imcui_hip_t* h) { return h ? h->gemm_last_route : -1; }

@@ -176,7 +176,7 @@ enum {
     OPT_NCNT
 };
 
-#define IMCUI_GEMM_ROUTE_SLOTS 320  // GEMM_ROUTE(kind, epi) < 20 x 16 (gemm.h)
+#define IMCUI_GEMM_ROUTE_SLOTS 384  // GEMM_ROUTE(kind, epi) < 24 x 16 (gemm.h)
 #define IMCUI_ATTN_ROUTE_SLOTS 16   // ATTN_ROUTE(kind, split) < 8 x 2 (attention.h)
 #define IMCUI_CONV_ROUTE_SLOTS 16   // CONV_ROUTE(kind) < 16 (conv.h)
 

@@ -104,6 +104,10 @@ struct GemmP {
     const float* ln_stats = nullptr;
     const float* ln_rowsum = nullptr;
     long ln_stride = 0;
+    // implicit im2col with dilated taps (conv_k > 0): tap (ky, kx) reads input pixel (oy stride - pad + ky conv_dil, ox stride - pad +
+    // kx conv_dil).  0 / 1 = no dilation: the launch is the undilated one, instantiation and bits.  > 1 selects the ASRC = 2
+    // instantiations (GR_EXACT_DIL / GR_CONVD_*); the single-product arithmetic is not built for them
+    int conv_dil = 0;
 };
 
 // Route of a launch: which kernel instantiation gemm_launch chose, GEMM_ROUTE(kind, epilogue).  The launch sites store it in the
@@ -128,7 +132,11 @@ enum GemmRouteKind {
     GR_WREG_PIPE_SINGLE = 15,    // gemm_wreg_kernel<EPI_CONV, true, true, 4>
     GR_WREG_MT2 = 16,        // gemm_wreg_kernel<EPI, false, true, 2>
     GR_WREG_MT1 = 17,        // gemm_wreg_kernel<EPI, false, true, 1>
-    GR_NKIND = 18
+    GR_EXACT_DIL = 18,       // gemm_kernel<EPI_CONV, true>: dilated taps (GemmP.conv_dil > 1)
+    GR_CONVD_F32B = 19,      // gemm_split_kernel<EPI_CONV, 2, false, 2>
+    GR_CONVD_128 = 20,       // gemm_split_kernel<EPI_CONV, 2, true, 2>
+    GR_CONVD_256 = 21,       // gemm_split_kernel<EPI_CONV, 2, true, 4>
+    GR_NKIND = 22
 };
 #define GEMM_ROUTE(kind, epi) ((kind) * 16 + (epi))
 static_assert(GR_NKIND * 16 <= IMCUI_GEMM_ROUTE_SLOTS, "route table of imcui_hip_s too small");

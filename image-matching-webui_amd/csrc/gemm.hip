@@ -163,7 +163,8 @@ __device__ __forceinline__ void gemm_epilogue(const GemmP& p, const TileCtx& c, 
 }
 
 // Source of `n` consecutive K elements starting at k for GEMM row `ar` (nullptr = zeros):
-// plain / concatenated matrix, or implicit im2col of an NHWC convolution.
+// plain / concatenated matrix, or implicit im2col of an NHWC convolution (DIL: taps conv_dil pixels apart).
+template <bool DIL>
 __device__ __forceinline__ const float* gemm_a_src(const GemmP& p, const float* A, const float* A2, int ar, int k) {
     if (p.conv_k > 0) {
         const int tap = k / p.conv_cin, c0 = k - tap * p.conv_cin;
@@ -171,7 +172,8 @@ __device__ __forceinline__ const float* gemm_a_src(const GemmP& p, const float* 
         const int ox = ar % p.conv_wout;
         const int t = ar / p.conv_wout;
         const int oy = t % p.conv_hout, b = t / p.conv_hout;
-        const int iy = oy * p.conv_stride - p.conv_pad + ky, ix = ox * p.conv_stride - p.conv_pad + kx;
+        const int dy = DIL ? ky * p.conv_dil : ky, dx = DIL ? kx * p.conv_dil : kx;
+        const int iy = oy * p.conv_stride - p.conv_pad + dy, ix = ox * p.conv_stride - p.conv_pad + dx;
         if (iy < 0 || iy >= p.conv_hin || ix < 0 || ix >= p.conv_win) return nullptr;
         return A + (((size_t)b * p.conv_hin + iy) * p.conv_win + ix) * p.conv_cin + c0;
     }
@@ -181,7 +183,7 @@ __device__ __forceinline__ const float* gemm_a_src(const GemmP& p, const float* 
 
 // ------------------------------------------------------------------ exact f32 kernel
 #define BK32 32
-template <int EPI>
+template <int EPI, bool DIL = false>
 __global__ __launch_bounds__(256) void gemm_kernel(GemmP p) {
     __shared__ float4 As[(BK32 / 4) * LDS_ROWS];
     __shared__ float4 Bs[(BK32 / 4) * LDS_ROWS];
@@ -217,7 +219,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmP p) {
         const int r = s_r + 32 * it;                                                 \
         const int ar = min(c.row0 + r, c.M - 1);                                     \
         const int br = min(c.col0 + r, c.N - 1);                                     \
-        const float* src = gemm_a_src(p, A, A2, ar, k);                                  \
+        const float* src = gemm_a_src<DIL>(p, A, A2, ar, k);                                  \
         ra##it = src ? *reinterpret_cast<const float4*>(src) : make_float4(0.f, 0.f, 0.f, 0.f); \
         rb##it = *reinterpret_cast<const float4*>(W + (size_t)br * p.ldw + k);       \
     }
@@ -693,7 +695,8 @@ __device__ __forceinline__ void gemm_epilogue_staged(const GemmP& p, const TileC
 //    (both the ds_write_b128 of 8 lanes = 2 rows x 4 octets and the fragment ds_read_b128 are then
 //    conflict-free).
 #define BK3 32
-// ASRC: 0 = matrix (optionally two K slabs), 1 = implicit im2col of an NHWC image
+// ASRC: 0 = matrix (optionally two K slabs), 1 = implicit im2col of an NHWC image, 2 = the same with dilated taps (tap (ky, kx) at
+//       (ky, kx) x conv_dil pixels; an instantiation of its own, so every ASRC = 1 launch compiles from the code it always had)
 // WDMA: weights are pre-split fragment-major planes; otherwise B is an f32 matrix [N][K] (activations,
 //       e.g. similarity products) staged like A
 // NW:   32-column fragments per wave: 2 -> tile 128 x 128 (three workgroups per CU), 4 -> tile 128 x 256 (two per
@@ -723,6 +726,7 @@ __global__ __launch_bounds__(256, (WDMA && NW == 2) ? 3 : 2) void gemm_split_ker
     const float* A2 = p.A2 ? p.A2 + (size_t)c.z * p.a2_bs : nullptr;
     const float wsc = (WDMA && p.wscale) ? p.wscale[c.wsel] : 1.0f;
     const int nkt = p.K / BK3;
+    constexpr bool CONV = ASRC != 0;
 
     f32x16 acc[2][NW];
 #pragma unroll
@@ -741,7 +745,7 @@ __global__ __launch_bounds__(256, (WDMA && NW == 2) ? 3 : 2) void gemm_split_ker
     const int ar0 = min(c.row0 + rl0, c.M - 1), ar1 = min(c.row0 + rl1, c.M - 1);
     const float *pa0, *pa1, *pb0 = nullptr, *pb1 = nullptr;
     int iy0 = 0, ix0 = 0, iy1 = 0, ix1 = 0;  // conv: top-left input pixel of the two rows
-    if (ASRC == 1) {
+    if (CONV) {
         const int ox0 = ar0 % p.conv_wout, t0 = ar0 / p.conv_wout, ox1 = ar1 % p.conv_wout, t1 = ar1 / p.conv_wout;
         const int oy0 = t0 % p.conv_hout, b0 = t0 / p.conv_hout, oy1 = t1 % p.conv_hout, b1 = t1 / p.conv_hout;
         iy0 = oy0 * p.conv_stride - p.conv_pad;
@@ -764,10 +768,11 @@ __global__ __launch_bounds__(256, (WDMA && NW == 2) ? 3 : 2) void gemm_split_ker
     // tiles are requested strictly in order kt = 0, 1, 2, ...
     auto issue_a = [&](int kt, f32x4& a0, f32x4& b0, f32x4& a1, f32x4& b1, bool& v0, bool& v1) __attribute__((always_inline)) {
         const float *q0, *q1;
-        if (ASRC == 1) {
-            const int off = (cv_ky * p.conv_win + cv_kx) * p.conv_cin + cv_c0;
-            v0 = (unsigned)(iy0 + cv_ky) < (unsigned)p.conv_hin && (unsigned)(ix0 + cv_kx) < (unsigned)p.conv_win;
-            v1 = (unsigned)(iy1 + cv_ky) < (unsigned)p.conv_hin && (unsigned)(ix1 + cv_kx) < (unsigned)p.conv_win;
+        if (CONV) {
+            const int dy = ASRC == 2 ? cv_ky * p.conv_dil : cv_ky, dx = ASRC == 2 ? cv_kx * p.conv_dil : cv_kx;  // pixel offset of the tap
+            const int off = (dy * p.conv_win + dx) * p.conv_cin + cv_c0;
+            v0 = (unsigned)(iy0 + dy) < (unsigned)p.conv_hin && (unsigned)(ix0 + dx) < (unsigned)p.conv_win;
+            v1 = (unsigned)(iy1 + dy) < (unsigned)p.conv_hin && (unsigned)(ix1 + dx) < (unsigned)p.conv_win;
             q0 = v0 ? pa0 + off : A;
             q1 = v1 ? pa1 + off : A;
             cv_c0 += BK3;
@@ -796,13 +801,13 @@ __global__ __launch_bounds__(256, (WDMA && NW == 2) ? 3 : 2) void gemm_split_ker
     auto store_a = [&](f32x4& a0, f32x4& b0, f32x4& a1, f32x4& b1, bool v0, bool v1) __attribute__((always_inline)) {
         uint4 h, l;
         float4 fa = __builtin_bit_cast(float4, a0), fb = __builtin_bit_cast(float4, b0);
-        if (ASRC == 1 && !v0) fa = fb = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (CONV && !v0) fa = fb = make_float4(0.f, 0.f, 0.f, 0.f);
         if constexpr (SINGLE) {  // one product: the nearest f16 of either operand (common.h)
             h = half8_rtn(fa, fb);
             *reinterpret_cast<uint4*>(sm + wo0) = h;
             fa = __builtin_bit_cast(float4, a1);
             fb = __builtin_bit_cast(float4, b1);
-            if (ASRC == 1 && !v1) fa = fb = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (CONV && !v1) fa = fb = make_float4(0.f, 0.f, 0.f, 0.f);
             h = half8_rtn(fa, fb);
             *reinterpret_cast<uint4*>(sm + wo1) = h;
             return;
@@ -812,7 +817,7 @@ __global__ __launch_bounds__(256, (WDMA && NW == 2) ? 3 : 2) void gemm_split_ker
         if constexpr (!SINGLE) *reinterpret_cast<uint4*>(sm + 8192 + wo0) = l;
         fa = __builtin_bit_cast(float4, a1);
         fb = __builtin_bit_cast(float4, b1);
-        if (ASRC == 1 && !v1) fa = fb = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (CONV && !v1) fa = fb = make_float4(0.f, 0.f, 0.f, 0.f);
         split8(fa, fb, h, l);
         *reinterpret_cast<uint4*>(sm + wo1) = h;
         if constexpr (!SINGLE) *reinterpret_cast<uint4*>(sm + 8192 + wo1) = l;
@@ -1096,6 +1101,22 @@ static void launch_one(imcui_hip_s* h, const GemmP& p, bool split, hipStream_t s
 static void launch_conv(imcui_hip_s* h, const GemmP& p, bool split, hipStream_t stream) {
     const bool wide = split && wide_ok(p);
     const dim3 grid(cdiv(p.M, BM) * cdiv(p.N, wide ? 256 : BN), 1, p.batch);
+    if (p.conv_dil > 1) {  // dilated taps: the ASRC = 2 instantiations (gemm_launch has refused `single`)
+        if (!split) {
+            gemm_route_note(h, GR_EXACT_DIL, EPI_CONV);
+            hipLaunchKernelGGL((gemm_kernel<EPI_CONV, true>), grid, dim3(256), 0, stream, p);
+        } else if (wide) {
+            gemm_route_note(h, GR_CONVD_256, EPI_CONV);
+            hipLaunchKernelGGL((gemm_split_kernel<EPI_CONV, 2, true, 4>), grid, dim3(256), 0, stream, p);
+        } else if (p.Wh != nullptr) {
+            gemm_route_note(h, GR_CONVD_128, EPI_CONV);
+            hipLaunchKernelGGL((gemm_split_kernel<EPI_CONV, 2, true, 2>), grid, dim3(256), occupancy_pad((long)grid.x * grid.z), stream, p);
+        } else {
+            gemm_route_note(h, GR_CONVD_F32B, EPI_CONV);
+            hipLaunchKernelGGL((gemm_split_kernel<EPI_CONV, 2, false, 2>), grid, dim3(256), 0, stream, p);
+        }
+        return;
+    }
     if (!split) {
         gemm_route_note(h, GR_EXACT, EPI_CONV);
         hipLaunchKernelGGL(gemm_kernel<EPI_CONV>, grid, dim3(256), 0, stream, p);
@@ -1127,6 +1148,10 @@ int gemm_launch(imcui_hip_s* h, const GemmP& p, hipStream_t stream) {
     if (p.conv_k > 0 && (p.conv_cin % BK32 != 0 || p.K != p.conv_k * p.conv_k * p.conv_cin || p.epi != EPI_CONV || p.A2))
         return imcui_set_err(h, IMCUI_ERR_ARG, "gemm(conv): cin=%d must be a multiple of %d, K=%d == k*k*cin, epilogue EPI_CONV", p.conv_cin,
                              BK32, p.K);
+    if (p.conv_dil < 0 || (p.conv_dil > 1 && p.conv_k == 0))
+        return imcui_set_err(h, IMCUI_ERR_ARG, "gemm: conv_dil=%d needs an implicit-im2col launch (conv_k > 0) and must not be negative", p.conv_dil);
+    if (p.conv_dil > 1 && p.single)
+        return imcui_set_err(h, IMCUI_ERR_UNSUPPORTED, "gemm(conv): the single-product arithmetic is not built for dilated taps (conv_dil=%d)", p.conv_dil);
     const bool split = h->precision == 1;
     if (p.rup_h > 0 && (!split || p.epi != EPI_CONV || p.N % 4 != 0 || p.ldr % 4 != 0 || p.M % (4 * p.rup_h * p.rup_w) != 0))
         return imcui_set_err(h, IMCUI_ERR_ARG, "gemm: the up-sampled residual needs the split mode, EPI_CONV, N %% 4 == 0 and M = images x 4 rup_h rup_w");

@@ -631,6 +631,166 @@ class AlikeHIP:
         return desc
 
 
+# ------------------------------------------------------------------ R2D2
+# (cin, cout, kernel, conv index in upstream's flat `ops` list, BatchNorm behind it): Quad_L2Net_ConfCFS, csrc/r2d2.hip
+R2D2_LAYERS = ((3, 32, 3, 0, True), (32, 32, 3, 3, True), (32, 64, 3, 6, True), (64, 64, 3, 9, True), (64, 128, 3, 12, True),
+               (128, 128, 3, 15, True), (128, 128, 2, 18, True), (128, 128, 2, 20, True), (128, 128, 2, 22, False))  # fmt: skip
+R2D2_NET = "Quad_L2Net_ConfCFS"
+R2D2_MAX_LEVELS = 32
+
+
+def r2d2_tensor_names() -> list[str]:
+    lib = load_library()
+    return [lib.imcui_hip_r2d2_tensor_name(i).decode() for i in range(lib.imcui_hip_r2d2_num_tensors())]
+
+
+def r2d2_tensor_shapes() -> dict:
+    shapes = {}
+    for cin, cout, k, op, bn in R2D2_LAYERS:
+        shapes[f"ops.{op}.weight"] = (cout, cin, k, k)
+        shapes[f"ops.{op}.bias"] = (cout,)
+        if bn:
+            shapes[f"ops.{op + 1}.running_mean"] = (cout,)
+            shapes[f"ops.{op + 1}.running_var"] = (cout,)
+    shapes.update({"clf.weight": (2, 128, 1, 1), "clf.bias": (2,), "sal.weight": (1, 128, 1, 1), "sal.bias": (1,)})
+    return shapes
+
+
+def r2d2_unwrap(checkpoint: dict) -> dict:
+    """Upstream's checkpoint {'net': 'Quad_L2Net_ConfCFS()', 'state_dict': ...} (or a bare state dict) -> state dict without the
+    `module.` prefix.  A 'net' string that names another class (Fast_Quad_L2Net_ConfCFS: faster2d2) is refused by name."""
+    sd = checkpoint
+    if isinstance(checkpoint, dict) and "state_dict" in checkpoint:
+        net = str(checkpoint.get("net", R2D2_NET + "()"))
+        if net.split("(")[0].strip() != R2D2_NET:
+            raise ImcuiHipError(f"R2D2 checkpoint builds '{net}': only {R2D2_NET} (r2d2_WASF_N16 / r2d2_WASF_N8 / r2d2_WAF_N16) is served by the "
+                                "HIP backend; faster2d2 (Fast_Quad_L2Net_ConfCFS) has other layers")  # fmt: skip
+        sd = checkpoint["state_dict"]
+    return {(k[len("module."):] if k.startswith("module.") else k): v for k, v in sd.items()}
+
+
+def pack_r2d2(state_dict: dict) -> torch.Tensor:
+    """R2D2 checkpoint or state dict -> packed float32 buffer (host); the affine-free BatchNorms (eval) are folded into the convolutions.
+    Strict: `num_batches_tracked` counters are ignored, every other key is consumed exactly once, every shape checked."""
+    lib = load_library()
+    sd = {k: t for k, t in r2d2_unwrap(state_dict).items() if not k.endswith("num_batches_tracked")}
+    return _pack_named("R2D2", f"upstream's {R2D2_NET}", r2d2_tensor_names(), r2d2_tensor_shapes(), sd, lib.imcui_hip_r2d2_packed_floats(),
+                       lib.imcui_hip_r2d2_pack_weights)
+
+
+def r2d2_levels(H: int, W: int, scale_f: float = 2**0.25, min_size: int = 256, max_size: int = 1024, min_scale: float = 0, max_scale: float = 1) -> list:
+    """extract_multiscale's schedule (naver/r2d2 extract.py), upstream's own float64 arithmetic and banker's `round`:
+    [(nh, nw, runs)] from the full image down; level l + 1 is interpolated from level l whether or not level l runs."""
+    if max_scale > 1:
+        raise ValueError(f"R2D2: max_scale={max_scale} above 1 (upstream asserts max_scale <= 1: would blur the image)")
+    if not scale_f > 1:
+        raise ValueError(f"R2D2: scale_factor={scale_f} must be above 1")
+    levels = []
+    s = 1.0
+    nh, nw = H, W
+    while s + 0.001 >= max(min_scale, min_size / max(H, W)):
+        levels.append((nh, nw, s - 0.001 <= min(max_scale, max_size / max(H, W))))
+        s /= scale_f
+        nh, nw = round(H * s), round(W * s)
+        if nh < 1 or nw < 1:  # (upstream's interpolate raises on an empty size)
+            break
+    while levels and not levels[-1][2]:  # trailing levels that do not run are never needed
+        levels.pop()
+    return levels
+
+
+def r2d2_check_args(image_shape, conf: dict) -> list:
+    """Refusals raised before anything is launched; returns the level list."""
+    if len(image_shape) != 4 or image_shape[1] != 3:
+        raise ValueError(f"R2D2 expects an RGB image [B,3,H,W], got shape {tuple(image_shape)}")
+    H, W = int(image_shape[2]), int(image_shape[3])
+    lv = r2d2_levels(H, W, conf["scale_factor"], conf["min_size"], conf["max_size"], conf["min_scale"], conf["max_scale"])
+    if len(lv) > R2D2_MAX_LEVELS:
+        raise ValueError(f"R2D2: {len(lv)} pyramid levels for {H}x{W} (at most {R2D2_MAX_LEVELS}: raise scale_factor or min_size)")
+    return lv
+
+
+class R2D2HIP:
+    def __init__(self):
+        self._ws = _Workspace()
+
+    @staticmethod
+    def _arrays(levels):
+        n = len(levels)
+        nh = (C.c_int * n)(*[l[0] for l in levels])
+        nw = (C.c_int * n)(*[l[1] for l in levels])
+        run = (C.c_int * n)(*[int(l[2]) for l in levels])
+        return n, nh, nw, run
+
+    def forward(self, packed: torch.Tensor, image: torch.Tensor, conf: dict, want_maps: bool = False, kcap: int | None = None):
+        """image [B,3,H,W] float32 RGB in [0,1] on the GPU -> fixed-stride outputs, no host synchronisation: keypoints [B,K,2] (pixels of
+        the input image), scores [B,K], descriptors [B,K,128], num_keypoints [B] int32, status [1] int32 (bit 1: more candidates than
+        `kcap`), rows in ascending score order.  K = max_keypoints, or kcap when max_keypoints is 0 (all).  kcap defaults to the bound
+        for maps without exact ties (3x3 maxima are not adjacent); "all" = every pixel of every level that runs.
+        want_maps adds `levels` and per running level reliability / repeatability [B,nh,nw] and the final map [B,nh,nw,128] as lists."""
+        levels = r2d2_check_args(tuple(image.shape), conf)
+        hd = get_handle(image.device)
+        _same_device(packed, image)
+        lib = hd.lib
+        image = image.contiguous().float()
+        B, _, H, W = image.shape
+        dev = image.device
+        running = [l for l in levels if l[2]]
+        npix_run = sum(l[0] * l[1] for l in running)
+        if kcap is None:
+            kcap = sum(((l[0] + 1) // 2) * ((l[1] + 1) // 2) for l in running)
+        elif kcap == "all":
+            kcap = npix_run
+        kcap = max(1, min(int(kcap), npix_run))
+        maxk = int(conf["max_keypoints"] or 0)
+        kout = kcap if maxk <= 0 else min(maxk, kcap)
+        kpts, scores, desc, nk, status, out = _sparse_outputs(B, kout, 128, dev)
+        n, nh, nw, run = self._arrays(levels)
+        maps = {}
+        if want_maps:
+            f32 = dict(dtype=torch.float32, device=dev)
+            maps = dict(rel=torch.empty(B * npix_run, **f32), rep=torch.empty(B * npix_run, **f32), fmap=torch.empty(B * npix_run * 128, **f32))
+        if n == 0 or not running:  # (min_size above the image and max_size below it: upstream returns nothing)
+            for t in (kpts, scores, desc, nk, status):
+                t.zero_()
+            return out
+        with self._ws.use(lib.imcui_hip_r2d2_workspace_bytes(B, n, nh, nw, kcap), dev) as ws:
+            hd.launch(
+                lib.imcui_hip_r2d2_forward, _ptr(packed), _ptr(image), B, H, W, n, nh, nw, run, float(conf["reliability_threshold"]),
+                float(conf["repetability_threshold"]), maxk, kcap, kout, _ptr(kpts), _ptr(scores), _ptr(desc), _ptr(nk), _ptr(status),
+                _ptr(maps.get("rel")), _ptr(maps.get("rep")), _ptr(maps.get("fmap")), _ptr(ws), ws.numel(),
+            )  # fmt: skip
+        if want_maps:
+            out["levels"] = [(l[0], l[1]) for l in running]
+            out["reliability"], out["repeatability"], out["final_map"] = [], [], []
+            off = 0
+            for lh, lw, _ in running:
+                m = B * lh * lw
+                out["reliability"].append(maps["rel"][off : off + m].view(B, lh, lw))
+                out["repeatability"].append(maps["rep"][off : off + m].view(B, lh, lw))
+                out["final_map"].append(maps["fmap"][off * 128 : (off + m) * 128].view(B, lh, lw, 128))
+                off += m
+        return out
+
+    def desc_probe(self, packed: torch.Tensor, image: torch.Tensor, xy: torch.Tensor) -> torch.Tensor:
+        """Test entry: F.normalize of the network's final map at integer pixels xy [n,2] (x, y) of ONE image [1,3,H,W] -> [n,128]."""
+        if image.dim() != 4 or image.shape[1] != 3:
+            raise ValueError(f"R2D2 expects an RGB image [B,3,H,W], got shape {tuple(image.shape)}")
+        hd = get_handle(image.device)
+        lib = hd.lib
+        image = image.contiguous().float()
+        _, _, H, W = image.shape
+        xy = xy.to(device=image.device, dtype=torch.int32).contiguous()
+        n = xy.shape[0]
+        if n == 0 or int(xy[:, 0].min()) < 0 or int(xy[:, 0].max()) >= W or int(xy[:, 1].min()) < 0 or int(xy[:, 1].max()) >= H:
+            raise ValueError("desc_probe: pixels outside the image (or none)")
+        desc = torch.empty((n, 128), dtype=torch.float32, device=image.device)
+        nh, nw = (C.c_int * 1)(H), (C.c_int * 1)(W)
+        with self._ws.use(lib.imcui_hip_r2d2_workspace_bytes(1, 1, nh, nw, 1), image.device) as ws:
+            hd.launch(lib.imcui_hip_r2d2_desc_probe, _ptr(packed), _ptr(image[:1]), H, W, _ptr(xy), n, _ptr(desc), _ptr(ws), ws.numel())
+        return desc
+
+
 # ------------------------------------------------------------------ SIFT
 SIFT_LAYERS = (3, 4, 5)  # nOctaveLayers (the wrapper's `num_octaves`) csrc/sift.hip is written for: blur radius at most 13
 
@@ -1877,7 +2037,8 @@ GEMM_EPI = {"bias": 0, "relu": 1, "resid": 2, "qkv": 3, "cross": 4, "conv": 5, "
 # GemmRouteKind of csrc/gemm.h: a route is 16 kind + epilogue (imcui_hip_gemm_last_route)
 GEMM_ROUTE_KINDS = {"none": 0, "exact": 1, "split_f32b": 2, "split_128": 3, "split_256": 4, "split_128_single": 5, "split_256_single": 6,
                     "conv_f32b": 7, "conv_128": 8, "conv_256": 9, "conv_128_single": 10, "conv_256_single": 11, "wreg_rolled": 12,
-                    "wreg_pipe": 13, "wreg_rolled_single": 14, "wreg_pipe_single": 15, "wreg_mt2": 16, "wreg_mt1": 17}  # fmt: skip
+                    "wreg_pipe": 13, "wreg_rolled_single": 14, "wreg_pipe_single": 15, "wreg_mt2": 16, "wreg_mt1": 17,
+                    "exact_dil": 18, "convd_f32b": 19, "convd_128": 20, "convd_256": 21}  # fmt: skip
 
 
 def gemm_route(kind: str, epi: str) -> int:
@@ -1904,7 +2065,8 @@ class GemmDesc(C.Structure):
                 ("conv_win", C.c_int), ("conv_hout", C.c_int), ("conv_wout", C.c_int), ("conv_cin", C.c_int), ("resid", C.c_void_p),
                 ("ldr", C.c_long), ("rup_h", C.c_int), ("rup_w", C.c_int), ("rup_align", C.c_int), ("act", C.c_int), ("single", C.c_int),
                 ("rope_cos", C.c_void_p), ("rope_sin", C.c_void_p), ("heads", C.c_int), ("role0", C.c_int), ("rope_seq_row0", C.c_void_p),
-                ("ln_stats", C.c_void_p), ("ln_rowsum", C.c_void_p), ("ln_stride", C.c_long)]  # fmt: skip
+                ("ln_stats", C.c_void_p), ("ln_rowsum", C.c_void_p), ("ln_stride", C.c_long),
+                ("conv_dil", C.c_int)]  # fmt: skip
     DEFAULTS = {"batch": 1, "cnt_stride": 1, "conv_stride": 1, "rup_align": 1, "heads": 4, "alpha": 1.0}
 
 

@@ -730,3 +730,36 @@ def xfeat_state_dict(seed: int = 0, logit_gain: float = 0.5, dustbin_bias: float
     sd["fine_matcher.0.weight"] = rn(512, 128, scale=1.0 / math.sqrt(128))
     sd["fine_matcher.0.bias"] = rn(512, scale=0.05)
     return sd
+
+
+# (cin, cout, kernel, conv index in upstream's flat `ops` list, BatchNorm behind it): naver/r2d2 Quad_L2Net_ConfCFS
+R2D2_LAYERS = ((3, 32, 3, 0, True), (32, 32, 3, 3, True), (32, 64, 3, 6, True), (64, 64, 3, 9, True), (64, 128, 3, 12, True),
+               (128, 128, 3, 15, True), (128, 128, 2, 18, True), (128, 128, 2, 20, True), (128, 128, 2, 22, False))  # fmt: skip
+
+
+def r2d2_state_dict(seed: int = 0, clf_gain: float = 0.15, sal_gain: float = 0.1, sal_shift: float = 2.2, checkpoint: bool = False) -> dict:
+    """Seeded R2D2 weights (Quad_L2Net_ConfCFS, upstream's key names: `ops.N` of the flat ModuleList, `clf`, `sal`; the
+    `num_batches_tracked` counters of the affine-free BatchNorms included, a loader has to skip them).  Convolutions are Kaiming-scaled
+    and carry a bias, BatchNorm running statistics are NOT the identity.  Both heads see x^2, all positive: their rows are centred over
+    the channels and scaled by the gains over sqrt(128) (the final map has a standard deviation near 3 on the seeded images), so the two logits differ by about a
+    unit either side of zero and the saliency logit spreads around `sal_shift` = softplus^-1(0.7 / 0.3): the default thresholds 0.7 /
+    0.7 cut through both maps instead of saturating (tests/test_r2d2_cpu.py asserts it).  checkpoint=True wraps the dict as upstream's
+    files do: {'net': 'Quad_L2Net_ConfCFS()', 'state_dict': {'module.' + key: ...}}."""
+    g = torch.Generator().manual_seed(seed)
+    sd = {}
+    for cin, cout, k, op, bn in R2D2_LAYERS:
+        sd[f"ops.{op}.weight"] = torch.randn(cout, cin, k, k, generator=g) * math.sqrt(2.0 / (cin * k * k))
+        sd[f"ops.{op}.bias"] = torch.randn(cout, generator=g) * 0.1
+        if bn:
+            sd[f"ops.{op + 1}.running_mean"] = torch.randn(cout, generator=g) * 0.2
+            sd[f"ops.{op + 1}.running_var"] = 0.5 + torch.rand(cout, generator=g)
+            sd[f"ops.{op + 1}.num_batches_tracked"] = torch.tensor(1000, dtype=torch.long)
+    clf = torch.randn(2, 128, 1, 1, generator=g)
+    sal = torch.randn(1, 128, 1, 1, generator=g)
+    sd["clf.weight"] = (clf - clf.mean(dim=1, keepdim=True)) * (clf_gain / math.sqrt(128))
+    sd["clf.bias"] = torch.tensor([0.0, 0.5])
+    sd["sal.weight"] = (sal - sal.mean(dim=1, keepdim=True)) * (sal_gain / math.sqrt(128))
+    sd["sal.bias"] = torch.tensor([sal_shift])
+    if checkpoint:
+        return {"net": "Quad_L2Net_ConfCFS()", "state_dict": {"module." + k: v for k, v in sd.items()}}
+    return sd

@@ -223,6 +223,45 @@ int imcui_hip_alike_forward(imcui_hip_t* h, int variant, const float* packed, co
 int imcui_hip_alike_desc_probe(imcui_hip_t* h, int variant, const float* packed, const float* image, int H, int W, const int* xy, int n,
                                float* descriptors, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- R2D2 (zoo entry r2d2: `feature: r2d2` + NN-mutual; imcui/hloc/extractors/r2d2.py) ----------------------------------- */
+/* Packed weights of naver/r2d2's Quad_L2Net_ConfCFS (r2d2_WASF_N16 / r2d2_WASF_N8 / r2d2_WAF_N16 share it; replaces `load_network`,
+ * r2d2.py:41): tensors in imcui_hip_r2d2_tensor_name order (`ops.N.weight` / `.bias`, the running statistics of the affine-free
+ * BatchNorms `ops.N+1`, `clf`, `sal`); BatchNorm (eval, eps 1e-5) is folded into the convolution before it in float32.  The network is
+ * restated from its description (tests/r2d2_reference.py): parity with upstream's code is NOT pinned. */
+size_t imcui_hip_r2d2_packed_floats(void);
+int imcui_hip_r2d2_num_tensors(void);
+const char* imcui_hip_r2d2_tensor_name(int i);
+int imcui_hip_r2d2_pack_weights(const float* const* tensors, float* packed);
+/* Scratch of imcui_hip_r2d2_forward for B images and the level list (nh, nw) [host, nlev] with room for kcap candidates per image (the
+ * feature maps are sized for the largest level, the parked candidate vectors are 512 bytes each). */
+size_t imcui_hip_r2d2_workspace_bytes(int B, int nlev, const int* nh, const int* nw, int kcap);
+/* r2d2.py:49-73 `_forward` (norm_rgb, extract_multiscale with NonMaxSuppression, the argsort cut): image [dev, B,3,H,W] RGB in [0,1].
+ * Levels [host, nlev]: level 0 = (H, W), level l + 1 = ATen bilinear (align_corners=False) of level l to (nh, nw)[l + 1]; the network
+ * and the detector run on the levels with run[l] != 0.  The BINDING evaluates upstream's float64 schedule (s /= scale_factor, round);
+ * nlev <= 32, every level inside the image (upstream asserts max_scale <= 1).  Per level: (x - mean) / std, nine convolutions (3x3 and
+ * 2x2, dilations 1 .. 16, every map nh x nw), reliability = softmax(clf(x^2))[1], repeatability = softplus(sal(x^2)) / (1 + softplus),
+ * candidates = (rep == 3x3 max) & (rep >= rep_thr) & (rel >= rel_thr) in row-major order, key-point = ((x * W) / nw, (y * H) / nh) in
+ * float32, score = rel * rep, descriptor = F.normalize of the 128-vector at the pixel.  Candidates are concatenated level-major; more
+ * than max_keypoints (> 0; 0 = all): the highest scores stay, among equal scores the later candidates; output in ASCENDING (score,
+ * candidate) order, i.e. scores.argsort(stable)[-max_keypoints:].
+ * kcap = room for candidates per image (<= the pixels of the running levels); kout = rows per image of the outputs = kcap when
+ * max_keypoints == 0, else min(max_keypoints, kcap).  Outputs, first num_keypoints[b] rows valid, the rest zero:
+ *   keypoints [dev, B,kout,2] (x, y);  scores [dev, B,kout];  descriptors [dev, B,kout,128];  num_keypoints [dev, B] int32
+ *   status [dev, 1] int32 optional: 0 = fine, bit 1 = an image had more candidates than kcap (a flat map: every pixel of a plateau is
+ *   a 3x3 maximum); the result is then that of the first kcap candidates
+ *   dbg_rel / dbg_rep optional: [dev] the maps of the running levels one after another, each [B, nh, nw]; dbg_map likewise, the final
+ *   128-channel map [B, nh, nw, 128]
+ * Zero key-points is a valid result.  No host synchronisation. */
+int imcui_hip_r2d2_forward(imcui_hip_t* h, const float* packed, const float* image, int B, int H, int W, int nlev, const int* nh, const int* nw,
+                           const int* run, float rel_thr, float rep_thr, int max_keypoints, int kcap, int kout, float* keypoints, float* scores,
+                           float* descriptors, int* num_keypoints, int* status, float* dbg_rel, float* dbg_rep, float* dbg_map, void* ws,
+                           size_t ws_bytes, void* stream);
+/* Test entry: the network on ONE image [dev, 3,H,W] at full resolution and F.normalize of its final map at n integer pixels xy
+ * [dev, n,2] int32 (x, y) -> descriptors [dev, n,128] (what the emit stage computes from a parked vector; extract.py: `descriptors[0, :, y,
+ * x]`).  ws: imcui_hip_r2d2_workspace_bytes(1, 1, &H, &W, 1). */
+int imcui_hip_r2d2_desc_probe(imcui_hip_t* h, const float* packed, const float* image, int H, int W, const int* xy, int n, float* descriptors,
+                              void* ws, size_t ws_bytes, void* stream);
+
 /* ---- SIFT (zoo entry sift-lightglue, and `sift` + NN; imcui/hloc/extractors/sift.py, backend "opencv") ------------------- */
 /* OpenCV 4.x SIFT_create(contrastThreshold, nfeatures, edgeThreshold, nOctaveLayers = `layers`; sigma 1.6, first octave -1, float
  * pipeline) -> detectAndCompute (sift.py:61-78), then `filter_dog_point` (:19-52), the score top-k (:188-193) and
@@ -827,6 +866,7 @@ typedef struct imcui_hip_gemm_desc {
     const float* ln_stats;
     const float* ln_rowsum;
     long ln_stride;
+    int conv_dil; /* implicit im2col: taps conv_dil pixels apart (torch's dilation); 0 / 1 = none */
 } imcui_hip_gemm_desc;
 /* Copies *d into the kernel parameters and calls the GEMM launcher unchanged (its own refusals are the only checks); a null
  * handle or descriptor is IMCUI_HIP_ERR_ARG.  sizeof(imcui_hip_gemm_desc) for the bindings' mirror: imcui_hip_gemm_desc_bytes. */
