@@ -424,6 +424,44 @@ extern "C" int imcui_hip_ffn_split_f32(imcui_hip_t* h, const float* x, const flo
     return ffn_launch(h, p, (hipStream_t)stream);
 }
 
+extern "C" size_t imcui_hip_ffn_desc_bytes(void) { return sizeof(imcui_hip_ffn_desc); }
+extern "C" int imcui_hip_ffn_probe_f32(imcui_hip_t* h, const imcui_hip_ffn_desc* d, void* stream) {
+    if (h) h->ffn_last_route = 0;
+    if (!h || !d) return imcui_set_err(h, IMCUI_ERR_ARG, "ffn_probe: null argument");
+    FfnP p;
+    p.x = d->x;
+    p.ctx = d->ctx;
+    p.out = d->out;
+    p.w1h = d->w1h;
+    p.w1l = d->w1l;
+    p.w2h = d->w2h;
+    p.w2l = d->w2l;
+    p.s1 = d->s1;
+    p.s2 = d->s2;
+    p.b1 = d->b1;
+    p.gamma = d->gamma;
+    p.beta = d->beta;
+    p.b2 = d->b2;
+    p.act = d->act;
+    p.M = d->M;
+    p.cnt = d->cnt;
+    p.active = d->active;
+    p.rows_per_seq = d->rows_per_seq;
+    return ffn_launch(h, p, (hipStream_t)stream);
+}
+extern "C" int imcui_hip_ffn_last_route(const imcui_hip_t* h) { return h ? h->ffn_last_route : -1; }
+extern "C" int imcui_hip_ffn_route_counts(const imcui_hip_t* h, int* out, int n) {
+    if (!h || (!out && n > 0)) return -1;
+    for (int i = 0; i < n && i < IMCUI_FFN_ROUTE_SLOTS; ++i) out[i] = h->ffn_route_count[i];
+    return IMCUI_FFN_ROUTE_SLOTS;
+}
+extern "C" int imcui_hip_ffn_route_reset(imcui_hip_t* h) {
+    if (!h) return IMCUI_ERR_ARG;
+    memset(h->ffn_route_count, 0, sizeof h->ffn_route_count);
+    h->ffn_last_route = 0;
+    return IMCUI_OK;
+}
+
 extern "C" int imcui_hip_conv3x3_pack(const float* w_oihw, int Cout, int Cin, float* packed) {
     if (!w_oihw || !packed || Cin % 32 || Cout % 64) return IMCUI_ERR_ARG;
     pack_conv3x3(w_oihw, Cout, Cin, packed);

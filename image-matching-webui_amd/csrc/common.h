@@ -179,6 +179,7 @@ enum {
 #define IMCUI_GEMM_ROUTE_SLOTS 384  // GEMM_ROUTE(kind, epi) < 24 x 16 (gemm.h)
 #define IMCUI_ATTN_ROUTE_SLOTS 16   // ATTN_ROUTE(kind, split) < 8 x 2 (attention.h)
 #define IMCUI_CONV_ROUTE_SLOTS 16   // CONV_ROUTE(kind) < 16 (conv.h)
+#define IMCUI_FFN_ROUTE_SLOTS 17    // FFN_ROUTE(kind, act) = 1 + 4 kind + act <= 16 (ffn.h)
 
 // optional per-kernel-class HIP-event timing (bench.py's live roofline measurement)
 enum { PROF_ATTN = 0, PROF_CONV = 1, PROF_GEMM = 2, PROF_NCLS = 3 };
@@ -213,6 +214,9 @@ struct imcui_hip_s {
     int conv_last_route;
     int conv_route_count[IMCUI_CONV_ROUTE_SLOTS];
     int conv_route_features[IMCUI_CONV_ROUTE_SLOTS];
+    // the same for ffn_launch (FFN_ROUTE of ffn.h; imcui_hip_ffn_route_reset)
+    int ffn_last_route;
+    int ffn_route_count[IMCUI_FFN_ROUTE_SLOTS];
 };
 // scan `rows` x `cols` f32 values (row stride ld; rows of sequence s beyond cnt[s] are padding and skipped) into h->range_flag
 void imcui_range_check(imcui_hip_s* h, const float* x, long rows, int cols, long ld, const int* cnt, int rows_per_seq, hipStream_t s);

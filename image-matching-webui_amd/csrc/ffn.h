@@ -21,12 +21,39 @@ struct FfnP {
     // residual (EfficientLoFTR / LoFTR coarse MLPs: x + LN(fc2(act(fc1([x | message])))), no biases: b1 = b2 = nullptr)
     int act = 0;
     int M = 0;
-    // ragged sequences, as in GemmP: a 128-row tile whose first row is >= cnt[seq] or whose pair is inactive is skipped
+    // ragged sequences, as in GemmP (rows_per_seq % 128 == 0, sequence = row / rows_per_seq, pair = sequence >> 1): the unit that is
+    // skipped is the launch's TOKEN TILE (128, 64 or 32 rows, see ffn_launch) -- a tile whose first row is >= cnt[seq], or whose pair
+    // has active[pair] == 0, neither reads nor writes.  A live tile is computed and stored whole: its rows past cnt[seq] (up to
+    // roundup(cnt[seq], tile)) are written with whatever the padding rows of x / ctx give; they never feed a live row.
     const int* cnt = nullptr;
     const int* active = nullptr;
     int rows_per_seq = 0;
     long long* dbg = nullptr;  // lab only: 8 wall-clock stamps per workgroup (phase boundaries, wave 0)
 };
+
+// Limit of the opt-in range check (imcui_hip_set_range_check): ffn_launch scans the two operands it can see, x and ctx.  The hidden
+// activations are re-split into f16 planes INSIDE the kernel (between the two GEMMs) and are not scanned: in the LayerNorm + GELU mode
+// they are bounded by |gamma| sqrt(512) + |beta|, in the ReLU / LeakyReLU modes (act 1, 2, 3) they are unbounded, and a hidden value
+// beyond 65504 saturates its hi plane without raising the flag.
+
+// Route of a launch: which kernel instantiation ffn_launch chose, FFN_ROUTE(kind, act); 0 = none (a refused or empty call).  The launch
+// site stores it in the handle (imcui_hip_ffn_last_route / _route_counts), so the report cannot disagree with what ran; host code only.
+// The kinds are the rows of ffn_launch's kernel table.  Values are part of the test ABI (imcui_hip/backend.py mirrors them; a CPU test
+// compares the two).
+enum FfnRouteKind {
+    FR_T128_ROLLED = 0,  // lg_ffn_kernel<0, ACT, 4>: 128-token tile, rolled K loop (lab: IMCUI_FFN_VARIANT=0)
+    FR_T128 = 1,         // lg_ffn_kernel<1, ACT, 4>
+    FR_T64 = 2,          // lg_ffn_kernel<1, ACT, 2>
+    FR_T32 = 3,          // lg_ffn_kernel<1, ACT, 1>
+    FR_NKIND = 4
+};
+#define FFN_ROUTE(kind, act) (1 + (kind) * 4 + (act))
+static_assert(FFN_ROUTE(FR_NKIND - 1, 3) < IMCUI_FFN_ROUTE_SLOTS, "route table of imcui_hip_s too small");
+static inline void ffn_route_note(imcui_hip_s* h, int kind, int act) {
+    const int r = FFN_ROUTE(kind, act);
+    h->ffn_last_route = r;
+    ++h->ffn_route_count[r];
+}
 
 int ffn_launch(imcui_hip_s* h, const FfnP& p, hipStream_t stream);
 

@@ -398,6 +398,7 @@ __global__ __launch_bounds__(512, 2) void lg_ffn_kernel(FfnP p) {
 }
 
 int ffn_launch(imcui_hip_s* h, const FfnP& p, hipStream_t stream) {
+    h->ffn_last_route = 0;  // a refused or empty call leaves "none"
     if (h->precision != 1) return imcui_set_err(h, IMCUI_ERR_UNSUPPORTED, "ffn: the fused kernel is the 3 x f16 split path (precision 1)");
     if (!p.x || !p.ctx || !p.out || !p.w1h || !p.w1l || !p.w2h || !p.w2l || !p.s1 || !p.s2 || (p.act != 1 && (!p.gamma || !p.beta)))
         return imcui_set_err(h, IMCUI_ERR_ARG, "ffn: null argument");
@@ -428,6 +429,7 @@ int ffn_launch(imcui_hip_s* h, const FfnP& p, hipStream_t stream) {
     hipLaunchKernelGGL(kerns[v][a], dim3((p.M + tok - 1) / tok), dim3(512), FFN_LDS_BYTES, stream, p);
     imcui_prof_end(h, PROF_GEMM, stream);
     IMCUI_CHECK_LAUNCH(h);
+    ffn_route_note(h, v, a);  // the rows of kerns[] are the FfnRouteKind values
     return IMCUI_OK;
 }
 

@@ -2210,6 +2210,88 @@ def attn_route_reset(device: torch.device) -> None:
     hd.call(hd.lib.imcui_hip_attn_route_reset)
 
 
+# ------------------------------------------------------------------ the fused-FFN launcher, entered directly (kernel-variant tests)
+# FfnRouteKind of csrc/ffn.h: a route is 1 + 4 kind + act (imcui_hip_ffn_last_route); 0 = nothing launched
+FFN_ROUTE_KINDS = {"t128_rolled": 0, "t128": 1, "t64": 2, "t32": 3}
+
+
+def ffn_route(kind: str, act: int) -> int:
+    return 1 + FFN_ROUTE_KINDS[kind] * 4 + int(act)
+
+
+def ffn_route_name(route: int) -> str:
+    if route <= 0:
+        return "none"
+    kinds = {v: k for k, v in FFN_ROUTE_KINDS.items()}
+    return f"{kinds.get((route - 1) // 4, (route - 1) // 4)}/act{(route - 1) % 4}"
+
+
+class FfnDesc(C.Structure):
+    """ctypes mirror of imcui_hip_ffn_desc (include/imcui_hip.h); the CPU suite compares its size with the library's."""
+
+    _fields_ = [("x", C.c_void_p), ("ctx", C.c_void_p), ("out", C.c_void_p), ("w1h", C.c_void_p), ("w1l", C.c_void_p), ("w2h", C.c_void_p),
+                ("w2l", C.c_void_p), ("s1", C.c_void_p), ("s2", C.c_void_p), ("b1", C.c_void_p), ("gamma", C.c_void_p), ("beta", C.c_void_p),
+                ("b2", C.c_void_p), ("act", C.c_int), ("M", C.c_int), ("cnt", C.c_void_p), ("active", C.c_void_p), ("rows_per_seq", C.c_int)]  # fmt: skip
+
+
+class FfnWeights:
+    """The two Linear layers of one FFN (host W1 [512, 512], W2 [256, 512]) in the operand format of csrc/ffn.hip, packed once and kept on
+    `device`: W1 as the planes of pack_linear_split, W2 as the planes of pack_ffn_w2 (K axis in the kernel's hand-over order), each with
+    its 2^-e scale.  The host copies of the planes and scales stay available (w1_planes / w2_planes: what the kernel multiplies)."""
+
+    def __init__(self, w1, w2, device):
+        self.w1_planes = pack_linear_split(w1)
+        self.w2_planes = pack_ffn_w2(w2)
+
+        def up(a):
+            return torch.from_numpy(a.view(np.int16)).to(device)
+
+        self.w1h, self.w1l, self.w2h, self.w2l = up(self.w1_planes[0]), up(self.w1_planes[1]), up(self.w2_planes[0]), up(self.w2_planes[1])
+        self.s1 = torch.tensor([self.w1_planes[2]], dtype=torch.float32, device=device)
+        self.s2 = torch.tensor([self.w2_planes[2]], dtype=torch.float32, device=device)
+
+    def fields(self) -> dict:
+        return {"w1h": self.w1h, "w1l": self.w1l, "s1": self.s1, "w2h": self.w2h, "w2l": self.w2l, "s2": self.s2}
+
+
+def ffn_probe(device: torch.device, check: bool = True, **fields) -> int:
+    """One launch through ffn_launch (imcui_hip_ffn_probe_f32) with the descriptor `fields` (tensors become device pointers, None a null
+    pointer).  Returns the route of the launch (ffn_route); with check=False a refused call returns its negative status instead of
+    raising."""
+    hd = get_handle(device)
+    d = FfnDesc()
+    for k, v in fields.items():
+        if isinstance(v, torch.Tensor):
+            if v.device.type != "cuda":
+                raise ImcuiHipError(f"ffn_probe: field {k} must be a device tensor")
+            v = v.data_ptr()
+        elif v is None:
+            v = 0
+        setattr(d, k, v)
+    if check:
+        hd.launch(hd.lib.imcui_hip_ffn_probe_f32, C.byref(d))
+    else:
+        with torch.cuda.device(hd.device_index):
+            rc = hd.lib.imcui_hip_ffn_probe_f32(hd.h, C.byref(d), _stream_ptr())
+        if rc != 0:
+            return rc
+    return int(hd.lib.imcui_hip_ffn_last_route(hd.h))
+
+
+def ffn_route_counts(device: torch.device) -> dict:
+    """{route: launches} of every fused-FFN launch on the device's handle since ffn_route_reset."""
+    hd = get_handle(device)
+    n = hd.lib.imcui_hip_ffn_route_counts(hd.h, None, 0)
+    buf = (C.c_int * n)()
+    hd.lib.imcui_hip_ffn_route_counts(hd.h, buf, n)
+    return {r: c for r, c in enumerate(buf) if c}
+
+
+def ffn_route_reset(device: torch.device) -> None:
+    hd = get_handle(device)
+    hd.call(hd.lib.imcui_hip_ffn_route_reset)
+
+
 # ------------------------------------------------------------------ the 3x3 convolution launchers, entered directly (kernel-variant tests)
 # ConvRouteKind / ConvFeature of csrc/conv.h (imcui_hip_conv_last_route, imcui_hip_conv_route_features)
 CONV_ROUTE_KINDS = {"none": 0, "f32": 1, "split_n2": 2, "split_n4": 3, "split_n2_single": 4, "split_n4_single": 5, "tall": 6,

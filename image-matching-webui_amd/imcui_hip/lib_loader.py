@@ -272,6 +272,11 @@ SIGNATURES = {
     "imcui_hip_conv_route_counts": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int]),
     "imcui_hip_conv_route_features": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int]),
     "imcui_hip_conv_route_reset": (C.c_int, [C.c_void_p]),
+    "imcui_hip_ffn_desc_bytes": (C.c_size_t, []),
+    "imcui_hip_ffn_probe_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "imcui_hip_ffn_last_route": (C.c_int, [C.c_void_p]),
+    "imcui_hip_ffn_route_counts": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int]),
+    "imcui_hip_ffn_route_reset": (C.c_int, [C.c_void_p]),
     "imcui_hip_attention_mx_f32": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 4 + [C.c_void_p, C.c_size_t, C.c_void_p]),
 }
 

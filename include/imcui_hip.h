@@ -953,6 +953,43 @@ int imcui_hip_conv_route_counts(const imcui_hip_t* h, int* out, int n);
 int imcui_hip_conv_route_features(const imcui_hip_t* h, int* out, int n);
 int imcui_hip_conv_route_reset(imcui_hip_t* h);
 
+/* ---- test entry into the fused-FFN launcher (tests/test_gpu_ffn_variants.py) --------------------------------------------------
+ * Every field of the launcher's parameters (csrc/ffn.h, FfnP; meanings there) except the lab's stamp buffer.  Device pointers; unset
+ * fields zero.  What imcui_hip_ffn_split_f32 cannot express: the ragged form LightGlue and SuperGlue launch (cnt [S], active [S / 2],
+ * rows_per_seq % 128 == 0, M = S * rows_per_seq) and the null arrays the networks pass (b1 = b2 = NULL: LoFTR, EfficientLoFTR;
+ * gamma = beta = NULL with act 1: SuperGlue). */
+typedef struct imcui_hip_ffn_desc {
+    const float* x;
+    const float* ctx;
+    float* out;
+    const unsigned short* w1h;
+    const unsigned short* w1l;
+    const unsigned short* w2h;
+    const unsigned short* w2l;
+    const float* s1;
+    const float* s2;
+    const float* b1;
+    const float* gamma;
+    const float* beta;
+    const float* b2;
+    int act;
+    int M;
+    const int* cnt;
+    const int* active;
+    int rows_per_seq;
+} imcui_hip_ffn_desc;
+/* Copies *d into the kernel parameters and calls the FFN launcher unchanged (its own refusals are the only checks: precision 0 is
+ * IMCUI_HIP_ERR_UNSUPPORTED; a null mandatory pointer, an act outside 0 .. 3, rows_per_seq % 128 != 0 are IMCUI_HIP_ERR_ARG); a null
+ * handle or descriptor is IMCUI_HIP_ERR_ARG.  Nothing is launched by a refused call or by M <= 0 (which is IMCUI_HIP_OK). */
+int imcui_hip_ffn_probe_f32(imcui_hip_t* h, const imcui_hip_ffn_desc* d, void* stream);
+size_t imcui_hip_ffn_desc_bytes(void);
+/* Route of the last fused-FFN launch on this handle = 1 + 4 kind + act (csrc/ffn.h FfnRouteKind: the token tile; 0 = nothing launched:
+ * a refused or empty call), and launches per route since imcui_hip_ffn_route_reset, as for the GEMM above.  Every launch of every
+ * network records its route (one host-side store), imcui_hip_ffn_split_f32 included. */
+int imcui_hip_ffn_last_route(const imcui_hip_t* h);
+int imcui_hip_ffn_route_counts(const imcui_hip_t* h, int* out, int n);
+int imcui_hip_ffn_route_reset(imcui_hip_t* h);
+
 #ifdef __cplusplus
 }
 #endif
