@@ -107,6 +107,8 @@ struct GemmP {
     // implicit im2col with dilated taps (conv_k > 0): tap (ky, kx) reads input pixel (oy stride - pad + ky conv_dil, ox stride - pad +
     // kx conv_dil).  0 / 1 = no dilation: the launch is the undilated one, instantiation and bits.  > 1 selects the ASRC = 2
     // instantiations (GR_EXACT_DIL / GR_CONVD_*); the single-product arithmetic is not built for them
+    // Dilated launches with K >= 2048 sum in two levels (gemm.hip, GEMM_CHUNK_MIN_K): the exact kernel in place, the split arithmetic
+    // (pre-split planes) on the 128-column kernel's CHUNK instantiation, route GR_CONVD_128 whatever N
     int conv_dil = 0;
 };
 
@@ -134,7 +136,7 @@ enum GemmRouteKind {
     GR_WREG_MT1 = 17,        // gemm_wreg_kernel<EPI, false, true, 1>
     GR_EXACT_DIL = 18,       // gemm_kernel<EPI_CONV, true>: dilated taps (GemmP.conv_dil > 1)
     GR_CONVD_F32B = 19,      // gemm_split_kernel<EPI_CONV, 2, false, 2>
-    GR_CONVD_128 = 20,       // gemm_split_kernel<EPI_CONV, 2, true, 2>
+    GR_CONVD_128 = 20,       // gemm_split_kernel<EPI_CONV, 2, true, 2> (K >= 2048: <EPI_CONV, 2, true, 2, false, true>)
     GR_CONVD_256 = 21,       // gemm_split_kernel<EPI_CONV, 2, true, 4>
     GR_NKIND = 22
 };

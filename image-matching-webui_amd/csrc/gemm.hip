@@ -183,6 +183,8 @@ __device__ __forceinline__ const float* gemm_a_src(const GemmP& p, const float* 
 
 // ------------------------------------------------------------------ exact f32 kernel
 #define BK32 32
+#define GEMM_CHUNK_MIN_K 2048  // exact dilated kernel: two-level summation from this K on
+#define GEMM_CHUNK_TILES 4     // ... in chunks of 4 K-tiles (128 products)
 template <int EPI, bool DIL = false>
 __global__ __launch_bounds__(256) void gemm_kernel(GemmP p) {
     __shared__ float4 As[(BK32 / 4) * LDS_ROWS];
@@ -205,6 +207,21 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmP p) {
         for (int n = 0; n < 2; ++n)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[m][n][r] = 0.0f;
+    // DIL, K >= GEMM_CHUNK_MIN_K: two-level summation.  One chain of K / 2 float32 accumulations loses sqrt(K)-many roundings (measured
+    // against float64 on one set of operands: 7.7e-07 at K = 576, 1.2e-06 at 1152, 1.9e-06 at 2304, 3.3e-06 at 4608, dilated or not);
+    // every GEMM_CHUNK_TILES K-tiles the accumulators are added to a second set and restart from zero.  Only the dilated instantiation
+    // carries it (D2-Net's K = 2304 / 4608 layers); launches below the threshold (R2D2: K <= 1152) keep their single chain and bits.
+    constexpr int TN = DIL ? 2 : 1;
+    f32x16 tot[TN][TN];
+    const bool chunked = DIL && p.K >= GEMM_CHUNK_MIN_K;
+    if constexpr (DIL) {
+#pragma unroll
+        for (int m = 0; m < 2; ++m)
+#pragma unroll
+            for (int n = 0; n < 2; ++n)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) tot[m][n][r] = 0.0f;
+    }
 
     // staging: 128 rows x 8 k-quads per operand = 1024 float4, 4 per thread
     const int s_kq = tid & 7;
@@ -255,7 +272,30 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmP p) {
                     acc[m][n] = mfma32(b[n].w, a[m].w, acc[m][n]);
                 }
         }
+        if constexpr (DIL) {
+            if (chunked && (kt % GEMM_CHUNK_TILES) == GEMM_CHUNK_TILES - 1) {
+#pragma unroll
+                for (int m = 0; m < 2; ++m)
+#pragma unroll
+                    for (int n = 0; n < 2; ++n)
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) {
+                            tot[m][n][r] += acc[m][n][r];
+                            acc[m][n][r] = 0.0f;
+                        }
+            }
+        }
         __syncthreads();
+    }
+    if constexpr (DIL) {
+        if (chunked) {
+#pragma unroll
+            for (int m = 0; m < 2; ++m)
+#pragma unroll
+                for (int n = 0; n < 2; ++n)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) acc[m][n][r] += tot[m][n][r];
+        }
     }
     gemm_epilogue<EPI>(p, c, acc, 1.0f, wm, wn, lo, hi);
 }
@@ -704,14 +744,18 @@ __device__ __forceinline__ void gemm_epilogue_staged(const GemmP& p, const TileC
 //       matrix pipe and everything else serialise, so the wave tile is the efficiency lever
 // SINGLE: one f16 product per element pair instead of three (hi planes only, f32 accumulate): the arithmetic class of a
 //       bf16 / fp16 autocast run (11-bit operands) for callers that ask for it (GemmP.single; pre-split weights only)
-template <int EPI, int ASRC, bool WDMA, int NW, bool SINGLE = false>
-__global__ __launch_bounds__(256, (WDMA && NW == 2) ? 3 : 2) void gemm_split_kernel(GemmP p) {
+// CHUNK: two-level summation as in gemm_kernel<EPI, true> (every GEMM_CHUNK_TILES K-tiles the accumulators move to a second set): the
+//       128-column dilated kernel only, launched for K >= GEMM_CHUNK_MIN_K; two workgroups per CU (twice the accumulator registers).
+//       Every other instantiation compiles from the code it always had.
+template <int EPI, int ASRC, bool WDMA, int NW, bool SINGLE = false, bool CHUNK = false>
+__global__ __launch_bounds__(256, (WDMA && NW == 2 && !CHUNK) ? 3 : 2) void gemm_split_kernel(GemmP p) {
     // 128-column tiles: the four weight fragments of a wave in four registers, single LDS buffer (written between
     // the two barriers like the activations).  256-column tiles: eight fragments, four registers, two halves,
     // double-buffered in LDS (parked while the current tile is multiplied).
     constexpr bool WREGP = WDMA && NW == 2;
     static_assert(NW == 2 || (NW == 4 && WDMA), "256-column tiles need pre-split weight planes");
     static_assert(!SINGLE || WDMA, "the single-product variant reads pre-split weight planes");
+    static_assert(!CHUNK || (WDMA && NW == 2 && ASRC == 2 && !SINGLE), "two-level summation is built for the 128-column dilated kernel");
     constexpr int BPL = 4 * NW * 1024;  // bytes per B plane per stage: [ks 2][nf 2 NW] fragments of 1 KiB
     // A_hi 8K | A_lo 8K | B stage 0 (hi, lo) | B stage 1 (256-column tiles) ; reused by the epilogue (<= 36864 B)
     __shared__ uint4 smem[((WDMA && NW == 2) ? 36864 : 16384 + 4 * BPL) / 16];
@@ -735,6 +779,28 @@ __global__ __launch_bounds__(256, (WDMA && NW == 2) ? 3 : 2) void gemm_split_ker
         for (int n = 0; n < NW; ++n)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[m][n][r] = 0.0f;
+    f32x16 tot[CHUNK ? 2 : 1][CHUNK ? NW : 1];
+    if constexpr (CHUNK) {
+#pragma unroll
+        for (int m = 0; m < 2; ++m)
+#pragma unroll
+            for (int n = 0; n < NW; ++n)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) tot[m][n][r] = 0.0f;
+    }
+    auto flush = [&]() __attribute__((always_inline)) {
+        if constexpr (CHUNK) {
+#pragma unroll
+            for (int m = 0; m < 2; ++m)
+#pragma unroll
+                for (int n = 0; n < NW; ++n)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        tot[m][n][r] += acc[m][n][r];
+                        acc[m][n][r] = 0.0f;
+                    }
+        }
+    };
 
     // ---- staging geometry: thread -> k-octet g = tid & 3 (8 consecutive k) of rows tid >> 2 and + 64
     const int g = tid & 3;
@@ -960,6 +1026,9 @@ __global__ __launch_bounds__(256, (WDMA && NW == 2) ? 3 : 2) void gemm_split_ker
             __syncthreads();
             if (kt + 1 < nkt) {
                 compute(1);
+                if constexpr (CHUNK) {
+                    if (((kt + 1) % GEMM_CHUNK_TILES) == GEMM_CHUNK_TILES - 1) flush();  // (GEMM_CHUNK_TILES is even: chunks end on odd tiles)
+                }
                 __syncthreads();
                 if (kt + 2 < nkt) {
                     store_a(xa0, xb0, xa1, xb1, xv0, xv1);
@@ -1047,6 +1116,14 @@ __global__ __launch_bounds__(256, (WDMA && NW == 2) ? 3 : 2) void gemm_split_ker
             }
         }
     }
+    if constexpr (CHUNK) {
+#pragma unroll
+        for (int m = 0; m < 2; ++m)
+#pragma unroll
+            for (int n = 0; n < NW; ++n)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[m][n][r] += tot[m][n][r];
+    }
     gemm_epilogue_staged<EPI, NW>(p, c, acc, wsc, wm, wn, lo, hi, sm);
 }
 
@@ -1099,12 +1176,17 @@ static void launch_one(imcui_hip_s* h, const GemmP& p, bool split, hipStream_t s
     }
 }
 static void launch_conv(imcui_hip_s* h, const GemmP& p, bool split, hipStream_t stream) {
-    const bool wide = split && wide_ok(p);
+    // long dilated layers with pre-split planes: the 128-column kernel with two-level summation, whatever N (route convd_128)
+    const bool chunk = split && p.conv_dil > 1 && p.Wh != nullptr && p.K >= GEMM_CHUNK_MIN_K;
+    const bool wide = split && wide_ok(p) && !chunk;
     const dim3 grid(cdiv(p.M, BM) * cdiv(p.N, wide ? 256 : BN), 1, p.batch);
     if (p.conv_dil > 1) {  // dilated taps: the ASRC = 2 instantiations (gemm_launch has refused `single`)
         if (!split) {
             gemm_route_note(h, GR_EXACT_DIL, EPI_CONV);
             hipLaunchKernelGGL((gemm_kernel<EPI_CONV, true>), grid, dim3(256), 0, stream, p);
+        } else if (chunk) {
+            gemm_route_note(h, GR_CONVD_128, EPI_CONV);
+            hipLaunchKernelGGL((gemm_split_kernel<EPI_CONV, 2, true, 2, false, true>), grid, dim3(256), 0, stream, p);
         } else if (wide) {
             gemm_route_note(h, GR_CONVD_256, EPI_CONV);
             hipLaunchKernelGGL((gemm_split_kernel<EPI_CONV, 2, true, 4>), grid, dim3(256), 0, stream, p);

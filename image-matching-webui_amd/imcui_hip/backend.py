@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes as C
+import math
 import threading
 
 import numpy as np
@@ -791,8 +792,142 @@ class R2D2HIP:
         return desc
 
 
+# ------------------------------------------------------------------ D2-Net / RoRD
+# (cin, cout, dilation, index in DenseFeatureExtractionModule.model): VGG-16 cut at conv4_3, csrc/d2net.hip
+D2NET_LAYERS = ((3, 64, 1, 0), (64, 64, 1, 2), (64, 128, 1, 5), (128, 128, 1, 7), (128, 256, 1, 10), (256, 256, 1, 12), (256, 256, 1, 14),
+                (256, 512, 2, 17), (512, 512, 2, 19), (512, 512, 2, 21))  # fmt: skip
+D2NET_SCALES_SS, D2NET_SCALES_MS = (1,), (0.5, 1, 2)  # process_multiscale: `scales=[1]` (d2net.py:46) and its default
+D2NET_MAX_LEVELS = 8
+
+
+def d2net_tensor_names() -> list[str]:
+    lib = load_library()
+    return [lib.imcui_hip_d2net_tensor_name(i).decode() for i in range(lib.imcui_hip_d2net_num_tensors())]
+
+
+def d2net_tensor_shapes() -> dict:
+    shapes = {}
+    for cin, cout, _, op in D2NET_LAYERS:
+        shapes[f"dense_feature_extraction.model.{op}.weight"] = (cout, cin, 3, 3)
+        shapes[f"dense_feature_extraction.model.{op}.bias"] = (cout,)
+    return shapes
+
+
+def pack_d2net(state_dict: dict) -> torch.Tensor:
+    """D2-Net / RoRD checkpoint ({'model': state dict}, as lib/model_test.py loads it) or a bare state dict -> packed float32 buffer
+    (host).  Strict: every key is consumed exactly once, every shape checked."""
+    lib = load_library()
+    sd = state_dict
+    if isinstance(sd, dict) and "model" in sd and isinstance(sd["model"], dict):
+        sd = sd["model"]
+    return _pack_named("D2-Net", "upstream's DenseFeatureExtractionModule", d2net_tensor_names(), d2net_tensor_shapes(), dict(sd),
+                       lib.imcui_hip_d2net_packed_floats(), lib.imcui_hip_d2net_pack_weights)
+
+
+def d2net_levels(H: int, W: int, scales=D2NET_SCALES_SS) -> list:
+    """process_multiscale's level images: F.interpolate(scale_factor=s) gives floor(H * s) x floor(W * s), evaluated in float64 as ATen
+    does; in list order.  A level whose feature map (size // 4 - 1) would be empty is refused."""
+    if not 1 <= len(scales) <= D2NET_MAX_LEVELS:
+        raise ValueError(f"D2-Net: {len(scales)} scales (1..{D2NET_MAX_LEVELS})")
+    levels = []
+    for s in scales:
+        lh, lw = int(math.floor(float(H) * float(s))), int(math.floor(float(W) * float(s)))
+        if lh // 4 - 1 < 1 or lw // 4 - 1 < 1:
+            raise ValueError(f"D2-Net: the {H}x{W} image at scale {s} is {lh}x{lw}, its feature map ({lh // 4 - 1}x{lw // 4 - 1}) is empty: "
+                             "every level needs at least 8x8 pixels")  # fmt: skip
+        levels.append((lh, lw))
+    return levels
+
+
+def d2net_check_args(image_shape, scales=D2NET_SCALES_SS) -> list:
+    """Refusals raised before anything is launched; returns the level list."""
+    if len(image_shape) != 4 or image_shape[1] != 3:
+        raise ValueError(f"D2-Net expects an RGB image [B,3,H,W], got shape {tuple(image_shape)}")
+    return d2net_levels(int(image_shape[2]), int(image_shape[3]), scales)
+
+
+class D2NetHIP:
+    def __init__(self):
+        self._ws = _Workspace()
+
+    def forward(self, packed: torch.Tensor, image: torch.Tensor, conf: dict, want_maps: bool = False, kcap: int | None = None, scales=None):
+        """image [B,3,H,W] float32 RGB in [0,1] on the GPU -> fixed-stride outputs, no host synchronisation: keypoints [B,K,2] (x, y in
+        pixels of the input image), scores [B,K], descriptors [B,K,512], num_keypoints [B] int32, status [1] int32 (bit 1: more
+        candidates than `kcap`), rows in ascending score order.  K = max_keypoints, or kcap when max_keypoints is 0 (all).  kcap
+        defaults to the sum of the levels' feature-map pixels: one candidate per pixel, enough unless channels tie for the maximum.
+        want_maps adds `levels` (feature-map sizes) and `dense_features`, per level [B,h,w,512] after the multi-scale sum."""
+        if scales is None:
+            scales = D2NET_SCALES_MS if conf.get("multiscale") else D2NET_SCALES_SS
+        levels = d2net_check_args(tuple(image.shape), scales)
+        hd = get_handle(image.device)
+        _same_device(packed, image)
+        lib = hd.lib
+        image = image.contiguous().float()
+        B, _, H, W = image.shape
+        dev = image.device
+        fsz = [(lh // 4 - 1, lw // 4 - 1) for lh, lw in levels]
+        npix = sum(a * b for a, b in fsz)
+        kcap = max(1, int(npix if kcap is None else kcap))
+        maxk = int(conf["max_keypoints"] or 0)
+        kout = kcap if maxk <= 0 else min(maxk, kcap)
+        kpts, scores, desc, nk, status, out = _sparse_outputs(B, kout, 512, dev)
+        n = len(levels)
+        lh = (C.c_int * n)(*[l[0] for l in levels])
+        lw = (C.c_int * n)(*[l[1] for l in levels])
+        fmap = torch.empty(B * npix * 512, dtype=torch.float32, device=dev) if want_maps else None
+        with self._ws.use(lib.imcui_hip_d2net_workspace_bytes(B, n, lh, lw, kcap), dev) as ws:
+            hd.launch(
+                lib.imcui_hip_d2net_forward, _ptr(packed), _ptr(image), B, H, W, n, lh, lw, int(bool(conf.get("use_relu", True))), maxk, kcap, kout,
+                _ptr(kpts), _ptr(scores), _ptr(desc), _ptr(nk), _ptr(status), _ptr(fmap), _ptr(ws), ws.numel(),
+            )  # fmt: skip
+        if want_maps:
+            out["levels"] = fsz
+            out["dense_features"] = []
+            off = 0
+            for fh, fw in fsz:
+                m = B * fh * fw * 512
+                out["dense_features"].append(fmap[off : off + m].view(B, fh, fw, 512))
+                off += m
+        return out
+
+    @staticmethod
+    def layer_probe(op: str, inp: torch.Tensor, packed: torch.Tensor | None = None) -> torch.Tensor:
+        """Test entry: one small kernel of the trunk alone.  "conv0": image [B,3,H,W] -> [B,H,W,64] (needs `packed`); "maxpool": NHWC
+        [B,H,W,C] -> [B,H//2,W//2,C]; "avgpool": -> [B,H-1,W-1,C]."""
+        code = {"conv0": 0, "maxpool": 1, "avgpool": 2}[op]
+        hd = get_handle(inp.device)
+        inp = inp.contiguous().float()
+        if code == 0:
+            B, _, H, W = inp.shape
+            Cc, shape = 64, (B, H, W, 64)
+        else:
+            B, H, W, Cc = inp.shape
+            shape = (B, H // 2, W // 2, Cc) if code == 1 else (B, H - 1, W - 1, Cc)
+        out = torch.empty(shape, dtype=torch.float32, device=inp.device)
+        hd.launch(hd.lib.imcui_hip_d2net_layer_probe, code, _ptr(packed), _ptr(inp), B, H, W, Cc, _ptr(out))
+        return out
+
+    def detect_probe(self, feat: torch.Tensor, max_keypoints: int = 0, kcap: int | None = None):
+        """Test entry: detector, localization, candidate list, cut and descriptors on the caller's maps feat [B,h,w,C] (C a multiple of
+        64 up to 512) as one level that is its own image -> the outputs of `forward` with descriptors [B,K,C]."""
+        if feat.dim() != 4 or feat.shape[3] % 64 or not 64 <= feat.shape[3] <= 512:
+            raise ValueError(f"detect_probe expects maps [B,h,w,C] with C a multiple of 64 up to 512, got {tuple(feat.shape)}")
+        hd = get_handle(feat.device)
+        lib = hd.lib
+        feat = feat.contiguous().float()
+        B, fh, fw, Cc = feat.shape
+        kcap = max(1, int(fh * fw if kcap is None else kcap))
+        maxk = int(max_keypoints or 0)
+        kout = kcap if maxk <= 0 else min(maxk, kcap)
+        kpts, scores, desc, nk, status, out = _sparse_outputs(B, kout, Cc, feat.device)
+        with self._ws.use(lib.imcui_hip_d2net_probe_workspace_bytes(B, fh, fw, Cc, kcap), feat.device) as ws:
+            hd.launch(lib.imcui_hip_d2net_detect_probe, _ptr(feat), B, fh, fw, Cc, maxk, kcap, kout, _ptr(kpts), _ptr(scores), _ptr(desc), _ptr(nk),
+                      _ptr(status), _ptr(ws), ws.numel())  # fmt: skip
+        return out
+
+
 # ------------------------------------------------------------------ SIFT
-SIFT_LAYERS = (3, 4, 5)  # nOctaveLayers (the wrapper's `num_octaves`) csrc/sift.hip is written for: blur radius at most 13
+SIFT_LAYERS =(3, 4, 5)  # nOctaveLayers (the wrapper's `num_octaves`) csrc/sift.hip is written for: blur radius at most 13
 
 
 def sift_check_args(image_shape, conf: dict) -> None:

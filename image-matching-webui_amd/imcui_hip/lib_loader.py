@@ -92,6 +92,15 @@ SIGNATURES = {
         [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_void_p] * 3 + [C.c_float] * 2 + [C.c_int] * 3 + [C.c_void_p] * 8 + [C.c_void_p, C.c_size_t, C.c_void_p],
     ),
     "imcui_hip_r2d2_desc_probe": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "imcui_hip_d2net_packed_floats": (C.c_size_t, []),
+    "imcui_hip_d2net_num_tensors": (C.c_int, []),
+    "imcui_hip_d2net_tensor_name": (C.c_char_p, [C.c_int]),
+    "imcui_hip_d2net_pack_weights": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p]),
+    "imcui_hip_d2net_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
+    "imcui_hip_d2net_forward": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_void_p] * 2 + [C.c_int] * 4 + [C.c_void_p] * 6 + [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "imcui_hip_d2net_layer_probe": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_void_p]),
+    "imcui_hip_d2net_probe_workspace_bytes": (C.c_size_t, [C.c_int] * 5),
+    "imcui_hip_d2net_detect_probe": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 7 + [C.c_void_p] * 5 + [C.c_void_p, C.c_size_t, C.c_void_p]),
     "imcui_hip_sift_num_octaves": (C.c_int, [C.c_int] * 2),
     "imcui_hip_sift_pyramid_floats": (C.c_size_t, [C.c_int] * 4),
     "imcui_hip_sift_workspace_bytes": (C.c_size_t, [C.c_int] * 6),

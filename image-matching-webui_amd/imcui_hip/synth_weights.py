@@ -763,3 +763,20 @@ def r2d2_state_dict(seed: int = 0, clf_gain: float = 0.15, sal_gain: float = 0.1
     if checkpoint:
         return {"net": "Quad_L2Net_ConfCFS()", "state_dict": {"module." + k: v for k, v in sd.items()}}
     return sd
+
+
+# (cin, cout, index in DenseFeatureExtractionModule.model): mihaidusmanu/d2-net lib/model_test.py, VGG-16 cut at conv4_3
+D2NET_LAYERS = ((3, 64, 0), (64, 64, 2), (64, 128, 5), (128, 128, 7), (128, 256, 10), (256, 256, 12), (256, 256, 14), (256, 512, 17), (512, 512, 19),
+                (512, 512, 21))  # fmt: skip
+
+
+def d2net_state_dict(seed: int = 0, checkpoint: bool = False) -> dict:
+    """Seeded D2-Net / RoRD weights under upstream's key names (`dense_feature_extraction.model.N.{weight,bias}`): Kaiming-scaled 3x3
+    convolutions, biases near 0.1 in size.  The first layer sees `x * 255 - mean` (hundreds), so the maps grow to the thousands; the
+    detector is scale-free.  checkpoint=True wraps the dict as upstream's files do: {'model': state dict}."""
+    g = torch.Generator().manual_seed(seed)
+    sd = {}
+    for cin, cout, op in D2NET_LAYERS:
+        sd[f"dense_feature_extraction.model.{op}.weight"] = torch.randn(cout, cin, 3, 3, generator=g) * math.sqrt(2.0 / (cin * 9))
+        sd[f"dense_feature_extraction.model.{op}.bias"] = torch.randn(cout, generator=g) * 0.1
+    return {"model": sd} if checkpoint else sd

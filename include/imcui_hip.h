@@ -262,6 +262,50 @@ int imcui_hip_r2d2_forward(imcui_hip_t* h, const float* packed, const float* ima
 int imcui_hip_r2d2_desc_probe(imcui_hip_t* h, const float* packed, const float* image, int H, int W, const int* xy, int n, float* descriptors,
                               void* ws, size_t ws_bytes, void* stream);
 
+/* ---- D2-Net / RoRD (zoo entries d2net, rord: `feature: d2net-ss` / `rord` + NN-mutual; imcui/hloc/extractors/d2net.py, rord.py) ---- */
+/* Packed weights of mihaidusmanu/d2-net's DenseFeatureExtractionModule (VGG-16 cut at conv4_3; replaces `_D2Net(model_file=...)`,
+ * d2net.py:32-34): tensors in imcui_hip_d2net_tensor_name order (`dense_feature_extraction.model.N.weight` / `.bias`, N = 0, 2, 5, 7, 10,
+ * 12, 14, 17, 19, 21).  The network, detector and pyramid are restated from their description (tests/d2net_reference.py): parity with
+ * upstream's code is NOT pinned; RoRD's lib/model_test.py is taken to be D2-Net's. */
+size_t imcui_hip_d2net_packed_floats(void);
+int imcui_hip_d2net_num_tensors(void);
+const char* imcui_hip_d2net_tensor_name(int i);
+int imcui_hip_d2net_pack_weights(const float* const* tensors, float* packed);
+/* Scratch of imcui_hip_d2net_forward for B images and the level list (lh, lw) [host, nlev] (IMAGE sizes of the levels) with room for kcap
+ * candidates per image; every level's 512-channel map stays in it until the descriptors are gathered. */
+size_t imcui_hip_d2net_workspace_bytes(int B, int nlev, const int* lh, const int* lw, int kcap);
+/* d2net.py:37-60 `_forward` (flip to BGR, x * 255 - mean, process_multiscale, the column swap, the argsort cut): image [dev, B,3,H,W] RGB
+ * in [0,1].  Levels [host, nlev <= 8]: the image sizes floor(H s) x floor(W s) in list order, evaluated by the BINDING in float64 (a
+ * level equal to (H, W) is the image itself, any other ATen's bilinear resize with align_corners=True of the normalised image).  Per
+ * level: the trunk -> f [h, w, 512] with (h, w) = (lh / 4 - 1, lw / 4 - 1), every one at least 1 or the call is refused; f += bilinear
+ * (align_corners=True) of the previous level's f; HardDetectionModule (channel-wise maximum, 3x3 maximum, edge test 7.2, det > 0)
+ * minus the pixels banned by earlier levels (nearest), HandcraftedLocalizationModule's step with |step| < 0.5, the four bilinear corners
+ * inside the map; candidates in (level, channel, row, column) order; key-point = ((p * 2 + 0.5) * 2 + 0.5) * (H / lh, W / lw) in
+ * float32, returned as (x, y); score = f[c, i, j] / (level index + 1); descriptor = F.normalize of the bilinear 512-vector at p.  More
+ * than max_keypoints (> 0; 0 = all): the highest scores stay, among equal scores the later candidates; output in ASCENDING (score,
+ * candidate) order, i.e. a STABLE argsort of upstream's concatenation (upstream's numpy argsort leaves ties open).
+ * use_relu: F.relu after conv4_3.  kcap = room for candidates per image; kout = rows per image of the outputs = kcap when
+ * max_keypoints == 0, else min(max_keypoints, kcap).  Outputs, first num_keypoints[b] rows valid, the rest zero:
+ *   keypoints [dev, B,kout,2] (x, y);  scores [dev, B,kout];  descriptors [dev, B,kout,512];  num_keypoints [dev, B] int32
+ *   status [dev, 1] int32 optional: 0 = fine, bit 1 = an image had more candidates than kcap (channels tied for the maximum); the
+ *   result is then that of the first kcap candidates
+ *   dbg_feat optional: [dev] the levels' maps after the sum, one after another, each [B, h, w, 512]
+ * Zero key-points is a valid result.  No host synchronisation. */
+int imcui_hip_d2net_forward(imcui_hip_t* h, const float* packed, const float* image, int B, int H, int W, int nlev, const int* lh, const int* lw,
+                            int use_relu, int max_keypoints, int kcap, int kout, float* keypoints, float* scores, float* descriptors,
+                            int* num_keypoints, int* status, float* dbg_feat, void* ws, size_t ws_bytes, void* stream);
+/* Test entry: detector, localization, candidate list, cut and descriptors (lib/model_test.py HardDetectionModule,
+ * HandcraftedLocalizationModule; lib/pyramid.py from `detections` on) on maps GIVEN by the caller, feat [dev, B,fh,fw,C] with C a
+ * multiple of 64 up to 512, as one level that is its own image (factors 1): descriptors [dev, B,kout,C], the rest as above. */
+/* Test entry: one small kernel of the trunk alone (the matrix layers have imcui_hip_conv_probe / imcui_hip_gemm_probe_f32).  op 0: layer 0
+ * with d2net.py:39-41 applied as the image is read, in = image [dev, B,3,H,W] -> out [dev, B,H,W,64] (model.0 + ReLU); op 1: model.4 / .9
+ * nn.MaxPool2d(2, 2), flooring, in [dev, B,H,W,C] -> out [dev, B,H/2,W/2,C]; op 2: model.16 nn.AvgPool2d(2, stride=1) -> [dev, B,H-1,W-1,C]. */
+int imcui_hip_d2net_layer_probe(imcui_hip_t* h, int op, const float* packed, const float* in, int B, int H, int W, int C, float* out, void* stream);
+size_t imcui_hip_d2net_probe_workspace_bytes(int B, int fh, int fw, int C, int kcap);
+int imcui_hip_d2net_detect_probe(imcui_hip_t* h, const float* feat, int B, int fh, int fw, int C, int max_keypoints, int kcap, int kout,
+                                 float* keypoints, float* scores, float* descriptors, int* num_keypoints, int* status, void* ws, size_t ws_bytes,
+                                 void* stream);
+
 /* ---- SIFT (zoo entry sift-lightglue, and `sift` + NN; imcui/hloc/extractors/sift.py, backend "opencv") ------------------- */
 /* OpenCV 4.x SIFT_create(contrastThreshold, nfeatures, edgeThreshold, nOctaveLayers = `layers`; sigma 1.6, first octave -1, float
  * pipeline) -> detectAndCompute (sift.py:61-78), then `filter_dog_point` (:19-52), the score top-k (:188-193) and
