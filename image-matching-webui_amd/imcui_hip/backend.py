@@ -926,6 +926,219 @@ class D2NetHIP:
         return out
 
 
+# ------------------------------------------------------------------ DeDoDe
+DEDODE_SCALES = (8, 4, 2, 1)
+DEDODE_FEATURE_CHANNELS = (512, 256, 128, 64)  # the encoders' maps in front of the pools, at DEDODE_SCALES
+DEDODE_MODELS = ("detector", "descriptor")
+DEDODE_MODEL_NAMES = {"detector": "dedode_detector_L.pth", "descriptor": "dedode_descriptor_B.pth"}  # the sizes csrc/dedode.hip serves
+# torchvision cfg "E" / "A" up to the fourth pool (vgg19_bn().features[:40], vgg11_bn().features[:22]); "M" = MaxPool2d(2, 2)
+DEDODE_ENCODERS = {"detector": (64, 64, "M", 128, 128, "M", 256, 256, 256, 256, "M", 512, 512, 512, 512, "M"),
+                   "descriptor": (64, "M", 128, "M", 256, 256, "M", 512, 512, "M")}  # fmt: skip
+DEDODE_DESC_DIM = 256
+
+
+def dedode_encoder_convs(model: str) -> list:
+    """(index in vgg.features, cin, cout) of every convolution; its BatchNorm is at index + 1."""
+    out, op, cin = [], 0, 3
+    for v in DEDODE_ENCODERS[model]:
+        if v == "M":
+            op += 1
+        else:
+            out.append((op, cin, v))
+            cin, op = v, op + 3
+    return out
+
+
+def dedode_dims(sd_detector: dict, sd_descriptor: dict) -> tuple:
+    """The ConvRefiner shapes of both state dicts, READ from the tensors: per model and scale (8, 4, 2, 1) `in` and `hidden` from
+    block1.0.weight, `out` from out_conv.weight and the number of hidden blocks from the keys -> the flat table the library takes."""
+    dims = []
+    for model, sd in zip(DEDODE_MODELS, (sd_detector, sd_descriptor)):
+        for s in DEDODE_SCALES:
+            p = f"decoder.layers.{s}."
+            for key in (p + "block1.0.weight", p + "out_conv.weight"):
+                if key not in sd or sd[key].dim() != 4:
+                    raise ImcuiHipError(f"DeDoDe {model} state dict: missing '{key}' (a [rows,cols,1,1] convolution): the refiner of scale {s} cannot be read")
+            hidden, cin = int(sd[p + "block1.0.weight"].shape[0]), int(sd[p + "block1.0.weight"].shape[1])
+            n = 0
+            while f"{p}hidden_blocks.{n}.0.weight" in sd:
+                n += 1
+            dims += [cin, hidden, int(sd[p + "out_conv.weight"].shape[0]), n]
+    dims = tuple(dims)
+    why = load_library().imcui_hip_dedode_dims_error(_dedode_cdims(dims)).decode()
+    if why:
+        raise ImcuiHipError(f"DeDoDe state dicts are not served: {why}")
+    return dims
+
+
+def _dedode_cdims(dims):
+    return (C.c_int * 32)(*dims)
+
+
+def dedode_tensor_names(dims) -> list[str]:
+    lib, cd = load_library(), _dedode_cdims(dims)
+    return [lib.imcui_hip_dedode_tensor_name(cd, i).decode() for i in range(lib.imcui_hip_dedode_num_tensors(cd))]
+
+
+def dedode_tensor_shapes(dims) -> dict:
+    shapes = {"density_taps": (51,)}
+
+    def bn(p, c):
+        for k in ("weight", "bias", "running_mean", "running_var"):
+            shapes[f"{p}.{k}"] = (c,)
+
+    def block(p, cin, c, depthwise):
+        shapes[p + ".0.weight"] = (c, 1, 5, 5) if depthwise else (c, cin, 1, 1)
+        shapes[p + ".0.bias"] = (c,)
+        bn(p + ".1", c)
+        shapes[p + ".3.weight"] = (c, c, 1, 1)
+        shapes[p + ".3.bias"] = (c,)
+
+    for m, model in enumerate(DEDODE_MODELS):
+        for op, cin, cout in dedode_encoder_convs(model):
+            shapes[f"{model}.encoder.layers.{op}.weight"] = (cout, cin, 3, 3)
+            shapes[f"{model}.encoder.layers.{op}.bias"] = (cout,)
+            bn(f"{model}.encoder.layers.{op + 1}", cout)
+        for i, s in enumerate(DEDODE_SCALES):
+            cin, hidden, out, n = dims[(m * 4 + i) * 4 : (m * 4 + i) * 4 + 4]
+            p = f"{model}.decoder.layers.{s}"
+            block(p + ".block1", cin, hidden, False)
+            for j in range(n):
+                block(f"{p}.hidden_blocks.{j}", hidden, hidden, True)
+            shapes[p + ".out_conv.weight"] = (out, hidden, 1, 1)
+            shapes[p + ".out_conv.bias"] = (out,)
+    return shapes
+
+
+def dedode_density_taps() -> torch.Tensor:
+    """sample_keypoints' `(-torch.linspace(-2, 2, steps=51) ** 2).exp()`, float32 on the host: the library filters with these bits."""
+    return torch.exp(-torch.linspace(-2, 2, 51, dtype=torch.float32) ** 2)
+
+
+def pack_dedode(sd_detector: dict, sd_descriptor: dict):
+    """The two DeDoDe state dicts -> (packed float32 buffer (host), dims).  Strict: every key is consumed exactly once and every shape is
+    checked against the widths read from the refiners; only the BatchNorm `num_batches_tracked` counters are skipped."""
+    lib = load_library()
+    dims = dedode_dims(sd_detector, sd_descriptor)
+    merged = {}
+    for model, sd in zip(DEDODE_MODELS, (sd_detector, sd_descriptor)):
+        merged.update({f"{model}.{k}": v for k, v in sd.items() if not k.endswith("num_batches_tracked")})
+    merged["density_taps"] = dedode_density_taps()
+    cd = _dedode_cdims(dims)
+    packed = _pack_named("DeDoDe", "the detector L / descriptor B", dedode_tensor_names(dims), dedode_tensor_shapes(dims), merged,
+                         lib.imcui_hip_dedode_packed_floats(cd), lib.imcui_hip_dedode_pack_weights, cd)  # fmt: skip
+    return packed, dims
+
+
+def dedode_check_args(image_shape, conf: dict) -> int:
+    """Refusals raised before anything is launched; returns num_keypoints."""
+    if conf.get("dense"):
+        raise ValueError("DeDoDe: `dense: True` (detect_dense) is not served by the HIP backend; the reference fixes it to False")
+    for key, model in (("model_detector_name", "detector"), ("model_descriptor_name", "descriptor")):
+        if conf.get(key, DEDODE_MODEL_NAMES[model]) != DEDODE_MODEL_NAMES[model]:
+            raise ValueError(f"DeDoDe: {key}={conf[key]!r} is not served, only {DEDODE_MODEL_NAMES[model]!r} (detector L with descriptor B)")
+    if len(image_shape) != 4 or image_shape[1] != 3:
+        raise ValueError(f"DeDoDe expects an RGB image [B,3,H,W], got shape {tuple(image_shape)}")
+    H, W = int(image_shape[2]), int(image_shape[3])
+    if H < 8 or W < 8 or H % 8 or W % 8:
+        raise ValueError(f"DeDoDe: image sides {H}x{W} must be multiples of 8 (every `dedode` conf of the reference resizes with dfactor 8)")
+    k = int(conf["max_keypoints"])
+    if not 1 <= k <= H * W:
+        raise ValueError(f"DeDoDe: max_keypoints={k} is out of range for a {H}x{W} image: topk over {H * W} pixels would raise")
+    return k
+
+
+class DeDoDeHIP:
+    def __init__(self):
+        self._ws = _Workspace()
+
+    def forward(self, packed: torch.Tensor, dims, image: torch.Tensor, conf: dict, want_maps: bool = False, want_dense: bool = False, kout: int | None = None):
+        """image [B,3,H,W] float32 RGB in [0,1] on the GPU -> fixed-stride outputs, no host synchronisation: keypoints [B,K,2] (x, y in
+        pixels), scores [B,K], descriptors [B,K,256] (not normalised), num_keypoints [B] int32 (= max_keypoints: every pixel is a
+        candidate), status [1] int32 (0), rows in descending score, ties by ascending pixel index; K = kout or max_keypoints, rows past
+        the count zero.  want_maps adds `logits` (the detector's accumulated logits at scales 8, 4, 2, 1, each [B,h,w]), `logp`,
+        `score` [B,H,W] and `desc2` [B,H/2,W/2,256]; want_dense adds `dense` [B,H,W,256], the grid the call otherwise never forms."""
+        k = dedode_check_args(tuple(image.shape), conf)
+        hd = get_handle(image.device)
+        _same_device(packed, image)
+        lib = hd.lib
+        image = image.contiguous().float()
+        B, _, H, W = image.shape
+        dev = image.device
+        kout = k if kout is None else int(kout)
+        if kout < k:
+            raise ValueError(f"DeDoDe: kout={kout} below max_keypoints={k}")
+        kpts, scores, desc, nk, status, out = _sparse_outputs(B, kout, DEDODE_DESC_DIM, dev)
+        cd = _dedode_cdims(dims)
+        sizes = [(H // s, W // s) for s in DEDODE_SCALES]
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)  # noqa: E731
+        logits = new(B * sum(a * b for a, b in sizes)) if want_maps else None
+        logp, score, desc2 = (new(B, H, W), new(B, H, W), new(B, H // 2, W // 2, DEDODE_DESC_DIM)) if want_maps else (None, None, None)
+        dense = new(B, H, W, DEDODE_DESC_DIM) if want_dense else None
+        with self._ws.use(lib.imcui_hip_dedode_workspace_bytes(cd, B, H, W, k), dev) as ws:
+            hd.launch(
+                lib.imcui_hip_dedode_forward, _ptr(packed), cd, _ptr(image), B, H, W, k, kout, _ptr(kpts), _ptr(scores), _ptr(desc), _ptr(nk), _ptr(status),
+                _ptr(logits), _ptr(logp), _ptr(score), _ptr(desc2), _ptr(dense), _ptr(ws), ws.numel(),
+            )  # fmt: skip
+        if want_maps:
+            out["logits"], off = [], 0
+            for a, b in sizes:
+                out["logits"].append(logits[off : off + B * a * b].view(B, a, b))
+                off += B * a * b
+            out.update(logp=logp, score=score, desc2=desc2)
+        if want_dense:
+            out["dense"] = dense
+        return out
+
+    @staticmethod
+    def layer_probe(op: str, inp: torch.Tensor, weights: torch.Tensor | None = None, packed: torch.Tensor | None = None, dims=None, model: str = "detector"):
+        """Test entry: one of the new kernels alone.  "conv0": image [B,3,H,W] -> [B,H,W,64] (needs `packed`, `dims`, `model`);
+        "depthwise": NHWC [B,H,W,C] with weights = cat([25,C] taps, [C] bias) -> ReLU(conv + bias); "bilinear2": NHWC -> [B,2H,2W,C];
+        "bicubic2": [B,H,W] -> [B,2H,2W]; "softmax_stats": [B,H,W] -> [B,2] = (max, log sum exp(l - max)); "filter51": [B,H,W] with
+        weights = the 51 taps -> [B,H,W]."""
+        code = {"conv0": 0, "depthwise": 1, "bilinear2": 2, "bicubic2": 3, "softmax_stats": 4, "filter51": 5}[op]
+        hd = get_handle(inp.device)
+        inp = inp.contiguous().float()
+        dev = inp.device
+        if code == 0:
+            B, _, H, W = inp.shape
+            Cc, shape = 64, (B, H, W, 64)
+        elif code in (1, 2):
+            B, H, W, Cc = inp.shape
+            shape = (B, H, W, Cc) if code == 1 else (B, 2 * H, 2 * W, Cc)
+        else:
+            B, H, W = inp.shape
+            Cc = 1
+            shape = {3: (B, 2 * H, 2 * W), 4: (2 * B + 2 * B * ((H * W + 4095) // 4096),), 5: (2, B, H, W)}[code]
+        out = torch.empty(shape, dtype=torch.float32, device=dev)
+        if weights is not None:
+            weights = weights.contiguous().float().to(dev)
+        cd = _dedode_cdims(dims) if dims is not None else None
+        hd.launch(hd.lib.imcui_hip_dedode_layer_probe, code, _ptr(packed), cd, DEDODE_MODELS.index(model), _ptr(weights), _ptr(inp), B, H, W, Cc, _ptr(out))
+        if code == 4:
+            return out[: 2 * B].view(B, 2)
+        return out[0] if code == 5 else out
+
+    def select_probe(self, map_: torch.Tensor, k: int, mode: str = "logp", kout: int | None = None):
+        """Test entry: the selection code on the caller's maps [B,H,W].  mode "logp": p = exp(log p), filter, score, cut, rows; mode
+        "score": cut and rows on the given score map -> keypoints, scores, num_keypoints and the score map used."""
+        hd = get_handle(map_.device)
+        lib = hd.lib
+        map_ = map_.contiguous().float()
+        B, H, W = map_.shape
+        dev = map_.device
+        kout = k if kout is None else int(kout)
+        kpts = torch.empty((B, kout, 2), dtype=torch.float32, device=dev)
+        scores = torch.empty((B, kout), dtype=torch.float32, device=dev)
+        nk = torch.empty((B,), dtype=torch.int32, device=dev)
+        smap = torch.empty((B, H, W), dtype=torch.float32, device=dev)
+        taps = dedode_density_taps().to(dev)
+        with self._ws.use(lib.imcui_hip_dedode_select_probe_workspace_bytes(B, H, W, k), dev) as ws:
+            hd.launch(lib.imcui_hip_dedode_select_probe, {"logp": 0, "score": 1}[mode], _ptr(taps), _ptr(map_), B, H, W, k, kout, _ptr(kpts), _ptr(scores),
+                      _ptr(nk), _ptr(smap), _ptr(ws), ws.numel())  # fmt: skip
+        return {"keypoints": kpts, "scores": scores, "num_keypoints": nk, "score": smap}
+
+
 # ------------------------------------------------------------------ SIFT
 SIFT_LAYERS =(3, 4, 5)  # nOctaveLayers (the wrapper's `num_octaves`) csrc/sift.hip is written for: blur radius at most 13
 

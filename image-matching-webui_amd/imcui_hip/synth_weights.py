@@ -780,3 +780,68 @@ def d2net_state_dict(seed: int = 0, checkpoint: bool = False) -> dict:
         sd[f"dense_feature_extraction.model.{op}.weight"] = torch.randn(cout, cin, 3, 3, generator=g) * math.sqrt(2.0 / (cin * 9))
         sd[f"dense_feature_extraction.model.{op}.bias"] = torch.randn(cout, generator=g) * 0.1
     return {"model": sd} if checkpoint else sd
+
+
+# torchvision cfg "E" / "A" up to the fourth pool: Parskatt/DeDoDe encoders VGG19 (vgg19_bn().features[:40]) and VGG (size "11",
+# vgg11_bn().features[:22]); "M" = MaxPool2d(2, 2)
+DEDODE_ENCODERS = {"detector": (64, 64, "M", 128, 128, "M", 256, 256, 256, 256, "M", 512, 512, 512, 512, "M"),
+                   "descriptor": (64, "M", 128, "M", 256, 256, "M", 512, 512, "M")}  # fmt: skip
+# ConvRefiner(in, hidden, out) per scale 8, 4, 2, 1 and the number of hidden blocks: dedode_detector_L / dedode_descriptor_B as recalled
+# from upstream's factory functions (out = context for the next scale + 1 key-point logit / 256 description channels)
+DEDODE_REFINERS = {"detector": (8, ((512, 512, 256 + 1), (512, 256, 128 + 1), (256, 128, 64 + 1), (128, 64, 1 + 1))),
+                   "descriptor": (5, ((512, 512, 256 + 256), (512, 256, 128 + 256), (256, 64, 32 + 256), (96, 32, 1 + 256)))}  # fmt: skip
+
+
+def dedode_state_dicts(seed: int = 0, logit_gain: float = 0.3, refiners: dict | None = None) -> tuple:
+    """Seeded DeDoDe weights -> (detector state dict, descriptor state dict) under upstream's key names (`encoder.layers.N.*` of the
+    truncated torchvision VGG-BN, `decoder.layers.S.{block1,hidden_blocks.I}.{0,1,3}.*`, `.out_conv.*`), the BatchNorm
+    `num_batches_tracked` counters included (a loader has to skip them).  BatchNorm statistics are NOT the identity.  Convolutions in
+    front of a ReLU'd input carry sqrt(2 / fan_in), the depth-wise 5x5 (which sees a linear layer's output) sqrt(1 / 25), so a
+    refiner's eight residual-free blocks neither grow nor fade and nothing comes near the 65504 of the split mode's f16 planes; the
+    logit rows of every out_conv carry `logit_gain` / sqrt(hidden): four scales add up to key-point logits a few units wide, which the
+    soft-max over the image turns into scores spread over decades instead of one saturated peak.  `refiners` replaces the table of
+    widths (tests: a checkpoint with other widths must load)."""
+    g = torch.Generator().manual_seed(seed)
+    refiners = refiners or DEDODE_REFINERS
+
+    def rn(*shape, scale=1.0):
+        return torch.randn(*shape, generator=g) * scale
+
+    def bn(sd, p, c):
+        sd[p + ".weight"] = 1.0 + rn(c, scale=0.1)
+        sd[p + ".bias"] = rn(c, scale=0.1)
+        sd[p + ".running_mean"] = rn(c, scale=0.2)
+        sd[p + ".running_var"] = 0.5 + torch.rand(c, generator=g)
+        sd[p + ".num_batches_tracked"] = torch.tensor(1000, dtype=torch.long)
+
+    def block(sd, p, cin, c, depthwise):
+        sd[p + ".0.weight"] = rn(c, 1, 5, 5, scale=0.2) if depthwise else rn(c, cin, 1, 1, scale=math.sqrt(2.0 / cin))
+        sd[p + ".0.bias"] = rn(c, scale=0.1)
+        bn(sd, p + ".1", c)
+        sd[p + ".3.weight"] = rn(c, c, 1, 1, scale=math.sqrt(2.0 / c))
+        sd[p + ".3.bias"] = rn(c, scale=0.1)
+
+    out = []
+    for model in ("detector", "descriptor"):
+        sd, op, cin = {}, 0, 3
+        for v in DEDODE_ENCODERS[model]:
+            if v == "M":
+                op += 1
+                continue
+            sd[f"encoder.layers.{op}.weight"] = rn(v, cin, 3, 3, scale=math.sqrt(2.0 / (cin * 9)))
+            sd[f"encoder.layers.{op}.bias"] = rn(v, scale=0.1)
+            bn(sd, f"encoder.layers.{op + 1}", v)
+            cin, op = v, op + 3
+        nblk, table = refiners[model]
+        P = 1 if model == "detector" else 256
+        for s, (rin, hidden, rout) in zip((8, 4, 2, 1), table):
+            p = f"decoder.layers.{s}"
+            block(sd, p + ".block1", rin, hidden, False)
+            for i in range(nblk):
+                block(sd, f"{p}.hidden_blocks.{i}", hidden, hidden, True)
+            w = rn(rout, hidden, 1, 1, scale=1.0 / math.sqrt(hidden))
+            w[:P] *= logit_gain
+            sd[p + ".out_conv.weight"] = w
+            sd[p + ".out_conv.bias"] = rn(rout, scale=0.1)
+        out.append(sd)
+    return tuple(out)

@@ -306,6 +306,53 @@ int imcui_hip_d2net_detect_probe(imcui_hip_t* h, const float* feat, int B, int f
                                  float* keypoints, float* scores, float* descriptors, int* num_keypoints, int* status, void* ws, size_t ws_bytes,
                                  void* stream);
 
+/* ---- DeDoDe (zoo entry dedode: `feature: dedode` + Dual-Softmax; imcui/hloc/extractors/dedode.py) ----------------------- */
+/* dedode_detector_L (vgg19_bn encoder) and dedode_descriptor_B (vgg11_bn encoder) of Parskatt/DeDoDe, each with a decoder of four
+ * ConvRefiners (scales 8, 4, 2, 1).  The refiners' shapes are READ from the checkpoint by the binding and handed over as
+ * dims [host, 2 models (detector, descriptor)][4 scales (8, 4, 2, 1)][in, hidden, out, hidden blocks]: hidden a multiple of 32 up to
+ * 512, 1..16 hidden blocks, in = feature channels (512, 256, 128, 64) + the context the coarser scale hands down (out - P there, a
+ * multiple of 32), P = 1 key-point logit (detector) or 256 description channels (descriptor).  imcui_hip_dedode_dims_error says why a
+ * dims table is refused (empty string: served).  Tensors in imcui_hip_dedode_tensor_name order: both state dicts under the prefixes
+ * `detector.` / `descriptor.` (`encoder.layers.N.*`, `decoder.layers.S.block1.{0,1,3}.*`, `.hidden_blocks.I.{0,1,3}.*`, `.out_conv.*`;
+ * BatchNorm as weight, bias, running_mean, running_var and folded here in float32), then `density_taps` [51] =
+ * exp(-linspace(-2, 2, 51)^2) as the binding's float32 evaluates it.  The networks are restated from their description
+ * (tests/dedode_reference.py): parity with upstream's code is NOT pinned. */
+size_t imcui_hip_dedode_packed_floats(const int* dims);
+int imcui_hip_dedode_num_tensors(const int* dims);
+const char* imcui_hip_dedode_tensor_name(const int* dims, int i);
+const char* imcui_hip_dedode_dims_error(const int* dims);
+int imcui_hip_dedode_pack_weights(const int* dims, const float* const* tensors, float* packed);
+size_t imcui_hip_dedode_workspace_bytes(const int* dims, int B, int H, int W, int k);
+/* dedode.py:55-86 `_forward`: image [dev, B,3,H,W] RGB in [0,1], H and W multiples of 8 (every dedode conf resizes with dfactor 8) ->
+ * transforms.Normalize, detector.detect(num_keypoints = k): p = soft-max of the logits over the image, density = the separable 51-tap
+ * filter of (p + 1e-6) * 10000 (rows, then columns, zero padding), score = p * (density + 1e-8)^-1/2, the k highest scores (1 <= k <=
+ * H W; equal scores: the lower flat index first), key-points at the pixel centres x = (2 j + 1) / W - 1; descriptor.describe_keypoints:
+ * bilinear grid_sample (align_corners=False) of the 256-channel description grid there, NOT normalised; to_pixel_coords.  Outputs, rows
+ * in descending score, the first k valid and rows k .. kout zero:
+ *   keypoints [dev, B,kout,2] (x, y in pixels);  scores [dev, B,kout];  descriptors [dev, B,kout,256];  num_keypoints [dev, B] int32 (= k)
+ *   status [dev, 1] int32 optional: 0 (every pixel is a candidate, no list can overflow)
+ *   dbg_logits optional [dev]: the detector's accumulated logits of the scales 8, 4, 2, 1, one after another, each [B, h, w]
+ *   dbg_logp / dbg_score optional [dev, B,H,W];  dbg_desc2 optional [dev, B,H/2,W/2,256]: the description grid accumulated down to 1/2
+ *   dbg_dense optional [dev, B,H,W,256]: the full-resolution description grid, which the call otherwise never forms (tests)
+ * No host synchronisation. */
+int imcui_hip_dedode_forward(imcui_hip_t* h, const float* packed, const int* dims, const float* image, int B, int H, int W, int k, int kout,
+                             float* keypoints, float* scores, float* descriptors, int* num_keypoints, int* status, float* dbg_logits, float* dbg_logp,
+                             float* dbg_score, float* dbg_desc2, float* dbg_dense, void* ws, size_t ws_bytes, void* stream);
+/* Test entry: one of the new kernels alone (the matrix layers have imcui_hip_conv_probe / imcui_hip_gemm_probe_f32).  op 0: layer 0 of
+ * `model` (0 detector, 1 descriptor) with Normalize applied as the image is read, in = image [dev, B,3,H,W] -> out [dev, B,H,W,64]
+ * (needs packed and dims); op 1: depth-wise 5x5 (pad 2) + bias + ReLU, in [dev, B,H,W,C], C a multiple of 32, wts [dev] = [25 taps][C]
+ * then [C] bias; op 2: bilinear x2 (align_corners=False), in [dev, B,H,W,C] -> [dev, B,2H,2W,C]; op 3: bicubic x2 of the planes
+ * in [dev, B,H,W]; op 4: soft-max statistics of in [dev, B,H*W] -> out [dev, 2 B + 2 B chunks]: (max, log sum exp(l - max)) per image,
+ * then scratch; op 5: the separable 51-tap filter of the planes in [dev, B,H,W], wts = the taps, out [dev, 2,B,H,W]: the result, then
+ * the row pass. */
+int imcui_hip_dedode_layer_probe(imcui_hip_t* h, int op, const float* packed, const int* dims, int model, const float* wts, const float* in, int B, int H,
+                                 int W, int C, float* out, void* stream);
+/* Test entry: the selection code on maps GIVEN by the caller.  mode 0: map = log p [dev, B,H,W] -> p = exp(log p), filter, score, cut,
+ * rows; mode 1: map = the score map itself -> cut and rows (crafted equal scores).  score_out optional [dev, B,H,W]. */
+size_t imcui_hip_dedode_select_probe_workspace_bytes(int B, int H, int W, int k);
+int imcui_hip_dedode_select_probe(imcui_hip_t* h, int mode, const float* taps, const float* map, int B, int H, int W, int k, int kout, float* keypoints,
+                                  float* scores, int* num_keypoints, float* score_out, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- SIFT (zoo entry sift-lightglue, and `sift` + NN; imcui/hloc/extractors/sift.py, backend "opencv") ------------------- */
 /* OpenCV 4.x SIFT_create(contrastThreshold, nfeatures, edgeThreshold, nOctaveLayers = `layers`; sigma 1.6, first octave -1, float
  * pipeline) -> detectAndCompute (sift.py:61-78), then `filter_dog_point` (:19-52), the score top-k (:188-193) and
