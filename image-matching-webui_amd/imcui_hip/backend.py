@@ -926,6 +926,141 @@ class D2NetHIP:
         return out
 
 
+# ------------------------------------------------------------------ NetVLAD
+# (cin, cout, index in torchvision's vgg16().features): VGG-16 to conv5_3, csrc/netvlad.hip
+NETVLAD_LAYERS = ((3, 64, 0), (64, 64, 2), (64, 128, 5), (128, 128, 7), (128, 256, 10), (256, 256, 12), (256, 256, 14), (256, 512, 17), (512, 512, 19),
+                  (512, 512, 21), (512, 512, 24), (512, 512, 26), (512, 512, 28))  # fmt: skip
+NETVLAD_DIM, NETVLAD_CLUSTERS, NETVLAD_WHITENED = 512, 64, 4096
+NETVLAD_MIN_SIDE = 16  # four flooring 2x2 pools: a smaller side leaves an empty conv5_3 map
+
+
+def netvlad_tensor_names(whiten: bool = True) -> list[str]:
+    lib = load_library()
+    return [lib.imcui_hip_netvlad_tensor_name(int(whiten), i).decode() for i in range(lib.imcui_hip_netvlad_num_tensors(int(whiten)))]
+
+
+def netvlad_tensor_shapes(whiten: bool = True) -> dict:
+    """The state-dict shapes of the reference's `NetVLAD` module (imcui/hloc/extractors/netvlad.py:64-114) + `preprocess.mean` (:118)."""
+    shapes = {}
+    for cin, cout, op in NETVLAD_LAYERS:
+        shapes[f"backbone.{op}.weight"] = (cout, cin, 3, 3)
+        shapes[f"backbone.{op}.bias"] = (cout,)
+    shapes["netvlad.score_proj.weight"] = (NETVLAD_CLUSTERS, NETVLAD_DIM, 1)
+    shapes["netvlad.centers"] = (NETVLAD_DIM, NETVLAD_CLUSTERS)
+    shapes["preprocess.mean"] = (3,)
+    if whiten:
+        shapes["whiten.weight"] = (NETVLAD_WHITENED, NETVLAD_DIM * NETVLAD_CLUSTERS)
+        shapes["whiten.bias"] = (NETVLAD_WHITENED,)
+    return shapes
+
+
+def pack_netvlad(state_dict: dict, whiten: bool | None = None) -> torch.Tensor:
+    """The reference module's state dict (+ `preprocess.mean`) -> packed float32 buffer (host).  whiten None: by the presence of
+    `whiten.weight`.  Strict: every key is consumed exactly once, every shape checked.  The whitening matrix (512 MB) is packed as float32."""
+    lib = load_library()
+    sd = dict(state_dict)
+    if whiten is None:
+        whiten = "whiten.weight" in sd
+    w = int(bool(whiten))
+    return _pack_named("NetVLAD", "the reference's NetVLAD module", netvlad_tensor_names(bool(w)), netvlad_tensor_shapes(bool(w)), sd,
+                       lib.imcui_hip_netvlad_packed_floats(w), lib.imcui_hip_netvlad_pack_weights, w)
+
+
+def netvlad_check_args(image_shape) -> None:
+    """Refusals raised before anything is launched (the library refuses the same)."""
+    if len(image_shape) != 4 or image_shape[1] != 3:
+        raise ValueError(f"NetVLAD expects an RGB image [B,3,H,W], got shape {tuple(image_shape)}")
+    if min(image_shape[2], image_shape[3]) < NETVLAD_MIN_SIDE:
+        raise ValueError(f"NetVLAD: a {image_shape[2]}x{image_shape[3]} image has an empty conv5_3 map: every side needs at least {NETVLAD_MIN_SIDE} pixels")
+
+
+class NetVLADHIP:
+    def __init__(self):
+        self._ws = _Workspace()
+
+    def forward_batched(self, packed: torch.Tensor, image: torch.Tensor, whiten: bool, want_map: bool = False) -> dict:
+        """image [B,3,H,W] float32 RGB in [0,1] on the GPU -> {"global_descriptor": [B,4096] (whiten) or [B,32768]}, unit norm; no host
+        synchronisation, graph-capturable.  want_map adds `backbone` [B,H//16,W//16,512], the conv5_3 map (NHWC)."""
+        netvlad_check_args(tuple(image.shape))
+        hd = get_handle(image.device)
+        _same_device(packed, image)
+        lib = hd.lib
+        w = int(bool(whiten))
+        if packed.numel() != lib.imcui_hip_netvlad_packed_floats(w):
+            raise ImcuiHipError(f"NetVLAD: the packed buffer holds {packed.numel()} floats, whiten={bool(w)} needs {lib.imcui_hip_netvlad_packed_floats(w)}")
+        image = image.contiguous().float()
+        B, Cc, H, W = image.shape
+        dev = image.device
+        desc = torch.empty((B, NETVLAD_WHITENED if w else NETVLAD_DIM * NETVLAD_CLUSTERS), dtype=torch.float32, device=dev)
+        fmap = torch.empty((B, H // 16, W // 16, NETVLAD_DIM), dtype=torch.float32, device=dev) if want_map else None
+        with self._ws.use(lib.imcui_hip_netvlad_workspace_bytes(B, H, W, w), dev) as ws:
+            hd.launch(lib.imcui_hip_netvlad_forward, _ptr(packed), _ptr(image), B, Cc, H, W, w, _ptr(desc), _ptr(fmap), _ptr(ws), ws.numel())
+        out = {"global_descriptor": desc}
+        if want_map:
+            out["backbone"] = fmap
+        return out
+
+    def layer_probe(self, op: str, inp: torch.Tensor, packed: torch.Tensor | None = None) -> torch.Tensor:
+        """Test entry: one stage alone.  "conv0": image [B,3,H,W] -> [B,H,W,64]; "maxpool": NHWC [B,H,W,C] -> [B,H//2,W//2,C]; "vlad": maps
+        [B,h,w,512] -> [B,32768] (pre-normalisation, assignment, aggregation, both normalisations); "conv5_3": maps [B,h,w,512] ->
+        [B,h,w,512], the last convolution (no ReLU) as the forward launches it (K summed in groups), in the handle's arithmetic mode.
+        All but maxpool need `packed`."""
+        code = {"conv0": 0, "maxpool": 1, "vlad": 2, "conv5_3": 3}[op]
+        hd = get_handle(inp.device)
+        lib = hd.lib
+        inp = inp.contiguous().float()
+        if code == 0:
+            B, _, H, W = inp.shape
+            Cc, shape = 64, (B, H, W, 64)
+        else:
+            B, H, W, Cc = inp.shape
+            shape = (B, H // 2, W // 2, Cc) if code == 1 else (B, NETVLAD_DIM * NETVLAD_CLUSTERS) if code == 2 else (B, H, W, Cc)
+        out = torch.empty(shape, dtype=torch.float32, device=inp.device)
+        with self._ws.use(max(256, lib.imcui_hip_netvlad_probe_workspace_bytes(B, H * W) if code >= 2 else 256), inp.device) as ws:
+            hd.launch(lib.imcui_hip_netvlad_layer_probe, code, _ptr(packed), _ptr(inp), B, H, W, Cc, _ptr(out), _ptr(ws), ws.numel())
+        return out
+
+    def whiten_probe(self, weight: torch.Tensor, bias: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
+        """Test entry: normalize(weight [out,in] @ x [B,in] + bias) through the split-K skinny GEMM and its fold -> [B,out]."""
+        hd = get_handle(x.device)
+        lib = hd.lib
+        weight, bias, x = weight.contiguous().float(), bias.contiguous().float(), x.contiguous().float()
+        (out_dim, in_dim), B = weight.shape, x.shape[0]
+        if x.shape[1] != in_dim or bias.shape != (out_dim,):
+            raise ValueError(f"whiten_probe: weight {tuple(weight.shape)}, bias {tuple(bias.shape)}, x {tuple(x.shape)}")
+        out = torch.empty((B, out_dim), dtype=torch.float32, device=x.device)
+        with self._ws.use(lib.imcui_hip_netvlad_whiten_workspace_bytes(B, in_dim, out_dim), x.device) as ws:
+            hd.launch(lib.imcui_hip_netvlad_whiten_probe, _ptr(weight), _ptr(bias), _ptr(x), B, in_dim, out_dim, _ptr(out), _ptr(ws), ws.numel())
+        return out
+
+
+_retrieval_ws = _Workspace()
+
+
+def retrieval_topk(query: torch.Tensor, db: torch.Tensor, num_select: int, invalid: torch.Tensor | None = None, min_score: float | None = None):
+    """pairs_from_retrieval.py:109 + :56-66 on the device: query [Q,D], db [N,D] -> (indices [Q,num_select] int32, scores [Q,num_select]):
+    the `num_select` highest similarities of every row in descending order, an `invalid` entry (bool / uint8 [Q,N]) or one below
+    `min_score` counting as -inf; equal scores by ascending database index; slots past N hold -1 / -inf.  The score matrix is not returned."""
+    hd = get_handle(query.device)
+    lib = hd.lib
+    _same_device(db, query)
+    query, db = query.contiguous().float(), db.contiguous().float()
+    (Q, D), N = query.shape, db.shape[0]
+    if db.dim() != 2 or db.shape[1] != D or num_select < 1:
+        raise ValueError(f"retrieval_topk: query {tuple(query.shape)}, db {tuple(db.shape)}, num_select {num_select}")
+    inv = None
+    if invalid is not None:
+        if tuple(invalid.shape) != (Q, N):
+            raise ValueError(f"retrieval_topk: invalid has shape {tuple(invalid.shape)}, expected {(Q, N)}")
+        inv = invalid.to(query.device).to(torch.uint8).contiguous()
+    idx = torch.empty((Q, num_select), dtype=torch.int32, device=query.device)
+    sc = torch.empty((Q, num_select), dtype=torch.float32, device=query.device)
+    with _retrieval_ws.use(lib.imcui_hip_retrieval_topk_workspace_bytes(Q, N), query.device) as ws:
+        hd.launch(lib.imcui_hip_retrieval_topk, _ptr(query), _ptr(db), Q, N, D, _ptr(inv), int(min_score is not None),
+                  float(min_score or 0.0), int(num_select), _ptr(idx), _ptr(sc), _ptr(ws), ws.numel())  # fmt: skip
+    return idx, sc
+
+
 # ------------------------------------------------------------------ DeDoDe
 DEDODE_SCALES = (8, 4, 2, 1)
 DEDODE_FEATURE_CHANNELS = (512, 256, 128, 64)  # the encoders' maps in front of the pools, at DEDODE_SCALES

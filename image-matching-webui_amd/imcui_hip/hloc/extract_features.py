@@ -37,6 +37,15 @@ from .utils.h5lite import open_h5
 GLOBS = ["*.jpg", "*.png", "*.jpeg", "*.JPG", "*.PNG"]  # ImageDataset.default_conf["globs"]
 DEFAULT_PREPROCESSING = {"globs": GLOBS, "grayscale": False, "resize_max": None, "force_resize": False, "interpolation": "cv2_area"}
 
+# the retrieval conf of imcui/hloc/configs/extractors.py:372-376 (the SfM tab's default `retrieval_name`)
+confs = {
+    "netvlad": {
+        "output": "global-feats-netvlad",
+        "model": {"name": "netvlad"},
+        "preprocessing": {"resize_max": 1024},
+    },
+}
+
 
 def list_h5_names(path) -> List[str]:
     """Names of the groups that hold datasets (imcui/hloc/utils/io.py:24-37)."""
@@ -285,13 +294,32 @@ def main(conf: Dict, image_dir: Path, export_dir: Optional[Path] = None, as_half
     noise = getattr(model, "detection_noise", 1)
     rgb = bool(getattr(model, "takes_rgb", False))  # extractors that take colour (DISK) get [B,3,h,w] with `grayscale: False`
 
+    is_global = bool(getattr(model, "returns_global_descriptor", False))  # retrieval models (NetVLAD): `global_descriptor`, no key-points
+
     pending: Dict[tuple, list] = {}  # preprocessed (h, w) -> [(name, image tensor, original size)]
+
+    def flush_global(items, desc):
+        """A model that returns `global_descriptor` (:206-235 with no key-points in `pred`): one group per image with the descriptor
+        (float16 under `as_half`, like every float32 entry) and `image_size`; no `keypoints`, so no `uncertainty` attribute."""
+        with open_h5(feature_path, "a") as fd:
+            for b, (name, _, original_size) in enumerate(items):
+                pred = {"global_descriptor": desc[b], "image_size": original_size}
+                if as_half:
+                    pred = {k: (v.astype(np.float16) if v.dtype == np.float32 else v) for k, v in pred.items()}
+                if name in fd:
+                    del fd[name]
+                grp = fd.create_group(name)
+                for k, v in pred.items():
+                    grp.create_dataset(k, data=v)
 
     def flush(key):
         items = pending.pop(key, [])
         if not items:
             return
         batch = torch.cat([it[1] for it in items], 0)
+        if is_global:
+            flush_global(items, model.forward_batched(batch)["global_descriptor"].cpu().numpy())
+            return
         if hasattr(model, "forward_checked"):  # counts + selection status in one copy; capacity overflow retried, failures raise
             out, counts = model.forward_checked(batch)
         else:

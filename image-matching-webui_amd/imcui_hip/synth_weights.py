@@ -845,3 +845,59 @@ def dedode_state_dicts(seed: int = 0, logit_gain: float = 0.3, refiners: dict | 
             sd[p + ".out_conv.bias"] = rn(rout, scale=0.1)
         out.append(sd)
     return tuple(out)
+
+
+# (cin, cout, index in torchvision's vgg16().features): VGG-16 to conv5_3, imcui/hloc/extractors/netvlad.py:64-68
+NETVLAD_LAYERS = ((3, 64, 0), (64, 64, 2), (64, 128, 5), (128, 128, 7), (128, 256, 10), (256, 256, 12), (256, 256, 14), (256, 512, 17), (512, 512, 19),
+                  (512, 512, 21), (512, 512, 24), (512, 512, 26), (512, 512, 28))  # fmt: skip
+NETVLAD_MODEL_NAMES = ("VGG16-NetVLAD-Pitts30K", "VGG16-NetVLAD-TokyoTM")
+
+
+def netvlad_synth_state(seed: int = 0, whiten: bool = True, score_gain: float = 6.0) -> dict:
+    """Seeded NetVLAD weights under the names of the reference module's state dict (`backbone.N.{weight,bias}`, `netvlad.score_proj.weight`
+    [64,512,1], `netvlad.centers` [512,64], `whiten.{weight,bias}`) plus `preprocess.mean` [3] (the checkpoint's averageImage), float32 torch
+    tensors.  numpy's default_rng, one stream in a fixed order with the whitening LAST: the 134 M whitening weights (512 MB) are regenerated
+    wherever they are needed and never stored, and `whiten=False` gives the same other tensors.  Kaiming-scaled 3x3 convolutions; the score
+    rows have norm `score_gain`, so that a unit-norm pixel gets scores of that spread and the soft-max is sharp but not one-hot; centers of
+    the size of a unit vector's entries."""
+    import numpy as np
+
+    rng = np.random.default_rng(seed)
+    sd = {}
+    for cin, cout, op in NETVLAD_LAYERS:
+        sd[f"backbone.{op}.weight"] = rng.standard_normal((cout, cin, 3, 3), dtype=np.float32) * np.float32(math.sqrt(2.0 / (cin * 9)))
+        sd[f"backbone.{op}.bias"] = rng.standard_normal(cout, dtype=np.float32) * np.float32(0.1)
+    sd["netvlad.score_proj.weight"] = rng.standard_normal((64, 512, 1), dtype=np.float32) * np.float32(score_gain)
+    sd["netvlad.centers"] = rng.standard_normal((512, 64), dtype=np.float32) * np.float32(1.0 / math.sqrt(512.0))
+    sd["preprocess.mean"] = np.array([122.68, 116.67, 104.01], dtype=np.float32)
+    if whiten:
+        sd["whiten.weight"] = rng.standard_normal((4096, 32768), dtype=np.float32) * np.float32(1.0 / math.sqrt(32768.0))
+        sd["whiten.bias"] = rng.standard_normal(4096, dtype=np.float32) * np.float32(0.01)
+    return {k: torch.from_numpy(v) for k, v in sd.items()}
+
+
+def netvlad_write_mat(path, state: dict) -> None:
+    """`state` (netvlad_synth_state) as the MATLAB checkpoint that imcui/hloc/extractors/netvlad.py:76-120 parses: `net.layers` a 1-D cell of
+    structs with a `weights` cell -- layers 0..28 line up with the truncated VGG `features` (convolutions [S,S,IN,OUT] + bias), layer 30 the
+    score [D,K] / NEGATED centre [D,K] pair, layer 33 the whitening pair ([1,1,IN,OUT], [OUT]; empty without whitening) -- and
+    `net.meta.normalization.averageImage` [2,2,3] (an image of the mean colour, read at [0, 0]).  Data only; needs scipy."""
+    import numpy as np
+    from scipy.io import savemat
+
+    def cell(*arrs):
+        c = np.empty(len(arrs), dtype=object)  # filled element by element: np.array([a, b], dtype=object) of equal shapes collapses
+        for i, a in enumerate(arrs):
+            c[i] = a
+        return c
+
+    convs = {op: (state[f"backbone.{op}.weight"].numpy(), state[f"backbone.{op}.bias"].numpy()) for _, _, op in NETVLAD_LAYERS}
+    layers = np.empty(34, dtype=object)
+    for i in range(34):
+        layers[i] = {"weights": cell()}
+    for op, (w, b) in convs.items():
+        layers[op] = {"weights": cell(np.ascontiguousarray(w.transpose(2, 3, 1, 0)), b)}
+    layers[30] = {"weights": cell(np.ascontiguousarray(state["netvlad.score_proj.weight"].numpy()[:, :, 0].T), -state["netvlad.centers"].numpy())}
+    if "whiten.weight" in state:
+        layers[33] = {"weights": cell(state["whiten.weight"].numpy().T[None, None], state["whiten.bias"].numpy())}
+    mean = np.ascontiguousarray(np.broadcast_to(state["preprocess.mean"].numpy().reshape(1, 1, 3), (2, 2, 3)))  # (loadmat squeezes a [1,1,3] to [3])
+    savemat(str(path), {"net": {"layers": layers, "meta": {"normalization": {"averageImage": mean}}}})

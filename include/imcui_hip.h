@@ -353,7 +353,47 @@ size_t imcui_hip_dedode_select_probe_workspace_bytes(int B, int H, int W, int k)
 int imcui_hip_dedode_select_probe(imcui_hip_t* h, int mode, const float* taps, const float* map, int B, int H, int W, int k, int kout, float* keypoints,
                                   float* scores, int* num_keypoints, float* score_out, void* ws, size_t ws_bytes, void* stream);
 
-/* ---- SIFT (zoo entry sift-lightglue, and `sift` + NN; imcui/hloc/extractors/sift.py, backend "opencv") ------------------- */
+/* ---- NetVLAD (retrieval_zoo entry netvlad; imcui/hloc/extractors/netvlad.py, imcui/hloc/pairs_from_retrieval.py) ---------------------- */
+/* Packed weights of the reference's `NetVLAD` module (replaces the MATLAB parsing of netvlad.py:76-120 as far as the device is
+ * concerned: the plugin parses the .mat, this packs the result): tensors in imcui_hip_netvlad_tensor_name order -- `backbone.N.weight` /
+ * `.bias` (N = 0, 2, 5, 7, 10, 12, 14, 17, 19, 21, 24, 26, 28 of torchvision's vgg16().features), `netvlad.score_proj.weight` [64,512,1],
+ * `netvlad.centers` [512,64], `preprocess.mean` [3] (netvlad.py:118) and, with whiten != 0, `whiten.weight` [4096,32768] / `whiten.bias`.
+ * The whitening matrix stays float32 (no f16 planes); without whitening it is neither packed nor launched. */
+size_t imcui_hip_netvlad_packed_floats(int whiten);
+int imcui_hip_netvlad_num_tensors(int whiten);
+const char* imcui_hip_netvlad_tensor_name(int whiten, int i);
+int imcui_hip_netvlad_pack_weights(int whiten, const float* const* tensors, float* packed);
+size_t imcui_hip_netvlad_workspace_bytes(int B, int H, int W, int whiten);
+/* netvlad.py:122-146 `_forward`: image [dev, B,C,H,W] RGB in [0,1] -> descriptor [dev, B,4096] (whiten) or [dev, B,32768], unit norm.
+ * clamp(x * 255, 0, 255) - mean as the image is read, VGG-16 to conv5_3 without its ReLU and pool (:66-68), F.normalize per pixel (:138),
+ * NetVLADLayer.forward (:27-38), `self.whiten` and the final F.normalize (:143-144).  Refused with a message: C != 3, a side below 16
+ * (empty conv5_3 map).  dbg_feat optional: [dev, B,H/16,W/16,512] the conv5_3 map (NHWC).  Every image is computed independently of the
+ * batch (bitwise); no float atomics; no host synchronisation, graph-capturable. */
+int imcui_hip_netvlad_forward(imcui_hip_t* h, const float* packed, const float* image, int B, int C, int H, int W, int whiten, float* descriptor,
+                              float* dbg_feat, void* ws, size_t ws_bytes, void* stream);
+/* Test entry: one stage alone.  op 0: layer 0 with netvlad.py:126-129 applied as the image is read, in = image [dev, B,3,H,W] -> out
+ * [dev, B,H,W,64]; op 1: nn.MaxPool2d(2, 2), flooring, in [dev, B,H,W,C] -> out [dev, B,H/2,W/2,C]; op 2: netvlad.py:138 + NetVLADLayer
+ * on maps in [dev, B,H,W,512] -> out [dev, B,32768]; op 3: backbone.28 (conv5_3, no ReLU) as the forward launches it -- the 512 input
+ * channels in 8 groups of 64, each a launch of the patch-staging kernels, summed in group order -- in the handle's arithmetic mode, in / out
+ * [dev, B,H,W,512].  Ops 2 and 3 take the workspace of imcui_hip_netvlad_probe_workspace_bytes(B, H * W). */
+size_t imcui_hip_netvlad_probe_workspace_bytes(int B, int N);
+int imcui_hip_netvlad_layer_probe(imcui_hip_t* h, int op, const float* packed, const float* in, int B, int H, int W, int C, float* out, void* ws,
+                                  size_t ws_bytes, void* stream);
+/* Test entry: the whitening's split-K skinny GEMM, its fold and the normalisation at a free shape: out [dev, B,out_dim] =
+ * normalize(weight [dev, out_dim,in_dim] x [dev, B,in_dim] + bias), in_dim a multiple of 4. */
+size_t imcui_hip_netvlad_whiten_workspace_bytes(int B, int in_dim, int out_dim);
+int imcui_hip_netvlad_whiten_probe(imcui_hip_t* h, const float* weight, const float* bias, const float* x, int B, int in_dim, int out_dim, float* out, void* ws,
+                                   size_t ws_bytes, void* stream);
+/* pairs_from_retrieval.py:109 `einsum("id,jd->ij")` and :56-66 `pairs_from_score_matrix` up to the top-k, on the device: query [dev, Q,D],
+ * db [dev, N,D] float32; invalid optional [dev, Q,N] bytes; an entry that is invalid, or below min_score when has_min_score != 0, counts
+ * as -inf.  indices [dev, Q,num_select] int32 / scores [dev, Q,num_select]: the num_select highest of every row in descending score,
+ * equal scores by ascending database index (torch.topk leaves that order open); slots past N hold -1 / -inf.  The score matrix lives in
+ * the workspace only. */
+size_t imcui_hip_retrieval_topk_workspace_bytes(int Q, int N);
+int imcui_hip_retrieval_topk(imcui_hip_t* h, const float* query, const float* db, int Q, int N, int D, const unsigned char* invalid, int has_min_score,
+                             float min_score, int num_select, int* indices, float* scores, void* ws, size_t ws_bytes, void* stream);
+
+/* ---- SIFT(zoo entry sift-lightglue, and `sift` + NN; imcui/hloc/extractors/sift.py, backend "opencv") ------------------- */
 /* OpenCV 4.x SIFT_create(contrastThreshold, nfeatures, edgeThreshold, nOctaveLayers = `layers`; sigma 1.6, first octave -1, float
  * pipeline) -> detectAndCompute (sift.py:61-78), then `filter_dog_point` (:19-52), the score top-k (:188-193) and
  * `sift_to_rootsift` (:55-58).  No weights.  OpenCV's sources are restated from its documentation (tests/sift_reference.py is the
