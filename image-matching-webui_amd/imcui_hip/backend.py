@@ -1274,6 +1274,163 @@ class DeDoDeHIP:
         return {"keypoints": kpts, "scores": scores, "num_keypoints": nk, "score": smap}
 
 
+# ------------------------------------------------------------------ DoG + HardNet / SOSNet patch descriptors
+PATCHDESC_MODELS = {"hardnet": 0, "sosnet": 1}
+# (cin, cout, kernel) of the seven convolutions and their index in kornia's nn.Sequential (the BatchNorm2d(affine=False) follows at + 1):
+# kornia.feature.HardNet.features / kornia.feature.SOSNet.layers (whose entry 0 is the InstanceNorm2d); csrc/dog.hip
+PATCHDESC_LAYERS = ((1, 32, 3), (32, 32, 3), (32, 64, 3), (64, 64, 3), (64, 128, 3), (128, 128, 3), (128, 128, 8))
+PATCHDESC_CONV_OPS = {"hardnet": (0, 3, 6, 9, 12, 15, 19), "sosnet": (1, 4, 7, 10, 13, 16, 20)}
+PATCHDESC_ROOT = {"hardnet": "features", "sosnet": "layers"}
+PATCHDESC_PROBE_OPS = {"pyrdown": 0, "norm": 1, "layer1": 2, "layer2": 3, "layer3": 4, "layer4": 5, "layer5": 6, "layer6": 7, "final": 8, "outnorm": 9}
+PATCHDESC_CHUNK = 1024  # dog.py:35 `max_batch_size`
+PATCHDESC_MAX_CHUNK = 8192
+
+
+def patchdesc_model(name: str) -> int:
+    if name not in PATCHDESC_MODELS:
+        raise ValueError(f"Unknown descriptor: {name}")
+    return PATCHDESC_MODELS[name]
+
+
+def patchdesc_tensor_names(model: str) -> list[str]:
+    lib, m = load_library(), patchdesc_model(model)
+    return [lib.imcui_hip_patchdesc_tensor_name(m, i).decode() for i in range(lib.imcui_hip_patchdesc_num_tensors(m))]
+
+
+def patchdesc_tensor_shapes(model: str) -> dict:
+    root, shapes = PATCHDESC_ROOT[model], {}
+    for (cin, cout, k), op in zip(PATCHDESC_LAYERS, PATCHDESC_CONV_OPS[model]):
+        shapes[f"{root}.{op}.weight"] = (cout, cin, k, k)
+        shapes[f"{root}.{op + 1}.running_mean"] = (cout,)
+        shapes[f"{root}.{op + 1}.running_var"] = (cout,)
+    return shapes
+
+
+def _pack_patchdesc(model: str, state_dict: dict) -> torch.Tensor:
+    lib = load_library()
+    sd = dict(state_dict)
+    if set(sd) >= {"state_dict"} and isinstance(sd["state_dict"], dict):  # HardNet's checkpoint_liberty_with_aug.pth wraps it
+        sd = dict(sd["state_dict"])
+    sd = {k: v for k, v in sd.items() if not k.endswith(".num_batches_tracked")}  # the counters of the affine-free BatchNorms
+    return _pack_named(model, f"kornia's {'HardNet' if model == 'hardnet' else 'SOSNet'}", patchdesc_tensor_names(model), patchdesc_tensor_shapes(model), sd,
+                       lib.imcui_hip_patchdesc_packed_floats(), lib.imcui_hip_patchdesc_pack_weights, patchdesc_model(model))  # fmt: skip
+
+
+def pack_hardnet(state_dict: dict) -> torch.Tensor:
+    """kornia.feature.HardNet's state dict (`features.N.*`, or a checkpoint {"state_dict": ...}) -> packed float32 buffer (host).
+    Strict: every key but the `num_batches_tracked` counters is consumed exactly once, every shape checked."""
+    return _pack_patchdesc("hardnet", state_dict)
+
+
+def pack_sosnet(state_dict: dict) -> torch.Tensor:
+    """kornia.feature.SOSNet's state dict (`layers.N.*`, or wrapped in {"state_dict": ...}) -> packed float32 buffer (host).  Strict."""
+    return _pack_patchdesc("sosnet", state_dict)
+
+
+def patchdesc_check_args(image_shape, kcap: int, chunk: int, mr_size: float) -> None:
+    """Refusals raised before anything is launched (the library refuses the same)."""
+    if len(image_shape) != 4 or image_shape[1] != 1:
+        raise ValueError(f"the patch descriptors expect a gray image [B,1,H,W], got shape {tuple(image_shape)}")
+    if image_shape[2] < 8 or image_shape[3] < 8:
+        raise ValueError(f"the patch descriptors need images of at least 8 x 8, got {tuple(image_shape[2:])}")
+    if kcap < 1 or not 1 <= chunk <= PATCHDESC_MAX_CHUNK:
+        raise ValueError(f"kcap={kcap} must be positive and chunk={chunk} within 1..{PATCHDESC_MAX_CHUNK}")
+    if not (mr_size > 0 and math.isfinite(mr_size)):
+        raise ValueError(f"mr_size={mr_size} must be positive and finite")
+
+
+class PatchDescHIP:
+    """dog.py:87-105 on the device: LAF patches from the image pyramid, HardNet / SOSNet, unit descriptors (imcui_hip_patchdesc_forward)."""
+
+    def __init__(self):
+        self._ws = _Workspace()
+
+    def forward(self, packed: torch.Tensor, image: torch.Tensor, keypoints: torch.Tensor, scales: torch.Tensor, oris_deg: torch.Tensor,
+                num_keypoints: torch.Tensor, model: str, mr_size: float = 12.0, chunk: int = PATCHDESC_CHUNK, want_patches: bool = False,
+                out: torch.Tensor | None = None) -> dict:  # fmt: skip
+        """image [B,1,H,W] in [0,1]; keypoints [B,K,2] (x, y), scales [B,K] (sigma), oris_deg [B,K], num_keypoints [B] int32, all on the
+        GPU -> {"descriptors": [B,K,128] (rows past num_keypoints[b] are not written: zero, or what `out` held), "status": [1] int32
+        (bit 1: a count above K, bit 2: a non-finite key-point, its row is zero)}; want_patches adds "patches" [B,K,32,32].  No host
+        synchronisation, graph-capturable."""
+        m = patchdesc_model(model)
+        B, K = keypoints.shape[:2]
+        patchdesc_check_args(tuple(image.shape), K, chunk, float(mr_size))
+        if image.shape[0] != B or tuple(keypoints.shape) != (B, K, 2) or tuple(scales.shape) != (B, K) or tuple(oris_deg.shape) != (B, K) or tuple(num_keypoints.shape) != (B,):
+            raise ValueError(f"patch descriptors: image {tuple(image.shape)}, keypoints {tuple(keypoints.shape)}, scales {tuple(scales.shape)}, "
+                             f"oris {tuple(oris_deg.shape)}, num_keypoints {tuple(num_keypoints.shape)} do not agree")  # fmt: skip
+        hd = get_handle(image.device)
+        _same_device(packed, image)
+        lib = hd.lib
+        if packed.numel() != lib.imcui_hip_patchdesc_packed_floats():
+            raise ImcuiHipError(f"patch descriptors: the packed buffer holds {packed.numel()} floats, {lib.imcui_hip_patchdesc_packed_floats()} are needed")
+        dev = image.device
+        image, keypoints, scales, oris_deg = (t.contiguous().float() for t in (image, keypoints, scales, oris_deg))
+        num_keypoints = num_keypoints.contiguous().to(torch.int32)
+        _, _, H, W = image.shape
+        desc = torch.zeros((B, K, 128), dtype=torch.float32, device=dev) if out is None else out
+        if tuple(desc.shape) != (B, K, 128) or desc.dtype != torch.float32 or not desc.is_contiguous() or desc.device != dev:
+            raise ValueError("patch descriptors: `out` must be a contiguous float32 [B,K,128] tensor on the image's device")
+        status = torch.empty((1,), dtype=torch.int32, device=dev)
+        patches = torch.zeros((B, K, 32, 32), dtype=torch.float32, device=dev) if want_patches else None
+        nbytes = lib.imcui_hip_patchdesc_workspace_bytes(B, H, W, K, int(chunk))
+        if nbytes == 0:
+            raise ImcuiHipError(f"patch descriptors: unsupported launch (B={B}, {H}x{W}, K={K}, chunk={chunk})")
+        with self._ws.use(nbytes, dev) as ws:
+            hd.launch(lib.imcui_hip_patchdesc_forward, _ptr(packed), _ptr(image), B, H, W, _ptr(keypoints), _ptr(scales), _ptr(oris_deg), _ptr(num_keypoints), K, m,
+                      float(mr_size), int(chunk), _ptr(desc), _ptr(status), _ptr(patches), _ptr(ws), ws.numel())  # fmt: skip
+        res = {"descriptors": desc, "status": status}
+        if want_patches:
+            res["patches"] = patches
+        return res
+
+    def layer_probe(self, op: str, inp: torch.Tensor, model: str = "hardnet", packed: torch.Tensor | None = None) -> torch.Tensor:
+        """Test entry: one launch alone, as the forward makes it.  "pyrdown": [n,H,W] -> [n,H//2,W//2]; "norm": patches [n,32,32] -> the
+        network's input normalisation; "layer1": patches -> NHWC [n,32,32,32]; "layer2" .. "layer6": NHWC in -> NHWC out; "final":
+        [n,8,8,128] -> [n,128] (BatchNorm folded, not normalised); "outnorm": [n,128] -> [n,128].  All but pyrdown / norm / outnorm need `packed`."""
+        code, m = PATCHDESC_PROBE_OPS[op], patchdesc_model(model)
+        hd = get_handle(inp.device)
+        lib = hd.lib
+        inp = inp.contiguous().float()
+        n, H, W = inp.shape[0], 1, 1
+        if code == 0:
+            _, H, W = inp.shape
+            shape = (n, H // 2, W // 2)
+        elif code == 1:
+            shape = tuple(inp.shape)
+        elif code == 2:
+            shape = (n, 32, 32, 32)
+        elif code <= 7:
+            cin, cout, _ = PATCHDESC_LAYERS[code - 2]
+            hin, hout = (32, 32, 16, 16, 8)[code - 3], (32, 16, 16, 8, 8)[code - 3]
+            if tuple(inp.shape) != (n, hin, hin, cin):
+                raise ValueError(f"{op}: expected NHWC [{n},{hin},{hin},{cin}], got {tuple(inp.shape)}")
+            shape = (n, hout, hout, cout)
+        else:
+            shape = (n, 128)
+        if code in (1, 2) and inp[0].numel() != 1024 or code == 8 and inp[0].numel() != 8192 or code == 9 and inp[0].numel() != 128:
+            raise ValueError(f"{op}: input of shape {tuple(inp.shape)}")
+        out = torch.empty(shape, dtype=torch.float32, device=inp.device)
+        with self._ws.use(lib.imcui_hip_patchdesc_probe_workspace_bytes(n, H, W), inp.device) as ws:
+            hd.launch(lib.imcui_hip_patchdesc_layer_probe, code, m, _ptr(packed), _ptr(inp), n, H, W, _ptr(out), _ptr(ws), ws.numel())
+        return out
+
+    def patch_probe(self, image: torch.Tensor, keypoints: torch.Tensor, scales: torch.Tensor, oris_deg: torch.Tensor, mr_size: float = 12.0):
+        """Test entry: pyramid + sampling alone on ONE image [H,W]: keypoints [n,2], scales [n], oris_deg [n] -> (patches [n,32,32], status [1])."""
+        hd = get_handle(image.device)
+        lib = hd.lib
+        image, keypoints, scales, oris_deg = (t.contiguous().float() for t in (image, keypoints, scales, oris_deg))
+        (H, W), n = image.shape, keypoints.shape[0]
+        patches = torch.empty((n, 32, 32), dtype=torch.float32, device=image.device)
+        status = torch.empty((1,), dtype=torch.int32, device=image.device)
+        nbytes = lib.imcui_hip_patchdesc_patch_probe_workspace_bytes(H, W)
+        if nbytes == 0:
+            raise ImcuiHipError(f"patch probe: unsupported image {H}x{W}")
+        with self._ws.use(nbytes, image.device) as ws:
+            hd.launch(lib.imcui_hip_patchdesc_patch_probe, _ptr(image), H, W, _ptr(keypoints), _ptr(scales), _ptr(oris_deg), n, float(mr_size), _ptr(patches),
+                      _ptr(status), _ptr(ws), ws.numel())  # fmt: skip
+        return patches, status
+
+
 # ------------------------------------------------------------------ SIFT
 SIFT_LAYERS =(3, 4, 5)  # nOctaveLayers (the wrapper's `num_octaves`) csrc/sift.hip is written for: blur radius at most 13
 

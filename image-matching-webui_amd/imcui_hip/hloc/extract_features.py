@@ -44,6 +44,17 @@ confs = {
         "model": {"name": "netvlad"},
         "preprocessing": {"resize_max": 1024},
     },
+    # imcui/hloc/configs/extractors.py:144-175: DoG key-points + SOSNet / HardNet patch descriptors (the `dog` plugin)
+    "sosnet": {
+        "output": "feats-sosnet-n5000-r1600",
+        "model": {"name": "dog", "descriptor": "sosnet", "max_keypoints": 5000},
+        "preprocessing": {"grayscale": True, "resize_max": 1600, "force_resize": True, "width": 640, "height": 480, "dfactor": 8},
+    },
+    "hardnet": {
+        "output": "feats-hardnet-n5000-r1600",
+        "model": {"name": "dog", "descriptor": "hardnet", "max_keypoints": 5000},
+        "preprocessing": {"grayscale": True, "resize_max": 1600, "force_resize": True, "width": 640, "height": 480, "dfactor": 8},
+    },
 }
 
 

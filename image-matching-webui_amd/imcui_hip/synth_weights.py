@@ -901,3 +901,32 @@ def netvlad_write_mat(path, state: dict) -> None:
         layers[33] = {"weights": cell(state["whiten.weight"].numpy().T[None, None], state["whiten.bias"].numpy())}
     mean = np.ascontiguousarray(np.broadcast_to(state["preprocess.mean"].numpy().reshape(1, 1, 3), (2, 2, 3)))  # (loadmat squeezes a [1,1,3] to [3])
     savemat(str(path), {"net": {"layers": layers, "meta": {"normalization": {"averageImage": mean}}}})
+
+
+# (cin, cout, kernel) of kornia.feature.HardNet / SOSNet and the index of each convolution in their nn.Sequential (BatchNorm at + 1)
+PATCHDESC_LAYERS = ((1, 32, 3), (32, 32, 3), (32, 64, 3), (64, 64, 3), (64, 128, 3), (128, 128, 3), (128, 128, 8))
+HARDNET_CONV_OPS = (0, 3, 6, 9, 12, 15, 19)
+SOSNET_CONV_OPS = (1, 4, 7, 10, 13, 16, 20)
+
+
+def _patchdesc_synth_state(seed: int, root: str, ops) -> dict:
+    g = torch.Generator().manual_seed(seed)
+    sd = {}
+    for (cin, cout, k), op in zip(PATCHDESC_LAYERS, ops):
+        sd[f"{root}.{op}.weight"] = torch.randn(cout, cin, k, k, generator=g) * math.sqrt(2.0 / (cin * k * k))
+        sd[f"{root}.{op + 1}.running_mean"] = torch.randn(cout, generator=g) * 0.2
+        sd[f"{root}.{op + 1}.running_var"] = 0.5 + torch.rand(cout, generator=g)
+        sd[f"{root}.{op + 1}.num_batches_tracked"] = torch.tensor(1000, dtype=torch.long)
+    return sd
+
+
+def hardnet_synth_state(seed: int = 0) -> dict:
+    """Seeded HardNet weights under kornia.feature.HardNet's key names (`features.N.weight`, bias-free convolutions; `features.N+1.
+    running_mean / running_var / num_batches_tracked` of the BatchNorm2d(affine=False) behind each).  Kaiming-scaled convolutions; the
+    running variances lie in [0.5, 1.5) and the running means are not zero, so a BatchNorm fold that is skipped or mis-ordered shows."""
+    return _patchdesc_synth_state(seed, "features", HARDNET_CONV_OPS)
+
+
+def sosnet_synth_state(seed: int = 0) -> dict:
+    """The same for kornia.feature.SOSNet (`layers.N.*`; `layers.0` is the parameter-free InstanceNorm2d)."""
+    return _patchdesc_synth_state(seed, "layers", SOSNET_CONV_OPS)

@@ -393,6 +393,43 @@ size_t imcui_hip_retrieval_topk_workspace_bytes(int Q, int N);
 int imcui_hip_retrieval_topk(imcui_hip_t* h, const float* query, const float* db, int Q, int N, int D, const unsigned char* invalid, int has_min_score,
                              float min_score, int num_select, int* indices, float* scores, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- DoG + HardNet / SOSNet patch descriptors (extractor confs `hardnet` / `sosnet`; imcui/hloc/extractors/dog.py:87-105) ------------ */
+/* model 0 = kornia.feature.HardNet (state dict `features.N.*`), 1 = kornia.feature.SOSNet (`layers.N.*`): seven bias-free convolutions,
+ * each with the running_mean / running_var of its BatchNorm2d(affine=False); tensors in imcui_hip_patchdesc_tensor_name order.  The
+ * BatchNorms are folded in float32 at pack time; both networks share one packed layout. */
+size_t imcui_hip_patchdesc_packed_floats(void);
+int imcui_hip_patchdesc_num_tensors(int model);
+const char* imcui_hip_patchdesc_tensor_name(int model, int i);
+int imcui_hip_patchdesc_pack_weights(int model, const float* const* tensors, float* packed);
+/* levels of the pyramid the call builds for an H x W image (level 0 = the image) */
+int imcui_hip_patchdesc_num_levels(int H, int W);
+/* the activations are sized by `chunk`; kcap only sizes the table of per-chunk row counts */
+size_t imcui_hip_patchdesc_workspace_bytes(int B, int H, int W, int kcap, int chunk);
+/* dog.py:87-105 on key-points given by the caller: image [dev, B,1,H,W] in [0,1]; keypoints [dev, B,kcap,2] (x, y as the detector returns
+ * them: the call adds 0.5), scales [dev, B,kcap] (sigma), oris_deg [dev, B,kcap] (degrees; the LAF angle is -ori), num_keypoints [dev, B]
+ * -> descriptors [dev, B,kcap,128], unit rows; rows past num_keypoints[b] are not written.  LAF scale = sigma mr_size / 2; pyramid =
+ * kornia pyrdown (5x5 binomial blur, reflect; bilinear halving) while min(h, w) >= 32; level floor(log2(2 laf_scale / 32)) clamped to
+ * [0, max(0, min(H, W) / 32 - 1)]; 32x32 affine grid, bilinear, border padding, align_corners=False.  Patches are processed per image in
+ * chunks of `chunk` rows (the reference's max_batch_size is 1024); the launches are fixed by (B, kcap, chunk) and a chunk past an image's
+ * count exits on the device.  A descriptor does not depend (bitwise) on B, on the other counts or on `chunk`.  status optional [dev, 1]:
+ * bit 1 = a count above kcap (clipped), bit 2 = a non-finite key-point, scale or orientation (its row is zero).  dbg_patches optional
+ * [dev, B,kcap,1024].  No float atomics, no host synchronisation, graph-capturable. */
+int imcui_hip_patchdesc_forward(imcui_hip_t* h, const float* packed, const float* image, int B, int H, int W, const float* keypoints, const float* scales,
+                                const float* oris_deg, const int* num_keypoints, int kcap, int model, float mr_size, int chunk, float* descriptors, int* status,
+                                float* dbg_patches, void* ws, size_t ws_bytes, void* stream);
+/* Test entry: pyramid + sampling alone on ONE image [dev, H,W]: n key-points -> patches [dev, n,1024]; status [dev, 1] as above. */
+size_t imcui_hip_patchdesc_patch_probe_workspace_bytes(int H, int W);
+int imcui_hip_patchdesc_patch_probe(imcui_hip_t* h, const float* image, int H, int W, const float* keypoints, const float* scales, const float* oris_deg, int n,
+                                    float mr_size, float* patches, int* status, void* ws, size_t ws_bytes, void* stream);
+/* Test entry: one launch alone on n rows, as the forward launches it (row counts read on the device).  op 0: pyrdown, in [dev, n,H,W] ->
+ * out [dev, n,H/2,W/2]; op 1: the input normalisation [n,1024] -> [n,1024]; op 2: normalisation + layer 1 -> NHWC [n,32,32,32]; ops 3..7:
+ * layers 2..6, NHWC in -> NHWC out; op 8: layer 7 (8 partial products over 1024 of K each, folded in group order, then the BatchNorm
+ * shift) [n,8192] -> [n,128]; op 9: the output
+ * normalisation [n,128] -> [n,128].  H, W are read by op 0 only. */
+size_t imcui_hip_patchdesc_probe_workspace_bytes(int n, int H, int W);
+int imcui_hip_patchdesc_layer_probe(imcui_hip_t* h, int op, int model, const float* packed, const float* in, int n, int H, int W, float* out, void* ws,
+                                    size_t ws_bytes, void* stream);
+
 /* ---- SIFT(zoo entry sift-lightglue, and `sift` + NN; imcui/hloc/extractors/sift.py, backend "opencv") ------------------- */
 /* OpenCV 4.x SIFT_create(contrastThreshold, nfeatures, edgeThreshold, nOctaveLayers = `layers`; sigma 1.6, first octave -1, float
  * pipeline) -> detectAndCompute (sift.py:61-78), then `filter_dog_point` (:19-52), the score top-k (:188-193) and
