@@ -1034,6 +1034,154 @@ class NetVLADHIP:
         return out
 
 
+# ------------------------------------------------------------------ CosPlace / EigenPlaces
+PLACES_BACKBONES = {"ResNet18": 18, "ResNet50": 50, "ResNet101": 101, "ResNet152": 152}  # conf["backbone"] -> the library's code
+PLACES_DEPTHS = {18: (2, 2, 2, 2), 50: (3, 4, 6, 3), 101: (3, 4, 23, 3), 152: (3, 8, 36, 3)}  # torchvision's resnetNN `layers`
+
+
+def places_backbone_code(backbone) -> int:
+    """"ResNet50" (or 50) -> 50.  The VGG16 checkpoints of upstream are refused by name: that trunk is not built."""
+    if isinstance(backbone, str) and backbone.lower() == "vgg16":
+        raise ValueError("CosPlace / EigenPlaces: the VGG16 backbone is not built; use ResNet18, ResNet50, ResNet101 or ResNet152")
+    code = PLACES_BACKBONES.get(backbone, backbone)
+    if code not in PLACES_DEPTHS:
+        raise ValueError(f"CosPlace / EigenPlaces: unknown backbone {backbone!r}; use ResNet18, ResNet50, ResNet101 or ResNet152")
+    return code
+
+
+def places_feature_dim(backbone) -> int:
+    return 512 if places_backbone_code(backbone) == 18 else 2048
+
+
+def places_map_size(h: int, w: int) -> tuple:
+    """Sizes after conv1, the max-pool, layer2, layer3 and layer4: each (n - 1) // 2 + 1 of the one before."""
+    out = []
+    for _ in range(5):
+        h, w = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+        out.append((h, w))
+    return tuple(out)
+
+
+def places_tensor_names(backbone, fc_output_dim: int) -> list[str]:
+    lib, code = load_library(), places_backbone_code(backbone)
+    return [lib.imcui_hip_places_tensor_name(code, fc_output_dim, i).decode() for i in range(lib.imcui_hip_places_num_tensors(code, fc_output_dim))]
+
+
+def places_tensor_shapes(backbone, fc_output_dim: int) -> dict:
+    """The state-dict shapes of upstream's GeoLocalizationNet on a torchvision ResNet (cosplace_model/network.py), restated."""
+    code = places_backbone_code(backbone)
+    bott = code != 18
+    shapes = {"backbone.0.weight": (64, 3, 7, 7)}
+
+    def bn(prefix, c):
+        for k in ("weight", "bias", "running_mean", "running_var"):
+            shapes[f"{prefix}.{k}"] = (c,)
+
+    bn("backbone.1", 64)
+    cin = 64
+    for L, depth in enumerate(PLACES_DEPTHS[code]):
+        width = 64 << L
+        cout = 4 * width if bott else width
+        for i in range(depth):
+            p, stride = f"backbone.{4 + L}.{i}", 2 if (i == 0 and L > 0) else 1
+            convs = ((cin, width, 1), (width, width, 3), (width, cout, 1)) if bott else ((cin, width, 3), (width, width, 3))
+            for j, (ci, co, k) in enumerate(convs, 1):
+                shapes[f"{p}.conv{j}.weight"] = (co, ci, k, k)
+                bn(f"{p}.bn{j}", co)
+            if stride != 1 or cin != cout:
+                shapes[f"{p}.downsample.0.weight"] = (cout, cin, 1, 1)
+                bn(f"{p}.downsample.1", cout)
+            cin = cout
+    shapes["aggregation.1.p"] = (1,)
+    shapes["aggregation.3.weight"] = (fc_output_dim, cin)
+    shapes["aggregation.3.bias"] = (fc_output_dim,)
+    return shapes
+
+
+def pack_places(state_dict: dict, backbone, fc_output_dim: int) -> torch.Tensor:
+    """Upstream's state dict (or a `{"state_dict": ...}` / `{"model_state_dict": ...}` wrapper of it) -> packed float32 buffer (host).
+    `num_batches_tracked` entries are ignored.  Strict: every other key is consumed exactly once, every shape checked."""
+    lib, code = load_library(), places_backbone_code(backbone)
+    sd = state_dict
+    for wrapper in ("state_dict", "model_state_dict"):
+        if wrapper in sd and isinstance(sd[wrapper], dict):
+            sd = sd[wrapper]
+    sd = {k: v for k, v in sd.items() if not k.endswith("num_batches_tracked")}
+    return _pack_named("CosPlace / EigenPlaces", f"the ResNet-{code} / {fc_output_dim}", places_tensor_names(code, fc_output_dim),
+                       places_tensor_shapes(code, fc_output_dim), sd, lib.imcui_hip_places_packed_floats(code, fc_output_dim),
+                       lib.imcui_hip_places_pack_weights, code, fc_output_dim)
+
+
+def places_check_args(image_shape) -> None:
+    """The refusal raised before anything is launched (the library refuses the same)."""
+    if len(image_shape) != 4 or image_shape[1] != 3 or min(image_shape[2], image_shape[3]) < 1:
+        raise ValueError(f"CosPlace / EigenPlaces expect an RGB image [B,3,H,W], got shape {tuple(image_shape)}")
+
+
+class PlacesHIP:
+    def __init__(self, backbone, fc_output_dim: int):
+        self.code, self.dim = places_backbone_code(backbone), int(fc_output_dim)
+        self.feat = places_feature_dim(self.code)
+        self._ws = _Workspace()
+
+    def _check_packed(self, lib, packed):
+        need = lib.imcui_hip_places_packed_floats(self.code, self.dim)
+        if packed.numel() != need:
+            raise ImcuiHipError(f"CosPlace / EigenPlaces: the packed buffer holds {packed.numel()} floats, ResNet-{self.code} / {self.dim} needs {need}")
+
+    def forward_batched(self, packed: torch.Tensor, image: torch.Tensor, want_map: bool = False) -> dict:
+        """image [B,3,H,W] float32 RGB in [0,1] on the GPU -> {"global_descriptor": [B,fc_output_dim]}, unit norm; no host synchronisation,
+        graph-capturable.  want_map adds `backbone` [B,h4,w4,F], the layer4 map (NHWC)."""
+        places_check_args(tuple(image.shape))
+        hd = get_handle(image.device)
+        _same_device(packed, image)
+        lib = hd.lib
+        self._check_packed(lib, packed)
+        image = image.contiguous().float()
+        B, Cc, H, W = image.shape
+        dev = image.device
+        desc = torch.empty((B, self.dim), dtype=torch.float32, device=dev)
+        fmap = torch.empty((B, *places_map_size(H, W)[-1], self.feat), dtype=torch.float32, device=dev) if want_map else None
+        with self._ws.use(lib.imcui_hip_places_workspace_bytes(self.code, self.dim, B, H, W), dev) as ws:
+            hd.launch(lib.imcui_hip_places_forward, _ptr(packed), _ptr(image), B, Cc, H, W, self.code, self.dim, _ptr(desc), _ptr(fmap), _ptr(ws), ws.numel())
+        out = {"global_descriptor": desc}
+        if want_map:
+            out["backbone"] = fmap
+        return out
+
+    def layer_probe(self, op: str, inp: torch.Tensor, packed: torch.Tensor, layer: int = 0, block: int = 0) -> torch.Tensor:
+        """Test entry: one stage alone.  "stem": image [B,3,H,W] -> [B,Hp,Wp,64]; "block": NHWC [B,H,W,cin] -> [B,Ho,Wo,cout], block `block`
+        of layer 1 .. 4 in the handle's arithmetic mode; "gem": [B,H,W,F] -> [B,F]; "head": [B,F] -> [B,fc_output_dim]."""
+        code = {"stem": 0, "block": 1, "gem": 2, "head": 3}[op]
+        hd = get_handle(inp.device)
+        lib = hd.lib
+        self._check_packed(lib, packed)
+        inp = inp.contiguous().float()
+        key = f"backbone.{3 + layer}.{block}.conv1.weight"
+        shapes = places_tensor_shapes(self.code, self.dim) if code == 1 else {}
+        want_c = 3 if code == 0 else shapes.get(key, (0, -1))[1] if code == 1 else self.feat
+        if inp.dim() != (2 if code == 3 else 4) or inp.shape[1 if code in (0, 3) else 3] != want_c:
+            raise ValueError(f"places layer probe '{op}' (layer {layer}, block {block}): input {tuple(inp.shape)}, {want_c} channels expected")
+        if code == 0:
+            B, _, H, W = inp.shape
+            shape = (B, *places_map_size(H, W)[1], 64)
+        elif code == 1:
+            B, H, W, _ = inp.shape
+            bott, width = self.code != 18, 64 << (layer - 1)
+            stride = 2 if (block == 0 and layer > 1) else 1
+            shape = (B, (H - 1) // stride + 1, (W - 1) // stride + 1, 4 * width if bott else width)
+        elif code == 2:
+            B, H, W, _ = inp.shape
+            shape = (B, self.feat)
+        else:
+            (B, _), H, W = inp.shape, 1, 1
+            shape = (B, self.dim)
+        out = torch.empty(shape, dtype=torch.float32, device=inp.device)
+        with self._ws.use(max(256, lib.imcui_hip_places_probe_workspace_bytes(self.code, self.dim, code, B, H, W, layer, block)), inp.device) as ws:
+            hd.launch(lib.imcui_hip_places_layer_probe, code, self.code, self.dim, _ptr(packed), _ptr(inp), B, H, W, layer, block, _ptr(out), _ptr(ws), ws.numel())
+        return out
+
+
 _retrieval_ws = _Workspace()
 
 

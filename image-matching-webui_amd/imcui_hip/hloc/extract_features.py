@@ -44,6 +44,17 @@ confs = {
         "model": {"name": "netvlad"},
         "preprocessing": {"resize_max": 1024},
     },
+    # imcui/hloc/configs/extractors.py:382-391: the two other ResNet retrieval models (the `cosplace` / `eigenplaces` plugins), RGB
+    "cosplace": {
+        "output": "global-feats-cosplace",
+        "model": {"name": "cosplace"},
+        "preprocessing": {"resize_max": 1024},
+    },
+    "eigenplaces": {
+        "output": "global-feats-eigenplaces",
+        "model": {"name": "eigenplaces"},
+        "preprocessing": {"resize_max": 1024},
+    },
     # imcui/hloc/configs/extractors.py:144-175: DoG key-points + SOSNet / HardNet patch descriptors (the `dog` plugin)
     "sosnet": {
         "output": "feats-sosnet-n5000-r1600",

@@ -123,6 +123,14 @@ SIGNATURES = {
     "imcui_hip_netvlad_whiten_probe": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_void_p] + [C.c_void_p, C.c_size_t, C.c_void_p]),
     "imcui_hip_retrieval_topk_workspace_bytes": (C.c_size_t, [C.c_int] * 2),
     "imcui_hip_retrieval_topk": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_void_p, C.c_int, C.c_float, C.c_int] + [C.c_void_p] * 2 + [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "imcui_hip_places_packed_floats": (C.c_size_t, [C.c_int] * 2),
+    "imcui_hip_places_num_tensors": (C.c_int, [C.c_int] * 2),
+    "imcui_hip_places_tensor_name": (C.c_char_p, [C.c_int] * 3),
+    "imcui_hip_places_pack_weights": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_void_p]),
+    "imcui_hip_places_workspace_bytes": (C.c_size_t, [C.c_int] * 5),
+    "imcui_hip_places_forward": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 6 + [C.c_void_p] * 2 + [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "imcui_hip_places_probe_workspace_bytes": (C.c_size_t, [C.c_int] * 8),
+    "imcui_hip_places_layer_probe": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] + [C.c_void_p, C.c_size_t, C.c_void_p]),
     "imcui_hip_patchdesc_packed_floats": (C.c_size_t, []),
     "imcui_hip_patchdesc_num_tensors": (C.c_int, [C.c_int]),
     "imcui_hip_patchdesc_tensor_name": (C.c_char_p, [C.c_int] * 2),

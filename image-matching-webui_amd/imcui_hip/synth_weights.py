@@ -903,6 +903,54 @@ def netvlad_write_mat(path, state: dict) -> None:
     savemat(str(path), {"net": {"layers": layers, "meta": {"normalization": {"averageImage": mean}}}})
 
 
+PLACES_DEPTHS = {18: (2, 2, 2, 2), 50: (3, 4, 6, 3), 101: (3, 4, 23, 3), 152: (3, 8, 36, 3)}  # torchvision's resnetNN `layers`
+
+
+def places_synth_state(backbone: int = 50, fc_output_dim: int = 2048, seed: int = 0) -> dict:
+    """Seeded CosPlace / EigenPlaces weights under the state-dict names of upstream's GeoLocalizationNet on a torchvision ResNet
+    (`backbone.0.weight`, `backbone.1.*`, `backbone.{4..7}.<block>.conv{1,2,3}.weight` / `.bn{1,2,3}.*` / `.downsample.{0,1}.*`,
+    `aggregation.1.p`, `aggregation.3.{weight,bias}`), in the module's own order, `num_batches_tracked` included.  backbone 18 / 50 / 101 /
+    152.  numpy's default_rng, one stream in that order.  He-initialised convolutions; BatchNorm weights in [0.8, 1.2), biases and running
+    means of spread 0.1 and running variances in [0.5, 1.5), so a fold that is skipped or mis-ordered shows; the last BatchNorm of every
+    block has a tenth of that weight, so the residual sum stays O(1) through 50 blocks; p = 2.7, a non-integer exponent."""
+    import numpy as np
+
+    rng = np.random.default_rng(seed)
+    sd = {}
+
+    def conv(name, cout, cin, k):
+        sd[name + ".weight"] = rng.standard_normal((cout, cin, k, k), dtype=np.float32) * np.float32(math.sqrt(2.0 / (cin * k * k)))
+
+    def bn(name, c, gain=1.0):
+        sd[name + ".weight"] = (np.float32(0.8) + np.float32(0.4) * rng.random(c, dtype=np.float32)) * np.float32(gain)
+        sd[name + ".bias"] = rng.standard_normal(c, dtype=np.float32) * np.float32(0.1)
+        sd[name + ".running_mean"] = rng.standard_normal(c, dtype=np.float32) * np.float32(0.1)
+        sd[name + ".running_var"] = np.float32(0.5) + rng.random(c, dtype=np.float32)
+        sd[name + ".num_batches_tracked"] = np.array(1000, dtype=np.int64)
+
+    bott = backbone != 18
+    conv("backbone.0", 64, 3, 7)
+    bn("backbone.1", 64)
+    cin = 64
+    for L, depth in enumerate(PLACES_DEPTHS[backbone]):
+        width = 64 << L
+        cout = 4 * width if bott else width
+        for i in range(depth):
+            p, stride = f"backbone.{4 + L}.{i}", 2 if (i == 0 and L > 0) else 1
+            convs = ((cin, width, 1), (width, width, 3), (width, cout, 1)) if bott else ((cin, width, 3), (width, width, 3))
+            for j, (ci, co, k) in enumerate(convs, 1):
+                conv(f"{p}.conv{j}", co, ci, k)
+                bn(f"{p}.bn{j}", co, 0.1 if j == len(convs) else 1.0)
+            if stride != 1 or cin != cout:
+                conv(f"{p}.downsample.0", cout, cin, 1)
+                bn(f"{p}.downsample.1", cout)
+            cin = cout
+    sd["aggregation.1.p"] = np.array([2.7], dtype=np.float32)
+    sd["aggregation.3.weight"] = rng.standard_normal((fc_output_dim, cin), dtype=np.float32) * np.float32(1.0 / math.sqrt(cin))
+    sd["aggregation.3.bias"] = rng.standard_normal(fc_output_dim, dtype=np.float32) * np.float32(0.01)
+    return {k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()}
+
+
 # (cin, cout, kernel) of kornia.feature.HardNet / SOSNet and the index of each convolution in their nn.Sequential (BatchNorm at + 1)
 PATCHDESC_LAYERS = ((1, 32, 3), (32, 32, 3), (32, 64, 3), (64, 64, 3), (64, 128, 3), (128, 128, 3), (128, 128, 8))
 HARDNET_CONV_OPS = (0, 3, 6, 9, 12, 15, 19)

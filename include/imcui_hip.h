@@ -393,6 +393,33 @@ size_t imcui_hip_retrieval_topk_workspace_bytes(int Q, int N);
 int imcui_hip_retrieval_topk(imcui_hip_t* h, const float* query, const float* db, int Q, int N, int D, const unsigned char* invalid, int has_min_score,
                              float min_score, int num_select, int* indices, float* scores, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- CosPlace / EigenPlaces (retrieval_zoo entry cosplace; imcui/hloc/extractors/cosplace.py, eigenplaces.py) ------------------------- */
+/* Packed weights of the model that cosplace.py:28-34 / eigenplaces.py:41-47 fetch with torch.hub.load("gmberton/...", "get_trained_model",
+ * backbone=, fc_output_dim=): backbone = 18 / 50 / 101 / 152 (torchvision ResNet without avgpool and fc), tensors in
+ * imcui_hip_places_tensor_name order -- `backbone.0.weight`, `backbone.1.{weight,bias,running_mean,running_var}`,
+ * `backbone.{4..7}.<block>.conv{1,2,3}.weight` / `.bn{1,2,3}.*` / `.downsample.0.weight` / `.downsample.1.*`, `aggregation.1.p` [1],
+ * `aggregation.3.weight` [fc_output_dim, F] / `.bias` (F = 512 for ResNet-18, else 2048).  Every BatchNorm (eps 1e-5) is folded into its
+ * convolution in float32.  The network is restated, not in the reference checkout: the names are as recalled from upstream, unverified. */
+size_t imcui_hip_places_packed_floats(int backbone, int fc_output_dim);
+int imcui_hip_places_num_tensors(int backbone, int fc_output_dim);
+const char* imcui_hip_places_tensor_name(int backbone, int fc_output_dim, int i);
+int imcui_hip_places_pack_weights(int backbone, int fc_output_dim, const float* const* tensors, float* packed);
+size_t imcui_hip_places_workspace_bytes(int backbone, int fc_output_dim, int B, int H, int W);
+/* cosplace.py:40-45 / eigenplaces.py:53-58 `_forward`: image [dev, B,C,H,W] RGB in [0,1] -> descriptor [dev, B,fc_output_dim], unit norm.
+ * tvf.Normalize (:36-38, :41) as the image is read, conv1 + bn1 + ReLU + max-pool in one kernel, layer1 .. layer4 on the shared GEMM,
+ * L2Norm, GeM (p from the packed buffer), Linear, L2Norm.  Any H, W >= 1.  Refused with a message: C != 3, an unknown backbone.  map
+ * optional: [dev, B,h4,w4,F] the layer4 map (NHWC), every stage's size (n - 1) / 2 + 1 of the one before, five times from H, W.  Every
+ * image is computed independently of the batch (bitwise); no float atomics; no host synchronisation, graph-capturable. */
+int imcui_hip_places_forward(imcui_hip_t* h, const float* packed, const float* image, int B, int C, int H, int W, int backbone, int fc_output_dim,
+                             float* descriptor, float* map, void* ws, size_t ws_bytes, void* stream);
+/* Test entry: one stage alone, through the forward's own launch code.  op 0: tvf.Normalize + conv1 + bn1 + ReLU + max-pool, in = image
+ * [dev, B,3,H,W] -> out [dev, B,Hp,Wp,64]; op 1: block `block` of layer 1 .. 4 in the handle's arithmetic mode, in [dev, B,H,W,cin] -> out
+ * [dev, B,Ho,Wo,cout]; op 2: L2Norm + GeM, in [dev, B,H,W,F] -> out [dev, B,F]; op 3: Linear + L2Norm, in [dev, B,F] (H = W = 1) -> out
+ * [dev, B,fc_output_dim].  Ops 1 and 2 take the workspace of imcui_hip_places_probe_workspace_bytes. */
+size_t imcui_hip_places_probe_workspace_bytes(int backbone, int fc_output_dim, int op, int B, int H, int W, int layer, int block);
+int imcui_hip_places_layer_probe(imcui_hip_t* h, int op, int backbone, int fc_output_dim, const float* packed, const float* in, int B, int H, int W, int layer,
+                                 int block, float* out, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- DoG + HardNet / SOSNet patch descriptors (extractor confs `hardnet` / `sosnet`; imcui/hloc/extractors/dog.py:87-105) ------------ */
 /* model 0 = kornia.feature.HardNet (state dict `features.N.*`), 1 = kornia.feature.SOSNet (`layers.N.*`): seven bias-free convolutions,
  * each with the running_mean / running_var of its BatchNorm2d(affine=False); tensors in imcui_hip_patchdesc_tensor_name order.  The
