@@ -195,7 +195,6 @@ struct AkIsCand {
 };
 
 static int ak_pad32(int v) { return (v + 31) / 32 * 32; }
-static unsigned ak_grid(long n) { return (unsigned)min((n + 255) / 256, (long)65536); }
 
 template <int COUT, int CC, int ACT>
 static void ak_conv3(const AkConvP& p, int B, hipStream_t stream) {

@@ -655,19 +655,19 @@ static int al_dense(imcui_hip_t* h, const AlDims& d, const AlLayout& l, const fl
     };
     auto pool = [&](const float* src, int lds, int C, float* dst, int ldd, int k, int sh_out) {
         const long n4 = (long)B * px(sh_out) * ldd / 4;
-        hipLaunchKernelGGL(ak_pool_kernel<true>, dim3(ak_grid(n4)), dim3(256), 0, stream, src, lds, C, dst, ldd, k, Hp >> sh_out, Wp >> sh_out, n4);
+        hipLaunchKernelGGL(ak_pool_kernel<true>, dim3(grid_stride_blocks(n4)), dim3(256), 0, stream, src, lds, C, dst, ldd, k, Hp >> sh_out, Wp >> sh_out, n4);
     };
     // a ResBlock at 1 / 2^sh: t = ReLU(bn1(conv1 x)); out = downsample(x) + bias; out = ReLU(bn2(conv2 t) + out)
     auto resblock = [&](int blk, const float* x, int sh, float* t, float* out) -> int {
         const int L = 2 * (blk - 2), cin = d.P[blk - 1], cout = d.P[blk];
         IMCUI_RUN(conv_gemm(L, x, sh, t, nullptr));
         const long n = B * px(sh) * cout;
-        hipLaunchKernelGGL(al_pw_kernel, dim3(ak_grid(n)), dim3(256), 0, stream, x, cin, cin, P + l.dw[blk - 2], P + l.db[blk - 2], out, cout, n);
+        hipLaunchKernelGGL(al_pw_kernel, dim3(grid_stride_blocks(n)), dim3(256), 0, stream, x, cin, cin, P + l.dw[blk - 2], P + l.db[blk - 2], out, cout, n);
         return conv_gemm(L + 1, t, sh, out, out);
     };
     auto head = [&](int i, const float* x, int sh, float* f, float* g) {
         const long np = B * px(sh);
-        const dim3 grid((unsigned)((np + 255) / 256));
+        const dim3 grid(blocks_256(np));
         const float *wt = P + l.cw[i], *ws = P + l.sw + (size_t)i * d.dq;
         if (d.dq == 16)
             hipLaunchKernelGGL(al_head_kernel<16>, grid, dim3(256), 0, stream, x, d.P[i + 1], d.P[i + 1], wt, ws, f, g, np);
@@ -703,7 +703,7 @@ static int al_dense(imcui_hip_t* h, const AlDims& d, const AlLayout& l, const fl
     // ---- the score map, cropped to H x W
     {
         const long np = (long)B * H * W;
-        const dim3 grid((unsigned)((np + 255) / 256));
+        const dim3 grid(blocks_256(np));
         const float *c1t = P + l.cw[0], *ws1 = P + l.sw;
         if (d.c1 == 8 && d.dq == 16)
             hipLaunchKernelGGL((al_score_kernel<8, 16>), grid, dim3(256), 0, stream, s.x1, c1t, ws1, s.g2, s.g3, s.g4, smap, H, W, Hp, Wp, np);

@@ -698,15 +698,15 @@ extern "C" int imcui_hip_aliked_forward(imcui_hip_t* h, const float* packed, con
         g.ldc = AK_GN[L];
         return gemm_launch(h, g, stream);
     };
-    auto selu = [&](float* x, long n) { hipLaunchKernelGGL(ak_selu_kernel, dim3(ak_grid(n / 4)), dim3(256), 0, stream, x, n / 4); };
+    auto selu = [&](float* x, long n) { hipLaunchKernelGGL(ak_selu_kernel, dim3(grid_stride_blocks(n / 4)), dim3(256), 0, stream, x, n / 4); };
     auto pw = [&](int L, const float* in, int ldi, const float* add, float* out, long npix, int act) {
         const long n = npix * AK_PCOUT[L];
-        hipLaunchKernelGGL(ak_pw_kernel, dim3(ak_grid(n)), dim3(256), 0, stream, in, ldi, AK_PCIN[L], P + l.pw[L], add, AK_PCOUT[L], out, AK_PCOUT[L],
+        hipLaunchKernelGGL(ak_pw_kernel, dim3(grid_stride_blocks(n)), dim3(256), 0, stream, in, ldi, AK_PCIN[L], P + l.pw[L], add, AK_PCOUT[L], out, AK_PCOUT[L],
                            AK_PCOUT[L], act, n);
     };
     auto pool = [&](const float* src, int C, float* dst, int ldd, int k, int sh_out) {
         const long n4 = (long)B * px(sh_out) * ldd / 4;
-        hipLaunchKernelGGL(ak_pool_kernel<false>, dim3(ak_grid(n4)), dim3(256), 0, stream, src, C, C, dst, ldd, k, Hp >> sh_out, Wp >> sh_out, n4);
+        hipLaunchKernelGGL(ak_pool_kernel<false>, dim3(grid_stride_blocks(n4)), dim3(256), 0, stream, src, C, C, dst, ldd, k, Hp >> sh_out, Wp >> sh_out, n4);
     };
     // deformable 3x3 (+ folded BatchNorm bias) of x [B, hl, wl, cin]: offsets (VALU layer V), gather, GEMM layer L -> out [.., N]
     auto deform = [&](int V, int L, const float* x, int cin, int sh, float* offb, float* A, float* out) -> int {
@@ -714,7 +714,7 @@ extern "C" int imcui_hip_aliked_forward(imcui_hip_t* h, const float* packed, con
         AkConvP c{x, 0, 0, 0, 0, 0, cin, cin, P + l.vw[V], P + l.vb[V], offb, 18, hl, wl, hl, wl, 0, 0};
         ak_conv3<18, 16, 0>(c, B, stream);
         const long n4 = (long)B * px(sh) * 9 * cin / 4;
-        hipLaunchKernelGGL(ak_deform_kernel, dim3(ak_grid(n4)), dim3(256), 0, stream, x, offb, A, hl, wl, cin, (float)max(hl, wl) / 4.0f, n4);
+        hipLaunchKernelGGL(ak_deform_kernel, dim3(grid_stride_blocks(n4)), dim3(256), 0, stream, x, offb, A, hl, wl, cin, (float)max(hl, wl) / 4.0f, n4);
         IMCUI_CHECK_LAUNCH(h);
         return gemm(L, A, sh, 0, out);
     };
@@ -761,7 +761,7 @@ extern "C" int imcui_hip_aliked_forward(imcui_hip_t* h, const float* packed, con
     float* smap = score_map ? score_map : s.score;
     {
         const long np = B * px(0);
-        hipLaunchKernelGGL(ak_score8_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, stream, s.x1, P + l.pw[3], P + l.pw[7], s.g2, s.g3, s.g4,
+        hipLaunchKernelGGL(ak_score8_kernel, dim3(blocks_256(np)), dim3(256), 0, stream, s.x1, P + l.pw[3], P + l.pw[7], s.g2, s.g3, s.g4,
                            s8, Hp, Wp, np);
         AkConvP c{s8, 0, 0, 0, 0, 0, 8, 8, P + l.vw[6], P + l.vb[6], s4a, 4, Hp, Wp, Hp, Wp, 0, 0};
         ak_conv3<4, 8, 1>(c, B, stream);

@@ -102,6 +102,8 @@ __device__ __forceinline__ int wave_sum_i(int v) {
     return v;
 }
 
+__device__ __forceinline__ float4 max4(float4 a, float4 b) { return make_float4(fmaxf(a.x, b.x), fmaxf(a.y, b.y), fmaxf(a.z, b.z), fmaxf(a.w, b.w)); }
+
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
 // log(sigmoid(x)) = min(x,0) - log1p(exp(-|x|))  (same form ATen uses)
 __device__ __forceinline__ float logsigmoidf_(float x) { return fminf(x, 0.0f) - log1pf(expf(-fabsf(x))); }
@@ -147,6 +149,9 @@ static inline bool imcui_lds_optin(std::atomic<unsigned long long>& done, const 
 }
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+// workgroups of 256 threads for n items: one thread per item, and the capped grid of a grid-stride loop
+static inline unsigned blocks_256(long n) { return (unsigned)((n + 255) / 256); }
+static inline unsigned grid_stride_blocks(long n) { return (n + 255) / 256 < 65536 ? blocks_256(n) : 65536u; }
 
 // status codes of the C ABI
 #define IMCUI_OK 0

@@ -8,7 +8,7 @@
 //               float32 roundings), so the zero padding of layer 0 stays zero in normalised units
 //   layer 0     3 -> 64 on the VALU, NHWC out
 //   conv1_2 .. conv3_3   the patch-staging 3x3 convolutions (conv.hip, both arithmetic modes) with the fused 2x2 max-pool where the
-//               map is even; an odd map takes the un-pooled launch and d2_maxpool_kernel (flooring, as nn.MaxPool2d)
+//               map is even; an odd map takes the un-pooled launch and pool2x2_kernel<0> (flooring, as nn.MaxPool2d)
 //   avg-pool    2x2, stride 1: (h, w) -> (h - 1, w - 1)
 //   conv4_1 .. conv4_3   dilation 2 on the implicit GEMM (gemm.hip, GemmP.conv_dil = 2; K = 2304 / 4608 summed in two levels there),
 //               ReLU in the epilogue (conv4_3: use_relu)
@@ -33,6 +33,7 @@
 
 #include "conv.h"
 #include "imcui_hip.h"
+#include "net_kernels.h"
 #include "netpack.h"
 #include "select.h"
 
@@ -138,109 +139,20 @@ __device__ __forceinline__ float d2_norm(float x, int c) {
     return __fsub_rn(__fmul_rn(x, 255.0f), mean);
 }
 
-// ATen's upsample_bilinear2d source index, align_corners=True: scale * dst with scale = (in - 1) / (out - 1)
-__device__ __forceinline__ void d2_src_index(int o, float scale, int in, int* i0, int* i1, float* l0, float* l1) {
-    const float s = __fmul_rn(scale, (float)o);
-    const int a = min((int)s, in - 1);
-    *i0 = a;
-    *i1 = a + (a < in - 1 ? 1 : 0);
-    *l1 = fminf(fmaxf(__fsub_rn(s, (float)a), 0.0f), 1.0f);
-    *l0 = __fsub_rn(1.0f, *l1);
-}
-static float d2_ac_scale(int in, int out) { return out > 1 ? (float)(in - 1) / (float)(out - 1) : 0.0f; }
+static float d2_ac_scale(int in, int out) { return out > 1 ? (float)(in - 1) / (float)(out - 1) : 0.0f; }  // align_corners=True
 
-// the normalised image, planar [B, 3, hi, wi] -> [B, 3, ho, wo] (channels stay RGB; layer 0 flips)
-__global__ __launch_bounds__(256) void d2_resize_kernel(const float* __restrict__ src, float* __restrict__ dst, int hi, int wi, int ho, int wo, float sh,
-                                                        float sw, long n) {
-    const long p = (long)blockIdx.x * 256 + threadIdx.x;
-    if (p >= n) return;
-    const int x = (int)(p % wo);
-    const long q = p / wo;
-    const int y = (int)(q % ho);
-    const long bc = q / ho;
-    const int c = (int)(bc % 3);
-    int y0, y1, x0, x1;
-    float hy0, hy1, wx0, wx1;
-    d2_src_index(y, sh, hi, &y0, &y1, &hy0, &hy1);
-    d2_src_index(x, sw, wi, &x0, &x1, &wx0, &wx1);
-    const float* pl = src + bc * (long)hi * wi;
-    const float v00 = d2_norm(pl[(long)y0 * wi + x0], c), v01 = d2_norm(pl[(long)y0 * wi + x1], c), v10 = d2_norm(pl[(long)y1 * wi + x0], c),
-                v11 = d2_norm(pl[(long)y1 * wi + x1], c);
-    const float top = __fadd_rn(__fmul_rn(wx0, v00), __fmul_rn(wx1, v01)), bot = __fadd_rn(__fmul_rn(wx0, v10), __fmul_rn(wx1, v11));
-    dst[p] = __fadd_rn(__fmul_rn(hy0, top), __fmul_rn(hy1, bot));
-}
-
-// layer 0: 3 -> 64, 3x3, pad 1, ReLU; one thread per pixel, the 27 window values in registers (input channel ci of the network is image
-// channel 2 - ci), the weights [tap][cin][64] in LDS (wave-uniform reads); taps and channels summed in ascending order
-__global__ __launch_bounds__(256) void d2_conv0_kernel(const float* __restrict__ img, const float* __restrict__ w, const float* __restrict__ bias,
-                                                       float* __restrict__ out, int h, int wd, int norm, long npix) {
-    __shared__ float sw[27 * 64 + 64];
-    for (int i = threadIdx.x; i < 27 * 64 + 64; i += 256) sw[i] = i < 27 * 64 ? w[i] : bias[i - 27 * 64];
-    __syncthreads();
-    const long p = (long)blockIdx.x * 256 + threadIdx.x;
-    if (p >= npix) return;
-    const int x = (int)(p % wd);
-    const long q = p / wd;
-    const int y = (int)(q % h);
-    const long b = q / h;
-    float win[27];
-#pragma unroll
-    for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-        for (int kx = 0; kx < 3; ++kx) {
-            const int yy = y + ky - 1, xx = x + kx - 1;
-            const bool in = yy >= 0 && yy < h && xx >= 0 && xx < wd;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                float v = 0.0f;
-                if (in) {
-                    v = img[((b * 3 + (2 - c)) * h + yy) * (long)wd + xx];
-                    if (norm) v = d2_norm(v, 2 - c);
-                }
-                win[(ky * 3 + kx) * 3 + c] = v;
-            }
-        }
-    float* o = out + p * 64;
-#pragma unroll 2
-    for (int c0 = 0; c0 < 64; c0 += 4) {
-        float a[4] = {sw[27 * 64 + c0], sw[27 * 64 + c0 + 1], sw[27 * 64 + c0 + 2], sw[27 * 64 + c0 + 3]};
-#pragma unroll
-        for (int t = 0; t < 27; ++t)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) a[j] = fmaf(win[t], sw[t * 64 + c0 + j], a[j]);
-        *reinterpret_cast<float4*>(o + c0) = make_float4(fmaxf(a[0], 0.0f), fmaxf(a[1], 0.0f), fmaxf(a[2], 0.0f), fmaxf(a[3], 0.0f));
+// what the level resize reads: the normalised image (channels stay RGB; layer 0 flips)
+struct D2ResizeLoad {
+    __device__ float operator()(float v, long plane) const { return d2_norm(v, (int)(plane % 3)); }
+};
+// what layer 0 reads: input channel c of the network is image channel 2 - c; norm: the image is the raw one
+struct D2StemLoad {
+    int norm;
+    __device__ float operator()(const float* __restrict__ img, long b, int c, int h, int w, int yy, int xx) const {
+        const float v = img[((b * 3 + (2 - c)) * h + yy) * (long)w + xx];
+        return norm ? d2_norm(v, 2 - c) : v;
     }
-}
-
-__device__ __forceinline__ float4 d2_max4(float4 a, float4 b) { return make_float4(fmaxf(a.x, b.x), fmaxf(a.y, b.y), fmaxf(a.z, b.z), fmaxf(a.w, b.w)); }
-__device__ __forceinline__ float4 d2_add4(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
-
-// MODE 0: nn.MaxPool2d(2, 2) of an NHWC map, flooring: [B, hi, wi, C] -> [B, hi / 2, wi / 2, C] (the last row / column of an odd map is
-// not read).  MODE 1: nn.AvgPool2d(2, stride=1): -> [B, hi - 1, wi - 1, C], the window summed row-major, then / 4.  n4 = float4s of the output
-template <int MODE>
-__global__ __launch_bounds__(256) void d2_pool_kernel(const float* __restrict__ src, float* __restrict__ dst, int hi, int wi, int ho, int wo, int C, long n4) {
-    const int C4 = C >> 2;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
-        const int c = (int)(i % C4) * 4;
-        long t = i / C4;
-        const int x = (int)(t % wo);
-        t /= wo;
-        const int y = (int)(t % ho);
-        const long b = t / ho;
-        const int st = MODE == 0 ? 2 : 1;
-        const float* s = src + ((b * hi + (long)st * y) * wi + (long)st * x) * C + c;
-        const float4 v00 = *reinterpret_cast<const float4*>(s), v01 = *reinterpret_cast<const float4*>(s + C),
-                     v10 = *reinterpret_cast<const float4*>(s + (long)wi * C), v11 = *reinterpret_cast<const float4*>(s + (long)wi * C + C);
-        float4 o;
-        if (MODE == 0) {
-            o = d2_max4(d2_max4(v00, v01), d2_max4(v10, v11));
-        } else {
-            o = d2_add4(d2_add4(d2_add4(v00, v01), v10), v11);
-            o = make_float4(o.x * 0.25f, o.y * 0.25f, o.z * 0.25f, o.w * 0.25f);
-        }
-        *reinterpret_cast<float4*>(dst + i * 4) = o;
-    }
-}
+};
 
 // pyramid.py `dense_features += F.interpolate(previous_dense_features, size=[h, w], mode='bilinear', align_corners=True)`, NHWC, in
 // place on f [B, h, w, C]; prev [B, ph, pw, C]
@@ -256,8 +168,8 @@ __global__ __launch_bounds__(256) void d2_addup_kernel(float* __restrict__ f, co
         const long b = t / h;
         int y0, y1, x0, x1;
         float hy0, hy1, wx0, wx1;
-        d2_src_index(y, sh, ph, &y0, &y1, &hy0, &hy1);
-        d2_src_index(x, sw, pw, &x0, &x1, &wx0, &wx1);
+        bilinear_src_align_corners(y, sh, ph, &y0, &y1, &hy0, &hy1);
+        bilinear_src_align_corners(x, sw, pw, &x0, &x1, &wx0, &wx1);
         const float* pb = prev + b * (long)ph * pw * C + c;
         const float4 v00 = *reinterpret_cast<const float4*>(pb + ((long)y0 * pw + x0) * C), v01 = *reinterpret_cast<const float4*>(pb + ((long)y0 * pw + x1) * C),
                      v10 = *reinterpret_cast<const float4*>(pb + ((long)y1 * pw + x0) * C), v11 = *reinterpret_cast<const float4*>(pb + ((long)y1 * pw + x1) * C);
@@ -388,47 +300,6 @@ struct D2Emit {
         cpix[(long)b * kcap + s] = pix;
     }
 };
-__global__ void d2_advance_kernel(int* __restrict__ base, const int* __restrict__ nlev, int B) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b < B) base[b] += nlev[b];  // (the true count: an overflow stays visible)
-}
-__global__ void d2_zero_kernel(int* __restrict__ p, int n) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) p[i] = 0;
-}
-
-// (score, candidate index) as one ordered key: a stable argsort puts equal scores in list order
-__device__ __forceinline__ unsigned long long d2_key(float s, int i) { return ((unsigned long long)order_key(s) << 32) | (unsigned)i; }
-
-// The cut.  One workgroup per image: more than `limit` candidates -> the `limit` largest keys stay; the kept slots leave in candidate
-// order (kslot), the emit kernel ranks them.
-__global__ __launch_bounds__(1024) void d2_cut_kernel(const float* __restrict__ cscore, const int* __restrict__ ntotal, int kcap, int limit_,
-                                                      int* __restrict__ kslot, int* __restrict__ nkept, int* __restrict__ status) {
-    __shared__ int wcnt[16];
-    const int b = blockIdx.x, tid = threadIdx.x;
-    const float* cs = cscore + (long)b * kcap;
-    int* ks = kslot + (long)b * kcap;
-    const int n = min(ntotal[b], kcap);
-    if (tid == 0 && ntotal[b] > kcap) atomicOr(status, 2);  // candidate capacity too small
-    bool filter = false;
-    unsigned long long kth = 0;
-    int limit = n;
-    if (limit_ > 0 && n > limit_) {
-        filter = true;
-        limit = limit_;
-        kth = radix_select_kth<1024, unsigned long long>([&](int i) { return d2_key(cs[i], i); }, n, limit_);
-    }
-    int run = 0;
-    for (int base = 0; base < n; base += 1024) {
-        const int i = base + tid;
-        const bool keep = i < n && (!filter || d2_key(cs[i], i) >= kth);
-        int tot;
-        const int pos = run + block_ordered_rank<16>(keep, wcnt, &tot);
-        if (keep && pos < limit) ks[pos] = i;
-        run += tot;
-    }
-    if (tid == 0) nkept[b] = min(run, limit);
-}
 
 // One workgroup = 256 kept candidates: the rank of each in ascending (score, slot) order (the kept list is in slot order), then one wave
 // per key-point: the step again (d2_eval: the same arithmetic as the detector's), interpolate_dense_features' four corners with
@@ -438,7 +309,6 @@ __global__ __launch_bounds__(256) void d2_emit_kernel(const float* __restrict__ 
                                                       const float* __restrict__ feat0, const int* __restrict__ kslot, const int* __restrict__ nkept, int kcap,
                                                       int kout, D2Levels lv, int C, float* __restrict__ kpts, float* __restrict__ scores,
                                                       float* __restrict__ desc, int* __restrict__ nkpts) {
-    __shared__ float tile[256];
     __shared__ int rank_s[256];
     const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, nk = C >> 6;
     const float* cs = cscore + (long)b * kcap;
@@ -455,20 +325,7 @@ __global__ __launch_bounds__(256) void d2_emit_kernel(const float* __restrict__ 
         if (i >= n)
             for (int k = 0; k < nk; ++k) de[(long)i * C + k * 64 + lane] = 0.0f;
     if (i0 >= n) return;  // (uniform)
-    const int i = i0 + tid;
-    const float mine = i < n ? cs[ks[i]] : 0.0f;
-    int rank = 0;
-    for (int base = 0; base < n; base += 256) {
-        __syncthreads();
-        tile[tid] = base + tid < n ? cs[ks[base + tid]] : INFINITY;
-        __syncthreads();
-        const int m = min(256, n - base);
-        for (int j = 0; j < m; ++j) {
-            const float o = tile[j];
-            rank += (o < mine || (o == mine && base + j < i)) ? 1 : 0;
-        }
-    }
-    rank_s[tid] = rank;
+    rank_s[tid] = kept_rank_ascending(cs, ks, n, i0 + tid);
     __syncthreads();
     for (int q = wv; q < min(256, n - i0); q += 4) {
         const int slot = ks[i0 + q], r = rank_s[q];
@@ -515,7 +372,18 @@ __global__ __launch_bounds__(256) void d2_emit_kernel(const float* __restrict__ 
 
 }  // namespace
 
-static unsigned d2_grid(long n) { return (unsigned)std::min((n + 255) / 256, (long)65536); }
+// layer 0 on the planar image [B, 3, H, W] -> out [B, H, W, 64]
+static void d2_stem(const D2Layout& l, const float* P, const float* img, int norm, int B, int H, int W, float* out, hipStream_t stream) {
+    const long npix = (long)B * H * W;
+    hipLaunchKernelGGL((stem3x3_kernel<64, D2StemLoad>), dim3(blocks_256(npix)), dim3(256), 0, stream, img, P + l.w0, P + l.b0, out, H, W, D2StemLoad{norm}, npix);
+}
+// MODE 0: the flooring 2x2 max-pool, [B, hi, wi, C] -> [B, hi / 2, wi / 2, C]; MODE 1: the 2x2 stride-1 average -> [B, hi - 1, wi - 1, C]
+template <int MODE>
+static void d2_pool(const float* src, float* dst, int B, int hi, int wi, int C, hipStream_t stream) {
+    const int ho = MODE == 0 ? hi / 2 : hi - 1, wo = MODE == 0 ? wi / 2 : wi - 1;
+    const long n4 = (long)B * ho * wo * (C / 4);
+    hipLaunchKernelGGL(pool2x2_kernel<MODE>, dim3(grid_stride_blocks(n4)), dim3(256), 0, stream, src, dst, hi, wi, ho, wo, C, n4);
+}
 
 // ------------------------------------------------------------------ workspace
 struct D2Ws {
@@ -593,8 +461,7 @@ static int d2_trunk(imcui_hip_t* h, const D2Layout& l, const float* P, const flo
                     float* out, hipStream_t stream) {
     const bool split = h->precision == 1;
     int rc;
-    const long npix0 = (long)B * H * W;
-    hipLaunchKernelGGL(d2_conv0_kernel, dim3((unsigned)((npix0 + 255) / 256)), dim3(256), 0, stream, img, P + l.w0, P + l.b0, s.fa, H, W, norm, npix0);
+    d2_stem(l, P, img, norm, B, H, W, s.fa, stream);
     IMCUI_CHECK_LAUNCH(h);
     float *cur = s.fa, *oth = s.fb;
     int hh = H, ww = W;
@@ -611,26 +478,20 @@ static int d2_trunk(imcui_hip_t* h, const D2Layout& l, const float* P, const flo
         IMCUI_RUN(conv(i, fused ? 1 : 0));
         std::swap(cur, oth);
         if (L.pool) {
-            const int ho = hh / 2, wo = ww / 2;
             if (!fused) {  // an odd map: nn.MaxPool2d floors
-                const long n4 = (long)B * ho * wo * (L.cout / 4);
-                hipLaunchKernelGGL(d2_pool_kernel<0>, dim3(d2_grid(n4)), dim3(256), 0, stream, cur, oth, hh, ww, ho, wo, L.cout, n4);
+                d2_pool<0>(cur, oth, B, hh, ww, L.cout, stream);
                 IMCUI_CHECK_LAUNCH(h);
                 std::swap(cur, oth);
             }
-            hh = ho;
-            ww = wo;
+            hh /= 2;
+            ww /= 2;
         }
     }
-    {  // nn.AvgPool2d(2, stride=1)
-        const int ho = hh - 1, wo = ww - 1;
-        const long n4 = (long)B * ho * wo * (256 / 4);
-        hipLaunchKernelGGL(d2_pool_kernel<1>, dim3(d2_grid(n4)), dim3(256), 0, stream, cur, oth, hh, ww, ho, wo, 256, n4);
-        IMCUI_CHECK_LAUNCH(h);
-        std::swap(cur, oth);
-        hh = ho;
-        ww = wo;
-    }
+    d2_pool<1>(cur, oth, B, hh, ww, 256, stream);  // nn.AvgPool2d(2, stride=1)
+    IMCUI_CHECK_LAUNCH(h);
+    std::swap(cur, oth);
+    --hh;
+    --ww;
     for (int i = 7; i < D2_NL; ++i) {
         const D2Layer& L = D2_LAYERS[i];
         GemmP g;
@@ -665,7 +526,7 @@ static int d2_detect_level(imcui_hip_t* h, const D2Ws& s, const float* feat, int
     hipLaunchKernelGGL((cand_count_kernel<D2Pred>), dim3(nchunk, B), dim3(256), 0, stream, feat, dom, pred, s.blkcnt, nchunk);
     hipLaunchKernelGGL((exclusive_scan_kernel<int>), dim3(B), dim3(1024), 0, stream, s.blkcnt, s.blkoff, s.nlev, (const int*)nullptr, nchunk, (long)nchunk);
     hipLaunchKernelGGL((cand_compact_kernel<D2Pred, D2Emit>), dim3(nchunk, B), dim3(256), 0, stream, feat, dom, pred, s.blkoff, nchunk, dom, emit);
-    hipLaunchKernelGGL(d2_advance_kernel, dim3(cdiv(B, 256)), dim3(256), 0, stream, s.base, s.nlev, B);
+    hipLaunchKernelGGL(advance_base_kernel<>, dim3(cdiv(B, 256)), dim3(256), 0, stream, s.base, s.nlev, B);
     IMCUI_CHECK_LAUNCH(h);
     return IMCUI_OK;
 }
@@ -687,8 +548,8 @@ extern "C" int imcui_hip_d2net_forward(imcui_hip_t* h, const float* packed, cons
     D2Ws s = d2_carve(ws, ws_bytes, B, z.imgpix, z.fpix_sum, z.fpix_max, D2_DIM, kcap, true);
     if (!ws || !s.ok) return imcui_set_err(h, IMCUI_ERR_WS, "d2net: workspace too small (%zu < %zu)", ws_bytes, s.total);
     int* st = status ? status : s.status;
-    hipLaunchKernelGGL(d2_zero_kernel, dim3(cdiv(B, 256)), dim3(256), 0, stream, s.base, B);
-    hipLaunchKernelGGL(d2_zero_kernel, dim3(1), dim3(64), 0, stream, st, 1);
+    hipLaunchKernelGGL(zero_i32_kernel<>, dim3(cdiv(B, 256)), dim3(256), 0, stream, s.base, B);
+    hipLaunchKernelGGL(zero_i32_kernel<>, dim3(1), dim3(64), 0, stream, st, 1);
     D2Levels lv;
     for (int i = 0; i < D2_MAXLEV; ++i) lv.off[i] = 0, lv.h[i] = lv.w[i] = 1, lv.rs[i] = lv.cs[i] = 1.0f;
     long off = 0;
@@ -704,8 +565,8 @@ extern "C" int imcui_hip_d2net_forward(imcui_hip_t* h, const float* packed, cons
         const bool same = ch == H && cw == W;  // align_corners=True at scale 1 is the identity
         if (!same) {
             const long n = (long)B * 3 * ch * cw;
-            hipLaunchKernelGGL(d2_resize_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, image, s.img, H, W, ch, cw, d2_ac_scale(H, ch),
-                               d2_ac_scale(W, cw), n);
+            hipLaunchKernelGGL((resize_planar_kernel<bilinear_src_align_corners, D2ResizeLoad>), dim3(blocks_256(n)), dim3(256), 0, stream, image, s.img, H, W,
+                               ch, cw, d2_ac_scale(H, ch), d2_ac_scale(W, cw), D2ResizeLoad{}, n);
             IMCUI_CHECK_LAUNCH(h);
             cur = s.img;
         }
@@ -713,7 +574,7 @@ extern "C" int imcui_hip_d2net_forward(imcui_hip_t* h, const float* packed, cons
         IMCUI_RUN(d2_trunk(h, l, packed, cur, same ? 1 : 0, B, ch, cw, use_relu, s, f, stream));
         const long nf = (long)B * fh * fw * D2_DIM;
         if (lev > 0) {
-            hipLaunchKernelGGL(d2_addup_kernel, dim3(d2_grid(nf / 4)), dim3(256), 0, stream, f, s.feat + lv.off[lev - 1], fh, fw, ph, pw, D2_DIM,
+            hipLaunchKernelGGL(d2_addup_kernel, dim3(grid_stride_blocks(nf / 4)), dim3(256), 0, stream, f, s.feat + lv.off[lev - 1], fh, fw, ph, pw, D2_DIM,
                                d2_ac_scale(ph, fh), d2_ac_scale(pw, fw), nf / 4);
             IMCUI_CHECK_LAUNCH(h);
         }
@@ -723,7 +584,7 @@ extern "C" int imcui_hip_d2net_forward(imcui_hip_t* h, const float* packed, cons
         ph = fh;
         pw = fw;
     }
-    hipLaunchKernelGGL(d2_cut_kernel, dim3(B), dim3(1024), 0, stream, s.cscore, s.base, kcap, max_keypoints, s.kslot, s.nkept, st);
+    hipLaunchKernelGGL(cand_cut_kernel<>, dim3(B), dim3(1024), 0, stream, s.cscore, s.base, kcap, max_keypoints, s.kslot, s.nkept, st);
     hipLaunchKernelGGL(d2_emit_kernel, dim3(cdiv(kout, 256), B), dim3(256), 0, stream, s.cscore, s.clc, s.cpix, s.feat, s.kslot, s.nkept, kcap, kout, lv,
                        D2_DIM, keypoints, scores, descriptors, num_keypoints);
     IMCUI_CHECK_LAUNCH(h);
@@ -739,17 +600,14 @@ extern "C" int imcui_hip_d2net_layer_probe(imcui_hip_t* h, int op, const float* 
     if (B < 1 || H < 1 || W < 1 || !in || !out || (long)B * H * W > 0x7fffffffL / 512) return imcui_set_err(h, IMCUI_ERR_ARG, "d2net layer probe: shape");
     if (op == 0) {
         if (!packed) return imcui_set_err(h, IMCUI_ERR_ARG, "d2net layer probe: layer 0 needs the packed weights");
-        const D2Layout l = d2_layout();
-        const long npix = (long)B * H * W;
-        hipLaunchKernelGGL(d2_conv0_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, stream, in, packed + l.w0, packed + l.b0, out, H, W, 1, npix);
+        d2_stem(d2_layout(), packed, in, 1, B, H, W, out, stream);
     } else if (op == 1 || op == 2) {
         const int ho = op == 1 ? H / 2 : H - 1, wo = op == 1 ? W / 2 : W - 1;
         if (C < 4 || C % 4 || C > 512 || ho < 1 || wo < 1) return imcui_set_err(h, IMCUI_ERR_ARG, "d2net layer probe: C=%d (a multiple of 4 up to 512), %dx%d", C, H, W);
-        const long n4 = (long)B * ho * wo * (C / 4);
         if (op == 1)
-            hipLaunchKernelGGL(d2_pool_kernel<0>, dim3(d2_grid(n4)), dim3(256), 0, stream, in, out, H, W, ho, wo, C, n4);
+            d2_pool<0>(in, out, B, H, W, C, stream);
         else
-            hipLaunchKernelGGL(d2_pool_kernel<1>, dim3(d2_grid(n4)), dim3(256), 0, stream, in, out, H, W, ho, wo, C, n4);
+            d2_pool<1>(in, out, B, H, W, C, stream);
     } else {
         return imcui_set_err(h, IMCUI_ERR_ARG, "d2net layer probe: op %d", op);
     }
@@ -779,14 +637,14 @@ extern "C" int imcui_hip_d2net_detect_probe(imcui_hip_t* h, const float* feat, i
     if (!ws || !s.ok) return imcui_set_err(h, IMCUI_ERR_WS, "d2net probe: workspace too small (%zu < %zu)", ws_bytes, s.total);
     int* st = status ? status : s.status;
     int rc;
-    hipLaunchKernelGGL(d2_zero_kernel, dim3(cdiv(B, 256)), dim3(256), 0, stream, s.base, B);
-    hipLaunchKernelGGL(d2_zero_kernel, dim3(1), dim3(64), 0, stream, st, 1);
+    hipLaunchKernelGGL(zero_i32_kernel<>, dim3(cdiv(B, 256)), dim3(256), 0, stream, s.base, B);
+    hipLaunchKernelGGL(zero_i32_kernel<>, dim3(1), dim3(64), 0, stream, st, 1);
     D2Levels lv;
     for (int i = 0; i < D2_MAXLEV; ++i) lv.off[i] = 0, lv.h[i] = lv.w[i] = 1, lv.rs[i] = lv.cs[i] = 1.0f;
     lv.h[0] = fh;
     lv.w[0] = fw;
     IMCUI_RUN(d2_detect_level(h, s, feat, B, fh, fw, C, 0, nullptr, 0, 0, s.ban[0], kcap, stream));
-    hipLaunchKernelGGL(d2_cut_kernel, dim3(B), dim3(1024), 0, stream, s.cscore, s.base, kcap, max_keypoints, s.kslot, s.nkept, st);
+    hipLaunchKernelGGL(cand_cut_kernel<>, dim3(B), dim3(1024), 0, stream, s.cscore, s.base, kcap, max_keypoints, s.kslot, s.nkept, st);
     hipLaunchKernelGGL(d2_emit_kernel, dim3(cdiv(kout, 256), B), dim3(256), 0, stream, s.cscore, s.clc, s.cpix, feat, s.kslot, s.nkept, kcap, kout, lv, C,
                        keypoints, scores, descriptors, num_keypoints);
     IMCUI_CHECK_LAUNCH(h);

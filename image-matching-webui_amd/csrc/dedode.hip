@@ -7,7 +7,7 @@
 // and block counts come from the checkpoint (`dims`, read from the tensors by the binding).
 //   layer 0     3 -> 64 on the VALU with Normalize applied as the raw image is read (zero padding stays zero in normalised units)
 //   encoder     conv3x3_launch / conv3x3_split_launch.  Every layer in front of a pool IS a feature, so its un-pooled map has to
-//               exist: those layers take the un-pooled launch and dd_pool_kernel follows; the fused pool has no layer to serve here
+//               exist: those layers take the un-pooled launch and pool2x2_kernel<0> follows; the fused pool has no layer to serve here
 //   refiner     block1.0 on the shared GEMM with feature and context as two K slabs (no concat buffer), ReLU in the epilogue; every
 //               other 1x1 on the same GEMM; the depth-wise 5x5 + folded BN + ReLU is dd_dw5_kernel (LDS tile with a 2-pixel halo,
 //               channels innermost); the x0 residual rides in the epilogue of the last hidden block's 1x1, `/ 1.4` is a pass of its own
@@ -35,6 +35,7 @@
 
 #include "conv.h"
 #include "imcui_hip.h"
+#include "net_kernels.h"
 #include "netpack.h"
 #include "select.h"
 
@@ -339,70 +340,15 @@ __device__ __forceinline__ float dd_exp(float x) {
     return ldexpf(y, (int)n);
 }
 
-// layer 0: 3 -> 64, 3x3, pad 1, folded BN, ReLU; one thread per pixel, the 27 window values in registers, the weights [tap][cin][64] in
-// LDS (wave-uniform reads).  norm: transforms.Normalize, (x - mean) / std with one rounding each
-__global__ __launch_bounds__(256) void dd_conv0_kernel(const float* __restrict__ img, const float* __restrict__ w, const float* __restrict__ bias,
-                                                       float* __restrict__ out, int h, int wd, int norm, long npix) {
-    __shared__ float sw[27 * 64 + 64];
-    for (int i = threadIdx.x; i < 27 * 64 + 64; i += 256) sw[i] = i < 27 * 64 ? w[i] : bias[i - 27 * 64];
-    __syncthreads();
-    const long p = (long)blockIdx.x * 256 + threadIdx.x;
-    if (p >= npix) return;
-    const int x = (int)(p % wd);
-    const long q = p / wd;
-    const int y = (int)(q % h);
-    const long b = q / h;
-    float win[27];
-#pragma unroll
-    for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-        for (int kx = 0; kx < 3; ++kx) {
-            const int yy = y + ky - 1, xx = x + kx - 1;
-            const bool in = yy >= 0 && yy < h && xx >= 0 && xx < wd;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                float v = 0.0f;
-                if (in) {
-                    v = img[((b * 3 + c) * h + yy) * (long)wd + xx];
-                    if (norm) {
-                        const float mean = c == 0 ? 0.485f : (c == 1 ? 0.456f : 0.406f), sd = c == 0 ? 0.229f : (c == 1 ? 0.224f : 0.225f);
-                        v = __fdiv_rn(__fsub_rn(v, mean), sd);
-                    }
-                }
-                win[(ky * 3 + kx) * 3 + c] = v;
-            }
-        }
-    float* o = out + p * 64;
-#pragma unroll 2
-    for (int c0 = 0; c0 < 64; c0 += 4) {
-        float a[4] = {sw[27 * 64 + c0], sw[27 * 64 + c0 + 1], sw[27 * 64 + c0 + 2], sw[27 * 64 + c0 + 3]};
-#pragma unroll
-        for (int t = 0; t < 27; ++t)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) a[j] = fmaf(win[t], sw[t * 64 + c0 + j], a[j]);
-        *reinterpret_cast<float4*>(o + c0) = make_float4(fmaxf(a[0], 0.0f), fmaxf(a[1], 0.0f), fmaxf(a[2], 0.0f), fmaxf(a[3], 0.0f));
+// what layer 0 reads: transforms.Normalize of the raw image, (x - mean) / std with one rounding each
+struct DdStemLoad {
+    __device__ float operator()(const float* __restrict__ img, long b, int c, int h, int w, int yy, int xx) const {
+        const float mean = c == 0 ? 0.485f : (c == 1 ? 0.456f : 0.406f), sd = c == 0 ? 0.229f : (c == 1 ? 0.224f : 0.225f);
+        return __fdiv_rn(__fsub_rn(img[((b * 3 + c) * h + yy) * (long)w + xx], mean), sd);
     }
-}
+};
 
-__device__ __forceinline__ float4 dd_max4(float4 a, float4 b) { return make_float4(fmaxf(a.x, b.x), fmaxf(a.y, b.y), fmaxf(a.z, b.z), fmaxf(a.w, b.w)); }
 __device__ __forceinline__ float4 dd_fma4(float4 a, float4 b, float4 c) { return make_float4(fmaf(a.x, b.x, c.x), fmaf(a.y, b.y, c.y), fmaf(a.z, b.z, c.z), fmaf(a.w, b.w, c.w)); }
-
-// nn.MaxPool2d(2, 2) of an NHWC map with even sides: [B, 2 ho, 2 wo, C] -> [B, ho, wo, C]; n4 = float4s of the output
-__global__ __launch_bounds__(256) void dd_pool_kernel(const float* __restrict__ src, float* __restrict__ dst, int ho, int wo, int C, long n4) {
-    const int C4 = C >> 2, wi = 2 * wo;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
-        const int c = (int)(i % C4) * 4;
-        long t = i / C4;
-        const int x = (int)(t % wo);
-        t /= wo;
-        const int y = (int)(t % ho);
-        const long b = t / ho;
-        const float* s = src + ((b * 2 * ho + 2L * y) * wi + 2L * x) * C + c;
-        const float4 v00 = *reinterpret_cast<const float4*>(s), v01 = *reinterpret_cast<const float4*>(s + C),
-                     v10 = *reinterpret_cast<const float4*>(s + (long)wi * C), v11 = *reinterpret_cast<const float4*>(s + (long)wi * C + C);
-        *reinterpret_cast<float4*>(dst + i * 4) = dd_max4(dd_max4(v00, v01), dd_max4(v10, v11));
-    }
-}
 
 // Depth-wise 5x5 (pad 2) + folded BatchNorm + ReLU on an NHWC map [B, H, W, C], C % 32 == 0; w [25 taps][C], bias [C].
 // One workgroup = 8 x 16 pixels x 32 channels: the 12 x 20 pixel window (2-pixel halo, zeros outside the map) is staged in LDS with the
@@ -454,7 +400,7 @@ __global__ __launch_bounds__(256) void dd_dw5_kernel(const float* __restrict__ i
 #pragma unroll
     for (int o = 0; o < 4; ++o) {
         const int gy = ty0 + yb + o;
-        if (gy < H) *reinterpret_cast<float4*>(ob + ((long)gy * W + gx) * C) = dd_max4(acc[o], z);
+        if (gy < H) *reinterpret_cast<float4*>(ob + ((long)gy * W + gx) * C) = max4(acc[o], z);
     }
 }
 
@@ -672,20 +618,11 @@ __device__ __forceinline__ unsigned long long dd_key(float s, int i) { return ((
 
 // The cut.  One workgroup per image, every pixel a candidate: the k largest keys stay and leave in pixel order (klist [B, k]).
 __global__ __launch_bounds__(1024) void dd_cut_kernel(const float* __restrict__ score, int npix, int k, int* __restrict__ klist) {
-    __shared__ int wcnt[16];
-    const int b = blockIdx.x, tid = threadIdx.x;
+    const int b = blockIdx.x;
     const float* sc = score + (long)b * npix;
-    int* ks = klist + (long)b * k;
-    const unsigned long long kth = radix_select_kth<1024, unsigned long long>([&](int i) { return dd_key(sc[i], i); }, npix, k);
-    int run = 0;
-    for (int base = 0; base < npix; base += 1024) {
-        const int i = base + tid;
-        const bool keep = i < npix && dd_key(sc[i], i) >= kth;
-        int tot;
-        const int pos = run + block_ordered_rank<16>(keep, wcnt, &tot);
-        if (keep && pos < k) ks[pos] = i;
-        run += tot;
-    }
+    const auto key_at = [&](int i) { return dd_key(sc[i], i); };
+    const unsigned long long kth = radix_select_kth<1024, unsigned long long>(key_at, npix, k);
+    keep_kth_in_order(key_at, npix, true, kth, k, klist + (long)b * k);
 }
 
 // One workgroup = 256 kept pixels: the rank of each in descending key order, then row `rank` gets the key-point: grid coordinate
@@ -774,15 +711,7 @@ __global__ __launch_bounds__(256) void dd_describe_kernel(const int* __restrict_
     for (int q = 0; q < 4; ++q) de[lane + 64 * q] = o[q];
 }
 
-__global__ void dd_zero_kernel(int* __restrict__ p, int n) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) p[i] = 0;
-}
-
 }  // namespace
-
-static unsigned dd_grid(long n) { return (unsigned)std::min((n + 255) / 256, (long)65536); }
-static unsigned dd_grid1(long n) { return (unsigned)((n + 255) / 256); }
 
 // ------------------------------------------------------------------ workspace
 struct DdWs {
@@ -853,6 +782,12 @@ static int dd_dw5(imcui_hip_t* h, const float* in, const float* w, const float* 
     return IMCUI_OK;
 }
 
+// layer 0 (weights w0, bias b0 of one model) on the raw planar image [B, 3, H, W] -> out [B, H, W, 64]
+static void dd_stem(const float* image, const float* w0, const float* b0, float* out, int B, int H, int W, hipStream_t stream) {
+    const long npix = (long)B * H * W;
+    hipLaunchKernelGGL((stem3x3_kernel<64, DdStemLoad>), dim3(blocks_256(npix)), dim3(256), 0, stream, image, w0, b0, out, H, W, DdStemLoad{}, npix);
+}
+
 // the encoder of model m on the raw image: features of steps 0..3 (scales 8, 4, 2, 1) -> s.feat
 static int dd_encoder(imcui_hip_t* h, int m, const DdLayout& l, const float* P, const float* image, int B, int H, int W, const DdWs& s, hipStream_t stream) {
     const bool split = h->precision == 1;
@@ -864,8 +799,7 @@ static int dd_encoder(imcui_hip_t* h, int m, const DdLayout& l, const float* P, 
     for (int i = 0; i < e.nconv; ++i) {
         float* dst = e.feat[i] ? s.feat[step] : s.enc[pp];
         if (i == 0) {
-            const long npix0 = (long)B * H * W;
-            hipLaunchKernelGGL(dd_conv0_kernel, dim3(dd_grid1(npix0)), dim3(256), 0, stream, image, P + o.w0, P + o.b0, dst, H, W, 1, npix0);
+            dd_stem(image, P + o.w0, P + o.b0, dst, B, H, W, stream);
             IMCUI_CHECK_LAUNCH(h);
         } else if (split) {
             IMCUI_RUN(conv3x3_split_launch(h, cur, reinterpret_cast<const unsigned short*>(P + o.wh[i]), reinterpret_cast<const unsigned short*>(P + o.wl[i]),
@@ -878,7 +812,7 @@ static int dd_encoder(imcui_hip_t* h, int m, const DdLayout& l, const float* P, 
             pp ^= 1;
         } else if (step > 0) {  // (the fourth pool's output is discarded)
             const long n4 = (long)B * (hh / 2) * (ww / 2) * (e.cout[i] / 4);
-            hipLaunchKernelGGL(dd_pool_kernel, dim3(dd_grid(n4)), dim3(256), 0, stream, cur, s.enc[pp], hh / 2, ww / 2, e.cout[i], n4);
+            hipLaunchKernelGGL(pool2x2_kernel<0>, dim3(grid_stride_blocks(n4)), dim3(256), 0, stream, cur, s.enc[pp], hh, ww, hh / 2, ww / 2, e.cout[i], n4);
             IMCUI_CHECK_LAUNCH(h);
             cur = s.enc[pp];
             pp ^= 1;
@@ -937,7 +871,7 @@ static int dd_refiner(imcui_hip_t* h, int m, int st, const DdDims& d, const DdLa
         x = s.ha;
     }
     const long n4 = (long)M * r.hid / 4;
-    hipLaunchKernelGGL(dd_div14_kernel, dim3(dd_grid(n4)), dim3(256), 0, stream, s.ha, n4);
+    hipLaunchKernelGGL(dd_div14_kernel, dim3(grid_stride_blocks(n4)), dim3(256), 0, stream, s.ha, n4);
     IMCUI_CHECK_LAUNCH(h);
     return IMCUI_OK;
 }
@@ -961,7 +895,7 @@ extern "C" int imcui_hip_dedode_forward(imcui_hip_t* h, const float* packed, con
     const float* P = packed;
     const int npix = H * W;
     const long bp = (long)B * npix;
-    hipLaunchKernelGGL(dd_zero_kernel, dim3(1), dim3(64), 0, stream, status ? status : s.status, 1);
+    hipLaunchKernelGGL(zero_i32_kernel<>, dim3(1), dim3(64), 0, stream, status ? status : s.status, 1);
 
     for (int m = 0; m < 2; ++m) {
         IMCUI_RUN(dd_encoder(h, m, l, P, image, B, H, W, s, stream));
@@ -991,9 +925,9 @@ extern "C" int imcui_hip_dedode_forward(imcui_hip_t* h, const float* packed, con
             if (m == 0) {
                 float* plane = s.logits + loff;
                 if (st == 0)
-                    hipLaunchKernelGGL(dd_col_kernel, dim3(dd_grid1(M)), dim3(256), 0, stream, lg, (long)ldo, plane, (long)M);
+                    hipLaunchKernelGGL(dd_col_kernel, dim3(blocks_256(M)), dim3(256), 0, stream, lg, (long)ldo, plane, (long)M);
                 else
-                    hipLaunchKernelGGL(dd_cub2_kernel, dim3(dd_grid1(M)), dim3(256), 0, stream, accp, acc_ld, hh / 2, ww / 2, plane, lg, (long)ldo, (long)M);
+                    hipLaunchKernelGGL(dd_cub2_kernel, dim3(blocks_256(M)), dim3(256), 0, stream, accp, acc_ld, hh / 2, ww / 2, plane, lg, (long)ldo, (long)M);
                 accp = plane;
                 acc_ld = 1;
                 loff += M;
@@ -1003,17 +937,17 @@ extern "C" int imcui_hip_dedode_forward(imcui_hip_t* h, const float* packed, con
             } else if (st < 3) {
                 float* acc = s.accd[st - 1];
                 const long n4 = (long)M * DD_DESC / 4;
-                hipLaunchKernelGGL(dd_up2_kernel, dim3(dd_grid(n4)), dim3(256), 0, stream, accp, acc_ld, hh / 2, ww / 2, DD_DESC, acc, lg, (long)ldo, n4);
+                hipLaunchKernelGGL(dd_up2_kernel, dim3(grid_stride_blocks(n4)), dim3(256), 0, stream, accp, acc_ld, hh / 2, ww / 2, DD_DESC, acc, lg, (long)ldo, n4);
                 accp = acc;
                 acc_ld = DD_DESC;
             } else if (dbg_dense) {
                 const long n4 = (long)M * DD_DESC / 4;
-                hipLaunchKernelGGL(dd_up2_kernel, dim3(dd_grid(n4)), dim3(256), 0, stream, accp, acc_ld, hh / 2, ww / 2, DD_DESC, dbg_dense, dbg_dense, (long)DD_DESC, n4);
+                hipLaunchKernelGGL(dd_up2_kernel, dim3(grid_stride_blocks(n4)), dim3(256), 0, stream, accp, acc_ld, hh / 2, ww / 2, DD_DESC, dbg_dense, dbg_dense, (long)DD_DESC, n4);
             }
             IMCUI_CHECK_LAUNCH(h);
             if (st < 3 && cc_next > 0) {
                 const long n4 = (long)M * 4 * cc_next / 4;
-                hipLaunchKernelGGL(dd_up2_kernel, dim3(dd_grid(n4)), dim3(256), 0, stream, o, (long)ldo, hh, ww, cc_next, s.ctx, (const float*)nullptr, 0L, n4);
+                hipLaunchKernelGGL(dd_up2_kernel, dim3(grid_stride_blocks(n4)), dim3(256), 0, stream, o, (long)ldo, hh, ww, cc_next, s.ctx, (const float*)nullptr, 0L, n4);
                 IMCUI_CHECK_LAUNCH(h);
             }
         }
@@ -1024,9 +958,9 @@ extern "C" int imcui_hip_dedode_forward(imcui_hip_t* h, const float* packed, con
             const float* taps = P + l.taps;
             hipLaunchKernelGGL(dd_smax_part_kernel, dim3(nchunk, B), dim3(256), 0, stream, L, npix, s.part, nchunk);
             hipLaunchKernelGGL(dd_smax_fin_kernel, dim3(B), dim3(256), 0, stream, s.part, nchunk, s.stat);
-            hipLaunchKernelGGL(dd_logp_kernel, dim3(dd_grid1(bp)), dim3(256), 0, stream, L, s.stat, npix, s.logp, s.p, bp);
-            hipLaunchKernelGGL(dd_rowf_kernel, dim3(dd_grid1(bp)), dim3(256), 0, stream, s.p, taps, s.rowf, W, 1, bp);
-            hipLaunchKernelGGL(dd_colf_kernel, dim3(dd_grid1(bp)), dim3(256), 0, stream, s.rowf, taps, s.p, s.score, H, W, bp);
+            hipLaunchKernelGGL(dd_logp_kernel, dim3(blocks_256(bp)), dim3(256), 0, stream, L, s.stat, npix, s.logp, s.p, bp);
+            hipLaunchKernelGGL(dd_rowf_kernel, dim3(blocks_256(bp)), dim3(256), 0, stream, s.p, taps, s.rowf, W, 1, bp);
+            hipLaunchKernelGGL(dd_colf_kernel, dim3(blocks_256(bp)), dim3(256), 0, stream, s.rowf, taps, s.p, s.score, H, W, bp);
             hipLaunchKernelGGL(dd_cut_kernel, dim3(B), dim3(1024), 0, stream, s.score, npix, k, s.klist);
             hipLaunchKernelGGL(dd_emit_kernel, dim3(cdiv(kout, 256), B), dim3(256), 0, stream, s.score, s.klist, npix, W, H, k, kout, keypoints, scores, s.kidx,
                                num_keypoints);
@@ -1061,24 +995,24 @@ extern "C" int imcui_hip_dedode_layer_probe(imcui_hip_t* h, int op, const float*
         std::string why;
         if (!packed || !dd_dims(dims, &d, &why) || model < 0 || model > 1) return imcui_set_err(h, IMCUI_ERR_ARG, "dedode layer probe: layer 0 needs packed weights, dims and a model");
         const DdLayout l = dd_layout(d);
-        hipLaunchKernelGGL(dd_conv0_kernel, dim3(dd_grid1(bp)), dim3(256), 0, stream, in, packed + l.m[model].w0, packed + l.m[model].b0, out, H, W, 1, bp);
+        dd_stem(in, packed + l.m[model].w0, packed + l.m[model].b0, out, B, H, W, stream);
     } else if (op == 1) {
         if (C < 32 || C % 32 || C > 512 || !wts) return imcui_set_err(h, IMCUI_ERR_ARG, "dedode layer probe: C=%d (a multiple of 32 up to 512) and weights", C);
         return dd_dw5(h, in, wts, wts + (size_t)25 * C, out, B, H, W, C, stream);
     } else if (op == 2) {
         if (C < 4 || C % 4 || C > 512) return imcui_set_err(h, IMCUI_ERR_ARG, "dedode layer probe: C=%d (a multiple of 4 up to 512)", C);
         const long n4 = bp * 4 * C / 4;
-        hipLaunchKernelGGL(dd_up2_kernel, dim3(dd_grid(n4)), dim3(256), 0, stream, in, (long)C, H, W, C, out, (const float*)nullptr, 0L, n4);
+        hipLaunchKernelGGL(dd_up2_kernel, dim3(grid_stride_blocks(n4)), dim3(256), 0, stream, in, (long)C, H, W, C, out, (const float*)nullptr, 0L, n4);
     } else if (op == 3) {
-        hipLaunchKernelGGL(dd_cub2_kernel, dim3(dd_grid1(bp * 4)), dim3(256), 0, stream, in, 1L, H, W, out, (const float*)nullptr, 0L, bp * 4);
+        hipLaunchKernelGGL(dd_cub2_kernel, dim3(blocks_256(bp * 4)), dim3(256), 0, stream, in, 1L, H, W, out, (const float*)nullptr, 0L, bp * 4);
     } else if (op == 4) {
         const int npix = H * W, nchunk = cdiv(npix, DD_CHUNK);
         hipLaunchKernelGGL(dd_smax_part_kernel, dim3(nchunk, B), dim3(256), 0, stream, in, npix, out + 2 * B, nchunk);
         hipLaunchKernelGGL(dd_smax_fin_kernel, dim3(B), dim3(256), 0, stream, out + 2 * B, nchunk, out);
     } else if (op == 5) {
         if (!wts) return imcui_set_err(h, IMCUI_ERR_ARG, "dedode layer probe: the filter needs its 51 taps");
-        hipLaunchKernelGGL(dd_rowf_kernel, dim3(dd_grid1(bp)), dim3(256), 0, stream, in, wts, out + bp, W, 0, bp);
-        hipLaunchKernelGGL(dd_colf_kernel, dim3(dd_grid1(bp)), dim3(256), 0, stream, out + bp, wts, (const float*)nullptr, out, H, W, bp);
+        hipLaunchKernelGGL(dd_rowf_kernel, dim3(blocks_256(bp)), dim3(256), 0, stream, in, wts, out + bp, W, 0, bp);
+        hipLaunchKernelGGL(dd_colf_kernel, dim3(blocks_256(bp)), dim3(256), 0, stream, out + bp, wts, (const float*)nullptr, out, H, W, bp);
     } else {
         return imcui_set_err(h, IMCUI_ERR_ARG, "dedode layer probe: op %d", op);
     }
@@ -1126,10 +1060,10 @@ extern "C" int imcui_hip_dedode_select_probe(imcui_hip_t* h, int mode, const flo
     const float* score = map;
     if (mode == 0) {
         // (log p is given: with zero statistics dd_logp_kernel leaves it as it is; its log p output lands in the row buffer)
-        hipLaunchKernelGGL(dd_zero_kernel, dim3(cdiv(2 * B, 256)), dim3(256), 0, stream, reinterpret_cast<int*>(s.stat), 2 * B);
-        hipLaunchKernelGGL(dd_logp_kernel, dim3(dd_grid1(bp)), dim3(256), 0, stream, map, s.stat, npix, s.rowf, s.p, bp);
-        hipLaunchKernelGGL(dd_rowf_kernel, dim3(dd_grid1(bp)), dim3(256), 0, stream, s.p, taps, s.rowf, W, 1, bp);
-        hipLaunchKernelGGL(dd_colf_kernel, dim3(dd_grid1(bp)), dim3(256), 0, stream, s.rowf, taps, s.p, s.score, H, W, bp);
+        hipLaunchKernelGGL(zero_i32_kernel<>, dim3(cdiv(2 * B, 256)), dim3(256), 0, stream, reinterpret_cast<int*>(s.stat), 2 * B);
+        hipLaunchKernelGGL(dd_logp_kernel, dim3(blocks_256(bp)), dim3(256), 0, stream, map, s.stat, npix, s.rowf, s.p, bp);
+        hipLaunchKernelGGL(dd_rowf_kernel, dim3(blocks_256(bp)), dim3(256), 0, stream, s.p, taps, s.rowf, W, 1, bp);
+        hipLaunchKernelGGL(dd_colf_kernel, dim3(blocks_256(bp)), dim3(256), 0, stream, s.rowf, taps, s.p, s.score, H, W, bp);
         score = s.score;
     }
     hipLaunchKernelGGL(dd_cut_kernel, dim3(B), dim3(1024), 0, stream, score, npix, k, s.klist);

@@ -494,8 +494,6 @@ extern "C" int imcui_hip_disk_max_keypoints_bound(int H, int W, int window) {
     return cdiv(H, s) * cdiv(W, s);
 }
 
-static unsigned dk_grid(long n) { return (unsigned)min((n + 255) / 256, (long)65536); }
-
 extern "C" int imcui_hip_disk_forward(imcui_hip_t* h, const float* packed, const float* image, int B, int H, int W, int pad_if_not_divisible,
                                       int window, float threshold, int max_keypoints, int kcap, float* keypoints, float* scores, float* descriptors,
                                       int* num_keypoints, int* status, float* heatmap, void* ws, size_t ws_bytes, void* stream_) {
@@ -524,7 +522,7 @@ extern "C" int imcui_hip_disk_forward(imcui_hip_t* h, const float* packed, const
         hipLaunchKernelGGL(dk_stats_part_kernel, dim3(nch, B), dim3(256), 0, stream, x, C, np, nch, s.part);
         hipLaunchKernelGGL(dk_stats_fin_kernel, dim3(B), dim3(128), 0, stream, s.part, C, np, nch, s.mean, s.rstd);
         const long n4 = (long)B * np * Cp / 4;
-        hipLaunchKernelGGL(dk_norm_kernel, dim3(dk_grid(n4)), dim3(256), 0, stream, x, C, Cp, np, s.mean, s.rstd, P + l.slope[L], s.X, n4);
+        hipLaunchKernelGGL(dk_norm_kernel, dim3(grid_stride_blocks(n4)), dim3(256), 0, stream, x, C, Cp, np, s.mean, s.rstd, P + l.slope[L], s.X, n4);
         IMCUI_CHECK_LAUNCH(h);
         return IMCUI_OK;
     };
@@ -542,16 +540,16 @@ extern "C" int imcui_hip_disk_forward(imcui_hip_t* h, const float* packed, const
     };
     auto pool = [&](const float* src, int lds, int soff, int lev_out, int C) {
         const long n4 = (long)B * px(lev_out) * C / 4;
-        hipLaunchKernelGGL(dk_pool_kernel, dim3(dk_grid(n4)), dim3(256), 0, stream, src, lds, soff, s.pool, Hp >> lev_out, Wp >> lev_out, C, n4);
+        hipLaunchKernelGGL(dk_pool_kernel, dim3(grid_stride_blocks(n4)), dim3(256), 0, stream, src, lds, soff, s.pool, Hp >> lev_out, Wp >> lev_out, C, n4);
     };
     auto up = [&](const float* src, int lev_in, float* dst, int ldd) {
         const long n4 = (long)B * px(lev_in - 1) * 16;
-        hipLaunchKernelGGL(dk_up_kernel, dim3(dk_grid(n4)), dim3(256), 0, stream, src, dst, ldd, Hp >> lev_in, Wp >> lev_in, n4);
+        hipLaunchKernelGGL(dk_up_kernel, dim3(grid_stride_blocks(n4)), dim3(256), 0, stream, src, dst, ldd, Hp >> lev_in, Wp >> lev_in, n4);
     };
     // ---- down path
     {
         const long np = (long)B * px(0);
-        hipLaunchKernelGGL(dk_conv0_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, stream, image, P + l.w0, P + l.b0, s.cat3, H, W, Hp, Wp,
+        hipLaunchKernelGGL(dk_conv0_kernel, dim3(blocks_256(np)), dim3(256), 0, stream, image, P + l.w0, P + l.b0, s.cat3, H, W, Hp, Wp,
                            80, 64, np);
         IMCUI_CHECK_LAUNCH(h);
     }

@@ -5,7 +5,7 @@
 // blur + bilinear halving, LAF / grid normalisation by w - 1), and the stage is parity-unpinned.
 //
 //   pyramid     level l + 1 = pyrdown(level l) while min(h, w) >= 32: dg_blur_kernel (reflect border, 25 taps in row-major order) and
-//               dg_down_kernel (ATen bilinear, align_corners=False, size (h / 2, w / 2)); planar [B, h, w]; only the levels a key-point
+//               resize_planar_kernel (ATen bilinear, align_corners=False, size (h / 2, w / 2)); planar [B, h, w]; only the levels a key-point
 //               can choose are built (index <= max(0, min(H, W) / 32 - 1)); a level index the loop never reaches leaves a ZERO patch, as
 //               kornia's `out = torch.zeros(..)` does
 //   sampling    one workgroup per patch: the LAF (centre xy + 0.5, scale sigma mr_size / 2, angle -ori), normalised by the image and
@@ -33,7 +33,9 @@
 #include <vector>
 
 #include "imcui_hip.h"
+#include "net_kernels.h"
 #include "netpack.h"
+#include "select.h"
 
 #define DG_NL 7
 #define DG_PS 32
@@ -201,32 +203,11 @@ __global__ __launch_bounds__(256) void dg_blur_kernel(const float* __restrict__ 
     dst[p] = acc;
 }
 
-// ATen's upsample_bilinear2d source index (align_corners=False): scale * (dst + 0.5) - 0.5, clamped at 0
-__device__ __forceinline__ void dg_src_index(int o, float scale, int in, int* i0, int* i1, float* l0, float* l1) {
-    const float s = fmaxf(__fsub_rn(__fmul_rn(scale, __fadd_rn((float)o, 0.5f)), 0.5f), 0.0f);
-    const int a = min((int)s, in - 1);
-    *i0 = a;
-    *i1 = a + (a < in - 1 ? 1 : 0);
-    *l1 = __fsub_rn(s, (float)a);
-    *l0 = __fsub_rn(1.0f, *l1);
-}
-// F.interpolate(size=(ho, wo), mode="bilinear", align_corners=False) of planar [B, hi, wi]
-__global__ __launch_bounds__(256) void dg_down_kernel(const float* __restrict__ src, float* __restrict__ dst, int hi, int wi, int ho, int wo, float sh, float sw,
-                                                      long n) {
-    const long p = (long)blockIdx.x * 256 + threadIdx.x;
-    if (p >= n) return;
-    const int x = (int)(p % wo);
-    const long q = p / wo;
-    const int y = (int)(q % ho);
-    const float* pl = src + (q / ho) * (long)hi * wi;
-    int y0, y1, x0, x1;
-    float hy0, hy1, wx0, wx1;
-    dg_src_index(y, sh, hi, &y0, &y1, &hy0, &hy1);
-    dg_src_index(x, sw, wi, &x0, &x1, &wx0, &wx1);
-    const float v00 = pl[(long)y0 * wi + x0], v01 = pl[(long)y0 * wi + x1], v10 = pl[(long)y1 * wi + x0], v11 = pl[(long)y1 * wi + x1];
-    const float top = __fadd_rn(__fmul_rn(wx0, v00), __fmul_rn(wx1, v01)), bot = __fadd_rn(__fmul_rn(wx0, v10), __fmul_rn(wx1, v11));
-    dst[p] = __fadd_rn(__fmul_rn(hy0, top), __fmul_rn(hy1, bot));
-}
+// what the pyramid's down-sampling (F.interpolate(size=(ho, wo), mode="bilinear", align_corners=False) of planar [B, hi, wi]) reads:
+// the blurred level as it is
+struct DgResizeLoad {
+    __device__ float operator()(float v, long) const { return v; }
+};
 
 // live rows of chunk c of image b for the four row granularities of the network (pixels of a 32x32, 16x16, 8x8 map, patches) ->
 // mc [B, nchunk, 4]; status bit 1: a count above kcap
@@ -242,10 +223,6 @@ __global__ __launch_bounds__(256) void dg_count_kernel(const int* __restrict__ c
     mc[4 * i + 1] = live * 256;
     mc[4 * i + 2] = live * 64;
     mc[4 * i + 3] = live;
-}
-__global__ void dg_zero_kernel(int* __restrict__ p, int n) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) p[i] = 0;
 }
 // test entries: the four live-row counts of a chunk that is full (n patches)
 __global__ void dg_full_kernel(int* __restrict__ mc, int n) {
@@ -429,9 +406,9 @@ __global__ __launch_bounds__(256) void dg_finish_kernel(const float* __restrict_
 static int dg_pyrdown(imcui_hip_t* h, const float* src, float* tmp, float* dst, int B, int hh, int ww, hipStream_t stream) {
     const int ho = hh / 2, wo = ww / 2;
     const long n = (long)B * hh * ww, no = (long)B * ho * wo;
-    hipLaunchKernelGGL(dg_blur_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, src, tmp, hh, ww, n);
-    hipLaunchKernelGGL(dg_down_kernel, dim3((unsigned)((no + 255) / 256)), dim3(256), 0, stream, tmp, dst, hh, ww, ho, wo, (float)hh / (float)ho,
-                       (float)ww / (float)wo, no);
+    hipLaunchKernelGGL(dg_blur_kernel, dim3(blocks_256(n)), dim3(256), 0, stream, src, tmp, hh, ww, n);
+    hipLaunchKernelGGL((resize_planar_kernel<bilinear_src_half_pixel, DgResizeLoad>), dim3(blocks_256(no)), dim3(256), 0, stream, tmp, dst, hh, ww, ho, wo,
+                       (float)hh / (float)ho, (float)ww / (float)wo, DgResizeLoad{}, no);
     IMCUI_CHECK_LAUNCH(h);
     return IMCUI_OK;
 }
@@ -546,7 +523,7 @@ extern "C" int imcui_hip_patchdesc_forward(imcui_hip_t* h, const float* packed, 
     const DgLayout l = dg_layout();
     int* st = status ? status : s.status;
     int rc;
-    hipLaunchKernelGGL(dg_zero_kernel, dim3(1), dim3(64), 0, stream, st, 1);
+    hipLaunchKernelGGL(zero_i32_kernel<>, dim3(1), dim3(64), 0, stream, st, 1);
     hipLaunchKernelGGL(dg_count_kernel, dim3(cdiv(B * nchunk, 256)), dim3(256), 0, stream, num_keypoints, B, nchunk, chunk, kcap, s.mc, st);
     IMCUI_CHECK_LAUNCH(h);
     for (int lev = 1; lev < lv.n; ++lev)
@@ -588,7 +565,7 @@ extern "C" int imcui_hip_patchdesc_patch_probe(imcui_hip_t* h, const float* imag
     float* tmp = a.get<float>((size_t)H * W);
     if (!ws || !a.ok) return imcui_set_err(h, IMCUI_ERR_WS, "patchdesc patch probe: workspace too small (%zu < %zu)", ws_bytes, a.off);
     int rc;
-    hipLaunchKernelGGL(dg_zero_kernel, dim3(1), dim3(64), 0, stream, status, 1);
+    hipLaunchKernelGGL(zero_i32_kernel<>, dim3(1), dim3(64), 0, stream, status, 1);
     for (int lev = 1; lev < lv.n; ++lev) IMCUI_RUN(dg_pyrdown(h, lev == 1 ? image : pb + lv.off[lev - 1], tmp, pb + lv.off[lev], 1, lv.h[lev - 1], lv.w[lev - 1], stream));
     hipLaunchKernelGGL(dg_sample_kernel, dim3(n), dim3(256), 0, stream, image, pb, lv, 0, keypoints, scales, oris_deg, (const int*)nullptr, n, mr_size, patches,
                        (float*)nullptr, status);

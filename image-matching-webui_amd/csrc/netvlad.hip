@@ -7,7 +7,7 @@
 //   layer 0     3 -> 64 on the VALU; clamp(x * 255, 0, 255) - mean (the three floats of the packed buffer; RGB, no flip) is applied as
 //               the raw image is read, so the zero padding stays zero in normalised units
 //   conv1_2 .. conv5_3   the patch-staging 3x3 convolutions (conv.hip, both arithmetic modes), ReLU on all but conv5_3 (activation 0);
-//               pools behind conv1_2, 2_2, 3_3, 4_3: fused where the map is even, else the un-pooled launch and nv_pool_kernel (flooring).
+//               pools behind conv1_2, 2_2, 3_3, 4_3: fused where the map is even, else the un-pooled launch and pool2x2_kernel<0> (flooring).
 //               The five 512 -> 512 layers (K = 4608) are summed in two levels, 8 launches over 64 input channels each (nv_conv_grouped):
 //               one chain over K = 4608 missed the float64 bar of conv5_3 in both modes
 //   assign      one wave per pixel: x^ = x / max(|x|, 1e-12), the 64 scores (lane = cluster, score_proj transposed [512][64]), soft-max
@@ -29,6 +29,7 @@
 
 #include "conv.h"
 #include "imcui_hip.h"
+#include "net_kernels.h"
 #include "netpack.h"
 
 #define NV_NL 13
@@ -159,48 +160,13 @@ extern "C" int imcui_hip_netvlad_pack_weights(int whiten, const float* const* t,
 
 namespace {
 
-// layer 0: 3 -> 64, 3x3, pad 1, ReLU; one thread per pixel, the 27 window values in registers, the weights [tap][cin][64] in LDS
-// (wave-uniform reads); taps and channels summed in ascending order.  netvlad.py:126-129: clamp(x * 255, 0, 255) - mean, one rounding each
-__global__ __launch_bounds__(256) void nv_conv0_kernel(const float* __restrict__ img, const float* __restrict__ w, const float* __restrict__ bias,
-                                                       const float* __restrict__ mean, float* __restrict__ out, int h, int wd, long npix) {
-    __shared__ float sw[27 * 64 + 64];
-    for (int i = threadIdx.x; i < 27 * 64 + 64; i += 256) sw[i] = i < 27 * 64 ? w[i] : bias[i - 27 * 64];
-    __syncthreads();
-    const long p = (long)blockIdx.x * 256 + threadIdx.x;
-    if (p >= npix) return;
-    const float m3[3] = {mean[0], mean[1], mean[2]};
-    const int x = (int)(p % wd);
-    const long q = p / wd;
-    const int y = (int)(q % h);
-    const long b = q / h;
-    float win[27];
-#pragma unroll
-    for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-        for (int kx = 0; kx < 3; ++kx) {
-            const int yy = y + ky - 1, xx = x + kx - 1;
-            const bool in = yy >= 0 && yy < h && xx >= 0 && xx < wd;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                float v = 0.0f;
-                if (in) {
-                    v = img[((b * 3 + c) * h + yy) * (long)wd + xx];
-                    v = fminf(fmaxf(v * 255.0f, 0.0f), 255.0f) - m3[c];
-                }
-                win[(ky * 3 + kx) * 3 + c] = v;
-            }
-        }
-    float* o = out + p * 64;
-#pragma unroll 2
-    for (int c0 = 0; c0 < 64; c0 += 4) {
-        float a[4] = {sw[27 * 64 + c0], sw[27 * 64 + c0 + 1], sw[27 * 64 + c0 + 2], sw[27 * 64 + c0 + 3]};
-#pragma unroll
-        for (int t = 0; t < 27; ++t)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) a[j] = fmaf(win[t], sw[t * 64 + c0 + j], a[j]);
-        *reinterpret_cast<float4*>(o + c0) = make_float4(fmaxf(a[0], 0.0f), fmaxf(a[1], 0.0f), fmaxf(a[2], 0.0f), fmaxf(a[3], 0.0f));
+// what layer 0 reads (netvlad.py:126-129): clamp(x * 255, 0, 255) - mean, one rounding each; mean = the three packed channel means
+struct NvStemLoad {
+    const float* mean;
+    __device__ float operator()(const float* __restrict__ img, long b, int c, int h, int w, int yy, int xx) const {
+        return fminf(fmaxf(img[((b * 3 + c) * h + yy) * (long)w + xx] * 255.0f, 0.0f), 255.0f) - mean[c];
     }
-}
+};
 
 // dst [P, NV_KG] = channels [c0, c0 + NV_KG) of src [P, 512]; n4 = float4s of dst
 __global__ __launch_bounds__(256) void nv_slice_kernel(const float* __restrict__ src, float* __restrict__ dst, int c0, long n4) {
@@ -218,26 +184,6 @@ __global__ __launch_bounds__(256) void nv_accum_kernel(float* __restrict__ acc, 
         a = make_float4(a.x + p.x, a.y + p.y, a.z + p.z, a.w + p.w);
         if (relu) a = make_float4(fmaxf(a.x, 0.0f), fmaxf(a.y, 0.0f), fmaxf(a.z, 0.0f), fmaxf(a.w, 0.0f));
         reinterpret_cast<float4*>(acc)[i] = a;
-    }
-}
-
-__device__ __forceinline__ float4 nv_max4(float4 a, float4 b) { return make_float4(fmaxf(a.x, b.x), fmaxf(a.y, b.y), fmaxf(a.z, b.z), fmaxf(a.w, b.w)); }
-
-// nn.MaxPool2d(2, 2) of an NHWC map, flooring: [B, hi, wi, C] -> [B, hi / 2, wi / 2, C] (the last row / column of an odd map is not
-// read); n4 = float4s of the output.  (A copy of D2-Net's: that file's bits do not depend on this one.)
-__global__ __launch_bounds__(256) void nv_pool_kernel(const float* __restrict__ src, float* __restrict__ dst, int hi, int wi, int ho, int wo, int C, long n4) {
-    const int C4 = C >> 2;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
-        const int c = (int)(i % C4) * 4;
-        long t = i / C4;
-        const int x = (int)(t % wo);
-        t /= wo;
-        const int y = (int)(t % ho);
-        const long b = t / ho;
-        const float* s = src + ((b * hi + 2L * y) * wi + 2L * x) * C + c;
-        const float4 v00 = *reinterpret_cast<const float4*>(s), v01 = *reinterpret_cast<const float4*>(s + C),
-                     v10 = *reinterpret_cast<const float4*>(s + (long)wi * C), v11 = *reinterpret_cast<const float4*>(s + (long)wi * C + C);
-        *reinterpret_cast<float4*>(dst + i * 4) = nv_max4(nv_max4(v00, v01), nv_max4(v10, v11));
     }
 }
 
@@ -486,9 +432,19 @@ __global__ __launch_bounds__(256) void nv_topk_kernel(const float* __restrict__ 
 
 }  // namespace
 
-static unsigned nv_grid(long n) { return (unsigned)std::min((n + 255) / 256, (long)65536); }
-
 // ------------------------------------------------------------------ launch helpers
+// layer 0 on the raw planar image [B, 3, H, W] -> out [B, H, W, 64]
+static void nv_stem(const NvLayout& l, const float* P, const float* img, int B, int H, int W, float* out, hipStream_t stream) {
+    const long npix = (long)B * H * W;
+    hipLaunchKernelGGL((stem3x3_kernel<64, NvStemLoad>), dim3(blocks_256(npix)), dim3(256), 0, stream, img, P + l.w0, P + l.b0, out, H, W, NvStemLoad{P + l.mean},
+                       npix);
+}
+// the flooring 2x2 max-pool, [B, hi, wi, C] -> [B, hi / 2, wi / 2, C]
+static void nv_pool(const float* src, float* dst, int B, int hi, int wi, int C, hipStream_t stream) {
+    const long n4 = (long)B * (hi / 2) * (wi / 2) * (C / 4);
+    hipLaunchKernelGGL(pool2x2_kernel<0>, dim3(grid_stride_blocks(n4)), dim3(256), 0, stream, src, dst, hi, wi, hi / 2, wi / 2, C, n4);
+}
+
 // A 512 -> 512 layer (K = 4608) as NV_NG partial convolutions over NV_KG input channels each, summed in group order: the patch-staging
 // kernels sum K in one chain per output, and at K = 4608 that chain alone is 5 .. 8 x the float32 error of a blocked sum (conv5_3 on a
 // 3 x 4 map against float64: one launch 1.07e-06 split / 1.80e-06 exact, 16 groups of 32 3.1e-07 / 2.8e-07, 8 groups of 64 3.6e-07 /
@@ -513,11 +469,11 @@ static int nv_conv_grouped(imcui_hip_t* h, const float* P, const NvLayout& l, in
                                            last ? act : 0, 0, stream, prev, NV_D));
         } else {
             const long s4 = (long)pix * (NV_KG / 4), o4 = (long)pix * (NV_D / 4);
-            hipLaunchKernelGGL(nv_slice_kernel, dim3((unsigned)std::min((s4 + 255) / 256, 65536L)), dim3(256), 0, stream, in, tmp, g * NV_KG, s4);
+            hipLaunchKernelGGL(nv_slice_kernel, dim3(grid_stride_blocks(s4)), dim3(256), 0, stream, in, tmp, g * NV_KG, s4);
             IMCUI_CHECK_LAUNCH(h);
             IMCUI_RUN(conv3x3_launch(h, tmp, P + l.w[i] + g * ng, bias, g == 0 ? out : other, B, hh, ww, NV_KG, L.cout, 0, 0, stream));
             if (g > 0) {
-                hipLaunchKernelGGL(nv_accum_kernel, dim3((unsigned)std::min((o4 + 255) / 256, 65536L)), dim3(256), 0, stream, out, other, last ? act : 0, o4);
+                hipLaunchKernelGGL(nv_accum_kernel, dim3(grid_stride_blocks(o4)), dim3(256), 0, stream, out, other, last ? act : 0, o4);
                 IMCUI_CHECK_LAUNCH(h);
             }
         }
@@ -612,8 +568,7 @@ extern "C" int imcui_hip_netvlad_forward(imcui_hip_t* h, const float* packed, co
     const bool split = h->precision == 1;
     const float* P = packed;
     int rc;
-    const long npix0 = (long)B * H * W;
-    hipLaunchKernelGGL(nv_conv0_kernel, dim3((unsigned)((npix0 + 255) / 256)), dim3(256), 0, stream, image, P + l.w0, P + l.b0, P + l.mean, s.fa, H, W, npix0);
+    nv_stem(l, P, image, B, H, W, s.fa, stream);
     IMCUI_CHECK_LAUNCH(h);
     float *cur = s.fa, *oth = s.fb;
     int hh = H, ww = W;
@@ -631,8 +586,7 @@ extern "C" int imcui_hip_netvlad_forward(imcui_hip_t* h, const float* packed, co
         if (L.pool) {
             const int ho = hh / 2, wo = ww / 2;
             if (!fused) {  // an odd map: nn.MaxPool2d floors (also behind conv4_3, which is summed in groups and has no fused pool)
-                const long n4 = (long)B * ho * wo * (L.cout / 4);
-                hipLaunchKernelGGL(nv_pool_kernel, dim3(nv_grid(n4)), dim3(256), 0, stream, cur, oth, hh, ww, ho, wo, L.cout, n4);
+                nv_pool(cur, oth, B, hh, ww, L.cout, stream);
                 IMCUI_CHECK_LAUNCH(h);
                 std::swap(cur, oth);
             }
@@ -663,14 +617,10 @@ extern "C" int imcui_hip_netvlad_layer_probe(imcui_hip_t* h, int op, const float
     const NvLayout l = nv_layout(0);
     if (op == 0) {
         if (!packed) return imcui_set_err(h, IMCUI_ERR_ARG, "netvlad layer probe: layer 0 needs the packed weights");
-        const long npix = (long)B * H * W;
-        hipLaunchKernelGGL(nv_conv0_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, stream, in, packed + l.w0, packed + l.b0, packed + l.mean, out, H, W,
-                           npix);
+        nv_stem(l, packed, in, B, H, W, out, stream);
     } else if (op == 1) {
-        const int ho = H / 2, wo = W / 2;
-        if (C < 4 || C % 4 || C > 512 || ho < 1 || wo < 1) return imcui_set_err(h, IMCUI_ERR_ARG, "netvlad layer probe: C=%d (a multiple of 4 up to 512), %dx%d", C, H, W);
-        const long n4 = (long)B * ho * wo * (C / 4);
-        hipLaunchKernelGGL(nv_pool_kernel, dim3(nv_grid(n4)), dim3(256), 0, stream, in, out, H, W, ho, wo, C, n4);
+        if (C < 4 || C % 4 || C > 512 || H < 2 || W < 2) return imcui_set_err(h, IMCUI_ERR_ARG, "netvlad layer probe: C=%d (a multiple of 4 up to 512), %dx%d", C, H, W);
+        nv_pool(in, out, B, H, W, C, stream);
     } else if (op == 2) {
         if (!packed || C != NV_D) return imcui_set_err(h, IMCUI_ERR_ARG, "netvlad layer probe: the NetVLAD layer needs the packed weights and C=512, got %d", C);
         const NvWs s = nv_carve(ws, ws_bytes, B, 0, (size_t)H * W, 0);

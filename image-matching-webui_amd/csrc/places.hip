@@ -177,8 +177,6 @@ extern "C" int imcui_hip_places_pack_weights(int backbone, int fc_output_dim, co
 
 namespace {
 
-__device__ __forceinline__ float4 pl_max4(float4 a, float4 b) { return make_float4(fmaxf(a.x, b.x), fmaxf(a.y, b.y), fmaxf(a.z, b.z), fmaxf(a.w, b.w)); }
-
 // cosplace.py:41 norm_rgb + backbone.0 (7x7, stride 2, pad 3) + bn1 + ReLU + MaxPool2d(3, 2, 1).  Workgroup (tile x, tile y, image): the
 // PL_TPH x PL_TPW pooled pixels from (py0, px0) need the conv positions from (2 py0 - 1, 2 px0 - 1), PL_CH x PL_CW of them, and those the
 // image window from (4 py0 - 5, 4 px0 - 5), PL_IH x PL_IW pixels: staged normalised, zeros outside the image.  Wave w owns output channels
@@ -245,7 +243,7 @@ __global__ __launch_bounds__(256) void pl_stem_kernel(const float* __restrict__ 
 #pragma unroll
             for (int dx = 0; dx < 3; ++dx) {
                 const int ly = 2 * ty + dy, lx = 2 * tx + dx, cy = cy0 + ly, cx = cx0 + lx;
-                if (cy >= 0 && cy < Hc && cx >= 0 && cx < Wc) m = pl_max4(m, *reinterpret_cast<const float4*>(sconv + (ly * PL_CW + lx) * PL_CS + c4 * 4));
+                if (cy >= 0 && cy < Hc && cx >= 0 && cx < Wc) m = max4(m, *reinterpret_cast<const float4*>(sconv + (ly * PL_CW + lx) * PL_CS + c4 * 4));
             }
         *reinterpret_cast<float4*>(out + (((long)b * Hp + py) * Wp + px) * 64 + c4 * 4) = m;
     }

@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "imcui_hip.h"
+#include "net_kernels.h"
 #include "netpack.h"
 #include "select.h"
 
@@ -149,17 +150,9 @@ __device__ __forceinline__ float r2_norm(float x, int c) {
     return __fdiv_rn(__fsub_rn(x, mean), sd);
 }
 
-// ATen's upsample_bilinear2d source index (align_corners=False): scale * (dst + 0.5) - 0.5, clamped at 0 (as xfeat.hip restates it)
-__device__ __forceinline__ void r2_src_index(int o, float scale, int in, int* i0, int* i1, float* l0, float* l1) {
-    const float s = fmaxf(__fsub_rn(__fmul_rn(scale, __fadd_rn((float)o, 0.5f)), 0.5f), 0.0f);
-    const int a = min((int)s, in - 1);
-    *i0 = a;
-    *i1 = a + (a < in - 1 ? 1 : 0);
-    *l1 = __fsub_rn(s, (float)a);
-    *l0 = __fsub_rn(1.0f, *l1);
-}
-
-// planar [B, 3, hi, wi] -> [B, 3, ho, wo]; norm: the source is the raw image (level 0) and is normalised as it is read
+// planar [B, 3, hi, wi] -> [B, 3, ho, wo]; norm: the source is the raw image (level 0) and is normalised as it is read.  (Not an
+// instance of net_kernels.h's resize_planar_kernel: this file is compiled with floating-point contraction on, the compiler fuses one
+// product of each row mix into the sum, and WHICH one it picked changed with the shape of the code; the bits of the levels follow.)
 __global__ __launch_bounds__(256) void r2_resize_kernel(const float* __restrict__ src, float* __restrict__ dst, int hi, int wi, int ho, int wo, float sh,
                                                         float sw, int norm, long n) {
     const long p = (long)blockIdx.x * 256 + threadIdx.x;
@@ -171,8 +164,8 @@ __global__ __launch_bounds__(256) void r2_resize_kernel(const float* __restrict_
     const int c = (int)(bc % 3);
     int y0, y1, x0, x1;
     float hy0, hy1, wx0, wx1;
-    r2_src_index(y, sh, hi, &y0, &y1, &hy0, &hy1);
-    r2_src_index(x, sw, wi, &x0, &x1, &wx0, &wx1);
+    bilinear_src_half_pixel(y, sh, hi, &y0, &y1, &hy0, &hy1);
+    bilinear_src_half_pixel(x, sw, wi, &x0, &x1, &wx0, &wx1);
     const float* pl = src + bc * (long)hi * wi;
     float v00 = pl[(long)y0 * wi + x0], v01 = pl[(long)y0 * wi + x1], v10 = pl[(long)y1 * wi + x0], v11 = pl[(long)y1 * wi + x1];
     if (norm) {
@@ -185,47 +178,14 @@ __global__ __launch_bounds__(256) void r2_resize_kernel(const float* __restrict_
     dst[p] = __fadd_rn(__fmul_rn(hy0, top), __fmul_rn(hy1, bot));
 }
 
-// layer 0: 3 -> 32, 3x3, pad 1, folded BatchNorm + ReLU; one thread per pixel, the 27 window values in registers, the weights
-// [tap][cin][32] in LDS (wave-uniform reads); taps and channels summed in ascending order
-__global__ __launch_bounds__(256) void r2_conv0_kernel(const float* __restrict__ img, const float* __restrict__ w, const float* __restrict__ bias,
-                                                       float* __restrict__ out, int h, int wd, int norm, long npix) {
-    __shared__ float sw[27 * 32 + 32];
-    for (int i = threadIdx.x; i < 27 * 32 + 32; i += 256) sw[i] = i < 27 * 32 ? w[i] : bias[i - 27 * 32];
-    __syncthreads();
-    const long p = (long)blockIdx.x * 256 + threadIdx.x;
-    if (p >= npix) return;
-    const int x = (int)(p % wd);
-    const long q = p / wd;
-    const int y = (int)(q % h);
-    const long b = q / h;
-    float win[27];
-#pragma unroll
-    for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-        for (int kx = 0; kx < 3; ++kx) {
-            const int yy = y + ky - 1, xx = x + kx - 1;
-            const bool in = yy >= 0 && yy < h && xx >= 0 && xx < wd;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                float v = 0.0f;
-                if (in) {
-                    v = img[((b * 3 + c) * h + yy) * (long)wd + xx];
-                    if (norm) v = r2_norm(v, c);
-                }
-                win[(ky * 3 + kx) * 3 + c] = v;
-            }
-        }
-    float* o = out + p * 32;
-#pragma unroll
-    for (int c0 = 0; c0 < 32; c0 += 4) {
-        float a[4] = {sw[27 * 32 + c0], sw[27 * 32 + c0 + 1], sw[27 * 32 + c0 + 2], sw[27 * 32 + c0 + 3]};
-#pragma unroll
-        for (int t = 0; t < 27; ++t)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) a[j] = fmaf(win[t], sw[t * 32 + c0 + j], a[j]);
-        *reinterpret_cast<float4*>(o + c0) = make_float4(fmaxf(a[0], 0.0f), fmaxf(a[1], 0.0f), fmaxf(a[2], 0.0f), fmaxf(a[3], 0.0f));
+// what layer 0 reads; norm: the image is the raw one (level 0)
+struct R2StemLoad {
+    int norm;
+    __device__ float operator()(const float* __restrict__ img, long b, int c, int h, int w, int yy, int xx) const {
+        const float v = img[((b * 3 + c) * h + yy) * (long)w + xx];
+        return norm ? r2_norm(v, c) : v;
     }
-}
+};
 
 // head: u = W (x * x) + b for the three rows (clf 0, clf 1, sal); reliability = softmax(clf)[1], repeatability = softplus(sal) / (1 +
 // softplus(sal)).  32 lanes per pixel, 4 channels per lane, a fixed xor tree over the 32 lanes
@@ -310,47 +270,6 @@ __global__ __launch_bounds__(256) void r2_park_kernel(const float* __restrict__ 
         *reinterpret_cast<float2*>(cvec + ((long)b * kcap + s) * R2_DIM + 2 * lane) = *reinterpret_cast<const float2*>(src + 2 * lane);
     }
 }
-__global__ void r2_advance_kernel(int* __restrict__ base, const int* __restrict__ nlev, int B) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b < B) base[b] += nlev[b];  // (the true count: an overflow stays visible)
-}
-__global__ void r2_zero_kernel(int* __restrict__ p, int n) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) p[i] = 0;
-}
-
-// (score, candidate index) as one ordered key: torch.argsort(stable=True) puts equal scores in index order
-__device__ __forceinline__ unsigned long long r2_key(float s, int i) { return ((unsigned long long)order_key(s) << 32) | (unsigned)i; }
-
-// The cut.  One workgroup per image: more than `limit` candidates -> the `limit` largest keys stay; the kept slots leave in candidate
-// order (kslot), the emit kernel ranks them.
-__global__ __launch_bounds__(1024) void r2_cut_kernel(const float* __restrict__ cscore, const int* __restrict__ ntotal, int kcap, int limit_,
-                                                      int* __restrict__ kslot, int* __restrict__ nkept, int* __restrict__ status) {
-    __shared__ int wcnt[16];
-    const int b = blockIdx.x, tid = threadIdx.x;
-    const float* cs = cscore + (long)b * kcap;
-    int* ks = kslot + (long)b * kcap;
-    const int n = min(ntotal[b], kcap);
-    if (tid == 0 && ntotal[b] > kcap) atomicOr(status, 2);  // candidate capacity too small
-    bool filter = false;
-    unsigned long long kth = 0;
-    int limit = n;
-    if (limit_ > 0 && n > limit_) {
-        filter = true;
-        limit = limit_;
-        kth = radix_select_kth<1024, unsigned long long>([&](int i) { return r2_key(cs[i], i); }, n, limit_);
-    }
-    int run = 0;
-    for (int base = 0; base < n; base += 1024) {
-        const int i = base + tid;
-        const bool keep = i < n && (!filter || r2_key(cs[i], i) >= kth);
-        int tot;
-        const int pos = run + block_ordered_rank<16>(keep, wcnt, &tot);
-        if (keep && pos < limit) ks[pos] = i;
-        run += tot;
-    }
-    if (tid == 0) nkept[b] = min(run, limit);
-}
 
 // F.normalize(v, dim=channel) of one 128-vector held two floats per lane
 __device__ __forceinline__ float2 r2_normalize(float2 v) {
@@ -364,7 +283,6 @@ __global__ __launch_bounds__(256) void r2_emit_kernel(const float* __restrict__ 
                                                       const float* __restrict__ cvec, const int* __restrict__ kslot, const int* __restrict__ nkept,
                                                       int kcap, int kout, R2Levels lv, int H, int W, float* __restrict__ kpts,
                                                       float* __restrict__ scores, float* __restrict__ desc, int* __restrict__ nkpts) {
-    __shared__ float tile[256];
     __shared__ int rank_s[256];
     const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const float* cs = cscore + (long)b * kcap;
@@ -380,20 +298,7 @@ __global__ __launch_bounds__(256) void r2_emit_kernel(const float* __restrict__ 
     for (int i = i0 + wv; i < min(i0 + 256, kout); i += 4)
         if (i >= n) *reinterpret_cast<float2*>(de + (long)i * R2_DIM + 2 * lane) = make_float2(0.0f, 0.0f);
     if (i0 >= n) return;  // (uniform)
-    const int i = i0 + tid;
-    const float mine = i < n ? cs[ks[i]] : 0.0f;
-    int rank = 0;
-    for (int base = 0; base < n; base += 256) {
-        __syncthreads();
-        tile[tid] = base + tid < n ? cs[ks[base + tid]] : INFINITY;
-        __syncthreads();
-        const int m = min(256, n - base);
-        for (int j = 0; j < m; ++j) {
-            const float o = tile[j];
-            rank += (o < mine || (o == mine && base + j < i)) ? 1 : 0;
-        }
-    }
-    rank_s[tid] = rank;
+    rank_s[tid] = kept_rank_ascending(cs, ks, n, i0 + tid);
     __syncthreads();
     for (int j = wv; j < min(256, n - i0); j += 4) {
         const int slot = ks[i0 + j], r = rank_s[j];
@@ -484,7 +389,7 @@ static int r2_net(imcui_hip_t* h, const R2Layout& l, const float* P, const float
     const long npix = (long)B * nh * nw;
     const bool split = h->precision == 1;
     int rc;
-    hipLaunchKernelGGL(r2_conv0_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, stream, img, P + l.w0, P + l.b0, s.fa, nh, nw, norm, npix);
+    hipLaunchKernelGGL((stem3x3_kernel<32, R2StemLoad>), dim3(blocks_256(npix)), dim3(256), 0, stream, img, P + l.w0, P + l.b0, s.fa, nh, nw, R2StemLoad{norm}, npix);
     IMCUI_CHECK_LAUNCH(h);
     const float* in = s.fa;
     float* out = s.fb;
@@ -528,8 +433,8 @@ extern "C" int imcui_hip_r2d2_forward(imcui_hip_t* h, const float* packed, const
     R2Ws s = r2_carve(ws, ws_bytes, B, npix_max, kcap);
     if (!ws || !s.ok) return imcui_set_err(h, IMCUI_ERR_WS, "r2d2: workspace too small (%zu < %zu)", ws_bytes, s.total);
     int* st = status ? status : s.status;
-    hipLaunchKernelGGL(r2_zero_kernel, dim3(cdiv(B, 256)), dim3(256), 0, stream, s.base, B);
-    hipLaunchKernelGGL(r2_zero_kernel, dim3(1), dim3(64), 0, stream, st, 1);
+    hipLaunchKernelGGL(zero_i32_kernel<>, dim3(cdiv(B, 256)), dim3(256), 0, stream, s.base, B);
+    hipLaunchKernelGGL(zero_i32_kernel<>, dim3(1), dim3(64), 0, stream, st, 1);
     R2Levels lv;
     lv.n = nlev;
     for (int i = 0; i < R2_MAXLEV; ++i) lv.nh[i] = lv.nw[i] = 1;
@@ -544,7 +449,7 @@ extern "C" int imcui_hip_r2d2_forward(imcui_hip_t* h, const float* packed, const
             float* dst = s.lev[lev & 1];
             const long n = (long)B * 3 * npix;
             // ATen: scale = in / out in float32
-            hipLaunchKernelGGL(r2_resize_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, cur, dst, nh[lev - 1], nw[lev - 1], ch, cw,
+            hipLaunchKernelGGL(r2_resize_kernel, dim3(blocks_256(n)), dim3(256), 0, stream, cur, dst, nh[lev - 1], nw[lev - 1], ch, cw,
                                (float)nh[lev - 1] / (float)ch, (float)nw[lev - 1] / (float)cw, lev == 1 ? 1 : 0, n);
             IMCUI_CHECK_LAUNCH(h);
             cur = dst;
@@ -568,11 +473,11 @@ extern "C" int imcui_hip_r2d2_forward(imcui_hip_t* h, const float* packed, const
         hipLaunchKernelGGL((cand_compact_kernel<R2Pred, R2Emit>), dim3(nchunk, B), dim3(256), 0, stream, s.rep, npix, pred, s.blkoff, nchunk, npix, emit);
         hipLaunchKernelGGL(r2_park_kernel, dim3(std::min(cdiv(std::min(npix, kcap), 4), 4096), B), dim3(256), 0, stream, s.fa, s.base, s.nlev, s.cidx, kcap, npix,
                            s.cvec);
-        hipLaunchKernelGGL(r2_advance_kernel, dim3(cdiv(B, 256)), dim3(256), 0, stream, s.base, s.nlev, B);
+        hipLaunchKernelGGL(advance_base_kernel<>,dim3(cdiv(B, 256)), dim3(256), 0, stream, s.base, s.nlev, B);
         IMCUI_CHECK_LAUNCH(h);
     }
     // ---- cut + emit
-    hipLaunchKernelGGL(r2_cut_kernel, dim3(B), dim3(1024), 0, stream, s.cscore, s.base, kcap, max_keypoints, s.kslot, s.nkept, st);
+    hipLaunchKernelGGL(cand_cut_kernel<>,dim3(B), dim3(1024), 0, stream, s.cscore, s.base, kcap, max_keypoints, s.kslot, s.nkept, st);
     hipLaunchKernelGGL(r2_emit_kernel, dim3(cdiv(kout, 256), B), dim3(256), 0, stream, s.cscore, s.clev, s.cidx, s.cvec, s.kslot, s.nkept, kcap, kout, lv, H, W,
                        keypoints, scores, descriptors, num_keypoints);
     IMCUI_CHECK_LAUNCH(h);

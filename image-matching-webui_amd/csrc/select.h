@@ -1,7 +1,9 @@
 // List-building blocks shared by the extractors and matchers: ordered candidate compaction over a score map, an exclusive scan, the
-// order-preserving float key, the radix select of the k-th largest key and the rank of a flagged thread inside its workgroup.
-// Device code only.  The RULES stay with their owners (sp_topk_kernel, dk_select_kernel, ak_select_kernel, ...): which candidates a
-// network keeps, in which order and how ties fall differs per network, and none of that is decided here.
+// order-preserving float key, the radix select of the k-th largest key, the rank of a flagged thread inside its workgroup, the loop
+// that keeps the keys >= the k-th in list order, and the candidate list of the multi-scale extractors (zero, advance, cut, rank).
+// Device code only.  The RULES stay with their owners (sp_topk_kernel, dk_select_kernel, ak_select_kernel, xf_rank_kernel, al_cut_kernel,
+// dd_cut_kernel, r2_emit_kernel, d2_emit_kernel, ...): which candidates a network keeps, in which order and how ties fall differs per
+// network, and none of that is decided here; R2D2 and D2-Net share one rule (a stable argsort of (score, list index)) and hence one cut.
 #pragma once
 #include "common.h"
 
@@ -205,6 +207,84 @@ __device__ __forceinline__ Key radix_select_kth(Load load, int n, int k, int* n_
     }
     if (n_equal) *n_equal = s_k;
     return s_prefix;
+}
+
+// ------------------------------------------------------------------ keeping the k largest of a list, in list order
+// Entries i of 0 .. n - 1 with key_at(i) >= kth (every entry when !filter) go to out[0 .. limit) in list order.  Returns how many
+// qualified (it may exceed limit).  Every thread of the workgroup of 1024 calls it.
+template <class KeyAt>
+__device__ __forceinline__ int keep_kth_in_order(KeyAt key_at, int n, bool filter, unsigned long long kth, int limit, int* __restrict__ out) {
+    __shared__ int wcnt[16];
+    int run = 0;
+    for (int base = 0; base < n; base += 1024) {
+        const int i = base + threadIdx.x;
+        const bool keep = i < n && (!filter || key_at(i) >= kth);
+        int tot;
+        const int pos = run + block_ordered_rank<16>(keep, wcnt, &tot);
+        if (keep && pos < limit) out[pos] = i;
+        run += tot;
+    }
+    return run;
+}
+
+// ------------------------------------------------------------------ the candidate list of a multi-scale extractor (R2D2, D2-Net)
+// Every level appends its candidates to the image's list at base[b]; after the last level the list is cut and the emit kernel of the
+// network ranks what is left.  (The three kernels are templates -- launched as name<> -- so that only the translation units that launch
+// them carry a copy.)
+template <class = void>
+__global__ void zero_i32_kernel(int* __restrict__ p, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) p[i] = 0;
+}
+template <class = void>
+__global__ void advance_base_kernel(int* __restrict__ base, const int* __restrict__ nlev, int B) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b < B) base[b] += nlev[b];  // (the true count: an overflow stays visible)
+}
+
+// (score, candidate index) as one ordered key: a stable argsort puts equal scores in list order
+__device__ __forceinline__ unsigned long long score_index_key(float s, int i) { return ((unsigned long long)order_key(s) << 32) | (unsigned)i; }
+
+// The cut.  One workgroup of 1024 per image: more than `limit` candidates -> the `limit` largest keys stay; the kept slots leave in
+// candidate order (kslot), the emit kernel ranks them.  status bit 1: more candidates than the list holds.
+template <class = void>
+__global__ __launch_bounds__(1024) void cand_cut_kernel(const float* __restrict__ cscore, const int* __restrict__ ntotal, int kcap, int limit_,
+                                                        int* __restrict__ kslot, int* __restrict__ nkept, int* __restrict__ status) {
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const float* cs = cscore + (long)b * kcap;
+    const int n = min(ntotal[b], kcap);
+    if (tid == 0 && ntotal[b] > kcap) atomicOr(status, 2);  // candidate capacity too small
+    const auto key_at = [&](int i) { return score_index_key(cs[i], i); };
+    bool filter = false;
+    unsigned long long kth = 0;
+    int limit = n;
+    if (limit_ > 0 && n > limit_) {
+        filter = true;
+        limit = limit_;
+        kth = radix_select_kth<1024, unsigned long long>(key_at, n, limit_);
+    }
+    const int run = keep_kth_in_order(key_at, n, filter, kth, limit, kslot + (long)b * kcap);
+    if (tid == 0) nkept[b] = min(run, limit);
+}
+
+// The rank of kept candidate i (this thread's; any value when i >= n) among the n kept ones ks[0 .. n) in ascending (score, position)
+// order; the kept list is in slot order, so equal scores keep it.  Every thread of the workgroup of 256 calls it.
+__device__ __forceinline__ int kept_rank_ascending(const float* __restrict__ cs, const int* __restrict__ ks, int n, int i) {
+    __shared__ float tile[256];
+    const int tid = threadIdx.x;
+    const float mine = i < n ? cs[ks[i]] : 0.0f;
+    int rank = 0;
+    for (int base = 0; base < n; base += 256) {
+        __syncthreads();
+        tile[tid] = base + tid < n ? cs[ks[base + tid]] : INFINITY;
+        __syncthreads();
+        const int m = min(256, n - base);
+        for (int j = 0; j < m; ++j) {
+            const float o = tile[j];
+            rank += (o < mine || (o == mine && base + j < i)) ? 1 : 0;
+        }
+    }
+    return rank;
 }
 
 }  // namespace

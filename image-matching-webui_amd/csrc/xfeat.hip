@@ -26,6 +26,7 @@
 
 #include "gemm.h"
 #include "imcui_hip.h"
+#include "net_kernels.h"
 #include "netpack.h"
 #include "select.h"
 
@@ -150,16 +151,6 @@ extern "C" int imcui_hip_xfeat_pack_weights(const float* const* t, float* packed
 }
 
 // ------------------------------------------------------------------ input stage
-// ATen's upsample_bilinear2d source index (align_corners=False): scale * (dst + 0.5) - 0.5, clamped at 0
-__device__ __forceinline__ void xf_src_index(int o, float scale, int in, int* i0, int* i1, float* l0, float* l1) {
-    const float s = fmaxf(__fsub_rn(__fmul_rn(scale, __fadd_rn((float)o, 0.5f)), 0.5f), 0.0f);
-    const int a = min((int)s, in - 1);
-    *i0 = a;
-    *i1 = a + (a < in - 1 ? 1 : 0);
-    *l1 = __fsub_rn(s, (float)a);
-    *l0 = __fsub_rn(1.0f, *l1);
-}
-
 // image [B, C, H, W] (C = 1 or 3) -> gray [B, Hr, Wr]: every channel resized (skipped when the sizes are equal: the interpolation is
 // then the identity), then the channel mean, summed in double so that three equal channels give the channel itself
 __global__ __launch_bounds__(256) void xf_gray_kernel(const float* __restrict__ img, float* __restrict__ gray, int C, int H, int W, int Hr, int Wr,
@@ -176,8 +167,8 @@ __global__ __launch_bounds__(256) void xf_gray_kernel(const float* __restrict__ 
     } else {
         int y0, y1, x0, x1;
         float hy0, hy1, wx0, wx1;
-        xf_src_index(y, sh, H, &y0, &y1, &hy0, &hy1);
-        xf_src_index(x, sw, W, &x0, &x1, &wx0, &wx1);
+        bilinear_src_half_pixel(y, sh, H, &y0, &y1, &hy0, &hy1);
+        bilinear_src_half_pixel(x, sw, W, &x0, &x1, &wx0, &wx1);
         for (int c = 0; c < C; ++c) {
             const float* pl = img + (b * C + c) * (long)H * W;
             const float v00 = pl[(long)y0 * W + x0], v01 = pl[(long)y0 * W + x1], v10 = pl[(long)y1 * W + x0], v11 = pl[(long)y1 * W + x1];
@@ -337,8 +328,8 @@ __global__ __launch_bounds__(256) void xf_unfold_kernel(const float* __restrict_
 __device__ __forceinline__ float4 xf_bilinear4(const float* __restrict__ m, int h, int w, float scale, int oy, int ox, int c) {
     int y0, y1, x0, x1;
     float hy0, hy1, wx0, wx1;
-    xf_src_index(oy, scale, h, &y0, &y1, &hy0, &hy1);
-    xf_src_index(ox, scale, w, &x0, &x1, &wx0, &wx1);
+    bilinear_src_half_pixel(oy, scale, h, &y0, &y1, &hy0, &hy1);
+    bilinear_src_half_pixel(ox, scale, w, &x0, &x1, &wx0, &wx1);
     const float4 v00 = *reinterpret_cast<const float4*>(m + ((long)y0 * w + x0) * 64 + c), v01 = *reinterpret_cast<const float4*>(m + ((long)y0 * w + x1) * 64 + c);
     const float4 v10 = *reinterpret_cast<const float4*>(m + ((long)y1 * w + x0) * 64 + c), v11 = *reinterpret_cast<const float4*>(m + ((long)y1 * w + x1) * 64 + c);
     float4 o;
@@ -654,8 +645,6 @@ extern "C" int imcui_hip_xfeat_max_keypoints_bound(int H, int W) {
     return cdiv(H / 32 * 32, 3) * cdiv(W / 32 * 32, 3);
 }
 
-static unsigned xf_grid(long n) { return (unsigned)((n + 255) / 256); }
-
 extern "C" int imcui_hip_xfeat_forward(imcui_hip_t* h, const float* packed, const float* image, int B, int C, int H, int W, float threshold, int top_k,
                                        int kcap, float* keypoints, float* scores, float* descriptors, int* num_keypoints, int* status, float* kpt_heat,
                                        float* reliability, float* feats_norm, void* ws, size_t ws_bytes, void* stream_) {
@@ -694,7 +683,7 @@ extern "C" int imcui_hip_xfeat_forward(imcui_hip_t* h, const float* packed, cons
     };
     // ---- input stage
     const long np0 = (long)B * px(0);
-    hipLaunchKernelGGL(xf_gray_kernel, dim3(xf_grid(np0)), dim3(256), 0, stream, image, s.gray, C, H, W, Hr, Wr, (float)H / (float)Hr, (float)W / (float)Wr,
+    hipLaunchKernelGGL(xf_gray_kernel, dim3(blocks_256(np0)), dim3(256), 0, stream, image, s.gray, C, H, W, Hr, Wr, (float)H / (float)Hr, (float)W / (float)Wr,
                        np0);
     const int nch = cdiv(Hr * Wr, XF_STAT_CHUNK);
     hipLaunchKernelGGL(xf_stats_part_kernel, dim3(nch, B), dim3(256), 0, stream, s.gray, px(0), nch, s.part);
@@ -702,13 +691,13 @@ extern "C" int imcui_hip_xfeat_forward(imcui_hip_t* h, const float* packed, cons
     IMCUI_CHECK_LAUNCH(h);
     // ---- block1 + skip1 (VALU)
     const float* nul = nullptr;
-    hipLaunchKernelGGL((xf_stem_kernel<1, 4, 4, 1, true, false>), dim3(xf_grid(np0)), dim3(256), 0, stream, s.gray, P + l.g[0].w, P + l.g[0].b, s.s1, Hr, Wr, Hr,
+    hipLaunchKernelGGL((xf_stem_kernel<1, 4, 4, 1, true, false>), dim3(blocks_256(np0)), dim3(256), 0, stream, s.gray, P + l.g[0].w, P + l.g[0].b, s.s1, Hr, Wr, Hr,
                        Wr, np0, s.norm, nul, nul, nul);
-    hipLaunchKernelGGL((xf_stem_kernel<4, 8, 8, 2, false, false>), dim3(xf_grid(B * px(1))), dim3(256), 0, stream, s.s1, P + l.g[1].w, P + l.g[1].b, s.s2, Hr, Wr,
+    hipLaunchKernelGGL((xf_stem_kernel<4, 8, 8, 2, false, false>), dim3(blocks_256(B * px(1))), dim3(256), 0, stream, s.s1, P + l.g[1].w, P + l.g[1].b, s.s2, Hr, Wr,
                        Hr / 2, Wr / 2, B * px(1), nul, nul, nul, nul);
-    hipLaunchKernelGGL((xf_stem_kernel<8, 8, 8, 1, false, false>), dim3(xf_grid(B * px(1))), dim3(256), 0, stream, s.s2, P + l.g[2].w, P + l.g[2].b, s.s3, Hr / 2,
+    hipLaunchKernelGGL((xf_stem_kernel<8, 8, 8, 1, false, false>), dim3(blocks_256(B * px(1))), dim3(256), 0, stream, s.s2, P + l.g[2].w, P + l.g[2].b, s.s3, Hr / 2,
                        Wr / 2, Hr / 2, Wr / 2, B * px(1), nul, nul, nul, nul);
-    hipLaunchKernelGGL((xf_stem_kernel<8, 24, 32, 2, false, true>), dim3(xf_grid(B * px(2))), dim3(256), 0, stream, s.s3, P + l.g[3].w, P + l.g[3].b, s.q0, Hr / 2,
+    hipLaunchKernelGGL((xf_stem_kernel<8, 24, 32, 2, false, true>), dim3(blocks_256(B * px(2))), dim3(256), 0, stream, s.s3, P + l.g[3].w, P + l.g[3].b, s.q0, Hr / 2,
                        Wr / 2, Hr / 4, Wr / 4, B * px(2), s.norm, s.gray, P + l.skw, P + l.skb);
     IMCUI_CHECK_LAUNCH(h);
     // ---- block2 .. block5
@@ -727,7 +716,7 @@ extern "C" int imcui_hip_xfeat_forward(imcui_hip_t* h, const float* packed, cons
     // ---- fusion, heads
     const int h8 = Hr / 8, w8 = Wr / 8;
     const long np3 = (long)B * px(3);
-    hipLaunchKernelGGL(xf_fuse_kernel, dim3(xf_grid(np3 * 16)), dim3(256), 0, stream, s.e0, s.x4a, s.x5c, s.e1, h8, w8, np3 * 16);
+    hipLaunchKernelGGL(xf_fuse_kernel, dim3(blocks_256(np3 * 16)), dim3(256), 0, stream, s.e0, s.x4a, s.x5c, s.e1, h8, w8, np3 * 16);
     IMCUI_CHECK_LAUNCH(h);
     IMCUI_RUN(layer(16, s.e1, 3, s.e2, 64));
     IMCUI_RUN(layer(17, s.e2, 3, s.e1, 64));
@@ -739,7 +728,7 @@ extern "C" int imcui_hip_xfeat_forward(imcui_hip_t* h, const float* packed, cons
     float* k1h = kpt_heat ? kpt_heat : s.k1h;
     hipLaunchKernelGGL(xf_heads_kernel, dim3((unsigned)((np3 + 3) / 4)), dim3(256), 0, stream, s.e3, s.e2, P + l.g[XF_L_HEAT].w, P + l.g[XF_L_HEAT].b, m1, rel,
                        np3);
-    hipLaunchKernelGGL(xf_unfold_kernel, dim3(xf_grid(np3 * 16)), dim3(256), 0, stream, s.gray, s.norm, s.e0, h8, w8, np3 * 16);
+    hipLaunchKernelGGL(xf_unfold_kernel, dim3(blocks_256(np3 * 16)), dim3(256), 0, stream, s.gray, s.norm, s.e0, h8, w8, np3 * 16);
     IMCUI_CHECK_LAUNCH(h);
     IMCUI_RUN(layer(22, s.e0, 3, s.e1, 64));
     IMCUI_RUN(layer(23, s.e1, 3, s.e2, 64));
