@@ -286,9 +286,15 @@ extern "C" int imcui_hip_gemm_route_counts(const imcui_hip_t* h, int* out, int n
     for (int i = 0; i < n && i < IMCUI_GEMM_ROUTE_SLOTS; ++i) out[i] = h->gemm_route_count[i];
     return IMCUI_GEMM_ROUTE_SLOTS;
 }
+extern "C" int imcui_hip_gemm_route_features(const imcui_hip_t* h, int* out, int n) {
+    if (!h || (!out && n > 0)) return -1;
+    for (int i = 0; i < n && i < IMCUI_GEMM_ROUTE_SLOTS; ++i) out[i] = h->gemm_route_features[i];
+    return IMCUI_GEMM_ROUTE_SLOTS;
+}
 extern "C" int imcui_hip_gemm_route_reset(imcui_hip_t* h) {
     if (!h) return IMCUI_ERR_ARG;
     memset(h->gemm_route_count, 0, sizeof h->gemm_route_count);
+    memset(h->gemm_route_features, 0, sizeof h->gemm_route_features);
     h->gemm_last_route = 0;
     return IMCUI_OK;
 }

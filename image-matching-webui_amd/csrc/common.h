@@ -208,9 +208,11 @@ struct imcui_hip_s {
     int loftr_fine_mode;  // how the last imcui_hip_loftr_forward evaluated the last FPN stage: 0 dense maps, 1 on the windows of the matches (bench.py reports it)
     int loftr_fine_matches;  // the match count that call read back (-1: no read-back)
     // which GEMM instantiation gemm_launch launched last (GEMM_ROUTE of gemm.h, 0 = none) and how often each one ran since the last
-    // imcui_hip_gemm_route_reset: stored by the launch sites themselves, read by the kernel-variant tests
+    // imcui_hip_gemm_route_reset: stored by the launch sites themselves, read by the kernel-variant tests; plus the OR of the features
+    // (GemmFeature of gemm.h, derived from the launch parameters) every launch of a route ran with
     int gemm_last_route;
     int gemm_route_count[IMCUI_GEMM_ROUTE_SLOTS];
+    int gemm_route_features[IMCUI_GEMM_ROUTE_SLOTS];
     // the same for attention_launch (ATTN_ROUTE of attention.h; imcui_hip_attn_route_reset)
     int attn_last_route;
     int attn_route_count[IMCUI_ATTN_ROUTE_SLOTS];

@@ -107,8 +107,7 @@ struct GemmP {
     // implicit im2col with dilated taps (conv_k > 0): tap (ky, kx) reads input pixel (oy stride - pad + ky conv_dil, ox stride - pad +
     // kx conv_dil).  0 / 1 = no dilation: the launch is the undilated one, instantiation and bits.  > 1 selects the ASRC = 2
     // instantiations (GR_EXACT_DIL / GR_CONVD_*); the single-product arithmetic is not built for them
-    // Dilated launches with K >= 2048 sum in two levels (gemm.hip, GEMM_CHUNK_MIN_K): the exact kernel in place, the split arithmetic
-    // (pre-split planes) on the 128-column kernel's CHUNK instantiation, route GR_CONVD_128 whatever N
+    // Dilated launches with K >= 2048 sum in two levels (gemm.hip, GEMM_CHUNK_MIN_K): the exact kernel in place, the split arithmetic (pre-split planes) on the 128-column kernel's CHUNK instantiation, route GR_CONVD_128 whatever N
     int conv_dil = 0;
 };
 
@@ -142,10 +141,92 @@ enum GemmRouteKind {
 };
 #define GEMM_ROUTE(kind, epi) ((kind) * 16 + (epi))
 static_assert(GR_NKIND * 16 <= IMCUI_GEMM_ROUTE_SLOTS, "route table of imcui_hip_s too small");
-static inline void gemm_route_note(imcui_hip_s* h, int kind, int epi) {
+#define GEMM_CHUNK_MIN_K 2048  // dilated launches (the exact kernel; the split kernel on pre-split planes) sum in two levels from this K on (gemm.hip)
+// undilated launches of the exact kernel take its two-level instantiation from this K on: one chain holds the 2e-6 bar of the exact mode
+// at K = 2048 .. 2400 and misses it at K = 4608 (tests/test_gpu_gemm_variants.py, the longk_* cases), and that instantiation runs at a
+// third of the occupancy, so nothing below gets it
+#define GEMM_EXACT_CHUNK_MIN_K 4096
+
+// What a launch ran with besides its route: the route names the kernel instantiation, but most of the hand-written index arithmetic
+// (tap walk, borders, device-side counts, output strides, residuals) is chosen by the parameters.  gemm_features derives the mask from
+// the parameters of the launch and every gemm_route_note call passes it, so the mask cannot disagree with what ran; the handle keeps
+// the OR per route (imcui_hip_gemm_route_features).  Host code only, O(1).  Values are part of the test interface
+// (imcui_hip/backend.py GEMM_FEATURES; a CPU test compares the two).
+enum GemmFeature {
+    GF_CONV_K1 = 1,             // implicit im2col, conv_k == 1
+    GF_CONV_K3 = 2,             // ... conv_k == 3
+    GF_CONV_K5 = 4,             // ... conv_k == 5
+    GF_CONV_KOTHER = 8,         // ... any other conv_k (2: R2D2's last layers)
+    GF_STRIDE2 = 16,            // conv_stride == 2
+    GF_STRIDE_OTHER = 32,       // conv_stride > 2 (own bit: the tests of stride 2 say nothing about a larger step between output pixels)
+    GF_PAD_NOT_SAME = 64,       // conv_pad != ((conv_k - 1) dilation) / 2: valid convolutions and every other pad
+    GF_DILATED = 128,           // conv_dil > 1
+    GF_CHUNK = 256,             // the two-level sum (dilated, K >= GEMM_CHUNK_MIN_K, exact kernel or pre-split planes; undilated exact kernel, K >= GEMM_EXACT_CHUNK_MIN_K)
+    GF_LONG_K = 512,            // K >= GEMM_CHUNK_MIN_K summed in ONE level: every other launch
+    GF_RESID = 1024,            // plain residual (EPI_CONV with resid, EPI_RESID)
+    GF_RUP = 2048,              // bilinear x2 up-sampled residual (rup_h > 0)
+    GF_ACT1 = 4096,             // EPI_CONV activation 1 (ReLU)
+    GF_ACT2 = 8192,             // ... 2 (LeakyReLU)
+    GF_ACT3 = 16384,            // ... 3 (GELU)
+    GF_LDC = 32768,             // ldc != N (row-major epilogues)
+    GF_N_MOD32 = 65536,         // N % 32 != 0: a partial weight fragment, scalar stores
+    GF_N_MOD_TILE = 131072,     // N % (column tile of the route: 256 on the *_256 and wreg kinds, else 128) != 0
+    GF_M_SMALL = 262144,        // M < 128: a single partial row tile
+    GF_A2 = 524288,             // second K slab
+    GF_BATCH = 1048576,         // batch > 1
+    GF_MCNT = 2097152,          // device-side row counts
+    GF_NCNT = 4194304,          // device-side column counts
+    GF_CONV_BATCHED = 8388608,  // implicit im2col together with (batch > 1 or mcnt): the pixel decode runs on per-item row counts
+    GF_CNT = 16777216,          // ragged sequences (cnt)
+    GF_ACTIVE = 33554432,       // per-pair active flags
+    GF_WSEL = 67108864,         // per-pair weight selection
+    GF_LN = 134217728,          // folded LayerNorm (ln_stats)
+    GF_ALPHA = 268435456,       // alpha != 1 on an epilogue that reads it (EPI_BIAS and the attention layouts)
+    GF_NO_BIAS = 536870912,     // null bias
+    GF_GROUP_ROWS = 1073741824  // group_rows > 1: the tiles are walked in another order (gemm_tile.h), own bit since the row / column decode differs
+};
+static inline int gemm_features(const GemmP& p, int kind) {
+    int f = 0;
+    const bool row_major = p.epi == EPI_BIAS || p.epi == EPI_RELU || p.epi == EPI_RESID || p.epi == EPI_CONV;
+    if (p.conv_k > 0) {
+        const int dil = p.conv_dil > 1 ? p.conv_dil : 1;
+        f |= p.conv_k == 1 ? GF_CONV_K1 : p.conv_k == 3 ? GF_CONV_K3 : p.conv_k == 5 ? GF_CONV_K5 : GF_CONV_KOTHER;
+        f |= p.conv_stride == 2 ? GF_STRIDE2 : p.conv_stride > 2 ? GF_STRIDE_OTHER : 0;
+        f |= p.conv_pad != (p.conv_k - 1) * dil / 2 ? GF_PAD_NOT_SAME : 0;
+        f |= dil > 1 ? GF_DILATED : 0;
+        f |= p.batch > 1 || p.mcnt ? GF_CONV_BATCHED : 0;
+    }
+    const bool chunk = (kind == GR_EXACT && p.K >= GEMM_EXACT_CHUNK_MIN_K) || ((kind == GR_EXACT_DIL || kind == GR_CONVD_128) && p.K >= GEMM_CHUNK_MIN_K);
+    f |= chunk ? GF_CHUNK : p.K >= GEMM_CHUNK_MIN_K ? GF_LONG_K : 0;
+    if (p.rup_h > 0)
+        f |= GF_RUP;
+    else if (p.epi == EPI_RESID || (p.epi == EPI_CONV && p.resid))
+        f |= GF_RESID;
+    if (p.epi == EPI_CONV) f |= p.act == 1 ? GF_ACT1 : p.act == 2 ? GF_ACT2 : p.act == 3 ? GF_ACT3 : 0;
+    f |= row_major && p.ldc != p.N ? GF_LDC : 0;
+    f |= p.N % 32 ? GF_N_MOD32 : 0;
+    const bool wide = kind == GR_SPLIT_256 || kind == GR_SPLIT_256_SINGLE || kind == GR_CONV_256 || kind == GR_CONV_256_SINGLE || kind == GR_CONVD_256 ||
+                      (kind >= GR_WREG_ROLLED && kind <= GR_WREG_MT1);
+    f |= p.N % (wide ? 256 : 128) ? GF_N_MOD_TILE : 0;
+    f |= p.M < 128 ? GF_M_SMALL : 0;
+    f |= p.A2 ? GF_A2 : 0;
+    f |= p.batch > 1 ? GF_BATCH : 0;
+    f |= p.mcnt ? GF_MCNT : 0;
+    f |= p.ncnt ? GF_NCNT : 0;
+    f |= p.cnt ? GF_CNT : 0;
+    f |= p.active ? GF_ACTIVE : 0;
+    f |= p.wsel ? GF_WSEL : 0;
+    f |= p.ln_stats ? GF_LN : 0;
+    f |= p.alpha != 1.0f && (p.epi == EPI_BIAS || p.epi == EPI_QKV || p.epi == EPI_CROSS || p.epi == EPI_QKV_VIT) ? GF_ALPHA : 0;
+    f |= p.bias == nullptr ? GF_NO_BIAS : 0;
+    f |= p.group_rows > 1 ? GF_GROUP_ROWS : 0;
+    return f;
+}
+static inline void gemm_route_note(imcui_hip_s* h, const GemmP& p, int kind, int epi) {
     const int r = GEMM_ROUTE(kind, epi);
     h->gemm_last_route = r;
     ++h->gemm_route_count[r];
+    h->gemm_route_features[r] |= gemm_features(p, kind);
 }
 
 int gemm_launch(imcui_hip_s* h, const GemmP& p, hipStream_t stream);

@@ -183,9 +183,10 @@ __device__ __forceinline__ const float* gemm_a_src(const GemmP& p, const float* 
 
 // ------------------------------------------------------------------ exact f32 kernel
 #define BK32 32
-#define GEMM_CHUNK_MIN_K 2048  // exact dilated kernel: two-level summation from this K on
+// exact kernel: two-level summation (TWO: a second accumulator set, 64 more registers and occupancy 1 instead of 3, so it is an
+// instantiation of its own) ...
 #define GEMM_CHUNK_TILES 4     // ... in chunks of 4 K-tiles (128 products)
-template <int EPI, bool DIL = false>
+template <int EPI, bool DIL = false, bool CHUNK = false>
 __global__ __launch_bounds__(256) void gemm_kernel(GemmP p) {
     __shared__ float4 As[(BK32 / 4) * LDS_ROWS];
     __shared__ float4 Bs[(BK32 / 4) * LDS_ROWS];
@@ -207,14 +208,17 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmP p) {
         for (int n = 0; n < 2; ++n)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[m][n][r] = 0.0f;
-    // DIL, K >= GEMM_CHUNK_MIN_K: two-level summation.  One chain of K / 2 float32 accumulations loses sqrt(K)-many roundings (measured
-    // against float64 on one set of operands: 7.7e-07 at K = 576, 1.2e-06 at 1152, 1.9e-06 at 2304, 3.3e-06 at 4608, dilated or not);
-    // every GEMM_CHUNK_TILES K-tiles the accumulators are added to a second set and restart from zero.  Only the dilated instantiation
-    // carries it (D2-Net's K = 2304 / 4608 layers); launches below the threshold (R2D2: K <= 1152) keep their single chain and bits.
-    constexpr int TN = DIL ? 2 : 1;
+    // Two-level summation.  One chain of K / 2 float32 accumulations loses sqrt(K)-many roundings (measured against float64 on one set
+    // of operands: 7.7e-07 at K = 576, 1.2e-06 at 1152, 1.9e-06 at 2304, 3.3e-06 at 4608, dilated or not); every GEMM_CHUNK_TILES
+    // K-tiles the accumulators are added to a second set and restart from zero.  The dilated instantiation carries it and takes it from
+    // K = GEMM_CHUNK_MIN_K on (D2-Net's K = 2304 / 4608 layers; R2D2, K <= 1152, keeps its single chain and bits); undilated launches
+    // get the CHUNK instantiation from the launcher from K = GEMM_EXACT_CHUNK_MIN_K on (gemm.h) and the plain one, with the registers
+    // and bits it always had, below.
+    constexpr bool TWO = DIL || CHUNK;
+    constexpr int TN = TWO ? 2 : 1;
     f32x16 tot[TN][TN];
-    const bool chunked = DIL && p.K >= GEMM_CHUNK_MIN_K;
-    if constexpr (DIL) {
+    const bool chunked = CHUNK || (DIL && p.K >= GEMM_CHUNK_MIN_K);
+    if constexpr (TWO) {
 #pragma unroll
         for (int m = 0; m < 2; ++m)
 #pragma unroll
@@ -272,7 +276,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmP p) {
                     acc[m][n] = mfma32(b[n].w, a[m].w, acc[m][n]);
                 }
         }
-        if constexpr (DIL) {
+        if constexpr (TWO) {
             if (chunked && (kt % GEMM_CHUNK_TILES) == GEMM_CHUNK_TILES - 1) {
 #pragma unroll
                 for (int m = 0; m < 2; ++m)
@@ -287,7 +291,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmP p) {
         }
         __syncthreads();
     }
-    if constexpr (DIL) {
+    if constexpr (TWO) {
         if (chunked) {
 #pragma unroll
             for (int m = 0; m < 2; ++m)
@@ -1144,34 +1148,37 @@ static void launch_one(imcui_hip_s* h, const GemmP& p, bool split, hipStream_t s
     const bool wide = split && wide_ok(p);
     const dim3 grid(cdiv(p.M, BM) * cdiv(p.N, wide ? 256 : BN), 1, p.batch);
     if (!split) {
-        gemm_route_note(h, GR_EXACT, EPI);
-        hipLaunchKernelGGL(gemm_kernel<EPI>, grid, dim3(256), 0, stream, p);
+        gemm_route_note(h, p, GR_EXACT, EPI);
+        if (p.K >= GEMM_EXACT_CHUNK_MIN_K)  // one long sum: the two-level instantiation (the plain one keeps its registers and bits)
+            hipLaunchKernelGGL((gemm_kernel<EPI, false, true>), grid, dim3(256), 0, stream, p);
+        else
+            hipLaunchKernelGGL(gemm_kernel<EPI>, grid, dim3(256), 0, stream, p);
     } else if (wide) {
         if constexpr (EPI == EPI_CONV) {
             if (p.single) {
-                gemm_route_note(h, GR_SPLIT_256_SINGLE, EPI);
+                gemm_route_note(h, p, GR_SPLIT_256_SINGLE, EPI);
                 hipLaunchKernelGGL((gemm_split_kernel<EPI, 0, true, 4, true>), grid, dim3(256), 0, stream, p);
                 return;
             }
         }
         if constexpr (EPI != EPI_QKV && EPI != EPI_CROSS) {
-            gemm_route_note(h, GR_SPLIT_256, EPI);
+            gemm_route_note(h, p, GR_SPLIT_256, EPI);
             hipLaunchKernelGGL((gemm_split_kernel<EPI, 0, true, 4>), grid, dim3(256), 0, stream, p);
         }
     }
     else if (p.Wh != nullptr) {
         if constexpr (EPI == EPI_CONV) {
             if (p.single) {
-                gemm_route_note(h, GR_SPLIT_128_SINGLE, EPI);
+                gemm_route_note(h, p, GR_SPLIT_128_SINGLE, EPI);
                 hipLaunchKernelGGL((gemm_split_kernel<EPI, 0, true, 2, true>), grid, dim3(256), occupancy_pad((long)grid.x * grid.z), stream, p);
                 return;
             }
         }
-        gemm_route_note(h, GR_SPLIT_128, EPI);
+        gemm_route_note(h, p, GR_SPLIT_128, EPI);
         hipLaunchKernelGGL((gemm_split_kernel<EPI, 0, true, 2>), grid, dim3(256), occupancy_pad((long)grid.x * grid.z), stream, p);
     }
     else {
-        gemm_route_note(h, GR_SPLIT_F32B, EPI);
+        gemm_route_note(h, p, GR_SPLIT_F32B, EPI);
         hipLaunchKernelGGL((gemm_split_kernel<EPI, 0, false, 2>), grid, dim3(256), 0, stream, p);
     }
 }
@@ -1182,40 +1189,43 @@ static void launch_conv(imcui_hip_s* h, const GemmP& p, bool split, hipStream_t 
     const dim3 grid(cdiv(p.M, BM) * cdiv(p.N, wide ? 256 : BN), 1, p.batch);
     if (p.conv_dil > 1) {  // dilated taps: the ASRC = 2 instantiations (gemm_launch has refused `single`)
         if (!split) {
-            gemm_route_note(h, GR_EXACT_DIL, EPI_CONV);
+            gemm_route_note(h, p, GR_EXACT_DIL, EPI_CONV);
             hipLaunchKernelGGL((gemm_kernel<EPI_CONV, true>), grid, dim3(256), 0, stream, p);
         } else if (chunk) {
-            gemm_route_note(h, GR_CONVD_128, EPI_CONV);
+            gemm_route_note(h, p, GR_CONVD_128, EPI_CONV);
             hipLaunchKernelGGL((gemm_split_kernel<EPI_CONV, 2, true, 2, false, true>), grid, dim3(256), 0, stream, p);
         } else if (wide) {
-            gemm_route_note(h, GR_CONVD_256, EPI_CONV);
+            gemm_route_note(h, p, GR_CONVD_256, EPI_CONV);
             hipLaunchKernelGGL((gemm_split_kernel<EPI_CONV, 2, true, 4>), grid, dim3(256), 0, stream, p);
         } else if (p.Wh != nullptr) {
-            gemm_route_note(h, GR_CONVD_128, EPI_CONV);
+            gemm_route_note(h, p, GR_CONVD_128, EPI_CONV);
             hipLaunchKernelGGL((gemm_split_kernel<EPI_CONV, 2, true, 2>), grid, dim3(256), occupancy_pad((long)grid.x * grid.z), stream, p);
         } else {
-            gemm_route_note(h, GR_CONVD_F32B, EPI_CONV);
+            gemm_route_note(h, p, GR_CONVD_F32B, EPI_CONV);
             hipLaunchKernelGGL((gemm_split_kernel<EPI_CONV, 2, false, 2>), grid, dim3(256), 0, stream, p);
         }
         return;
     }
     if (!split) {
-        gemm_route_note(h, GR_EXACT, EPI_CONV);
-        hipLaunchKernelGGL(gemm_kernel<EPI_CONV>, grid, dim3(256), 0, stream, p);
+        gemm_route_note(h, p, GR_EXACT, EPI_CONV);
+        if (p.K >= GEMM_EXACT_CHUNK_MIN_K)
+            hipLaunchKernelGGL((gemm_kernel<EPI_CONV, false, true>), grid, dim3(256), 0, stream, p);
+        else
+            hipLaunchKernelGGL(gemm_kernel<EPI_CONV>, grid, dim3(256), 0, stream, p);
     } else if (wide && p.single) {
-        gemm_route_note(h, GR_CONV_256_SINGLE, EPI_CONV);
+        gemm_route_note(h, p, GR_CONV_256_SINGLE, EPI_CONV);
         hipLaunchKernelGGL((gemm_split_kernel<EPI_CONV, 1, true, 4, true>), grid, dim3(256), 0, stream, p);
     } else if (wide) {
-        gemm_route_note(h, GR_CONV_256, EPI_CONV);
+        gemm_route_note(h, p, GR_CONV_256, EPI_CONV);
         hipLaunchKernelGGL((gemm_split_kernel<EPI_CONV, 1, true, 4>), grid, dim3(256), 0, stream, p);
     } else if (p.Wh != nullptr && p.single) {
-        gemm_route_note(h, GR_CONV_128_SINGLE, EPI_CONV);
+        gemm_route_note(h, p, GR_CONV_128_SINGLE, EPI_CONV);
         hipLaunchKernelGGL((gemm_split_kernel<EPI_CONV, 1, true, 2, true>), grid, dim3(256), occupancy_pad((long)grid.x * grid.z), stream, p);
     } else if (p.Wh != nullptr) {
-        gemm_route_note(h, GR_CONV_128, EPI_CONV);
+        gemm_route_note(h, p, GR_CONV_128, EPI_CONV);
         hipLaunchKernelGGL((gemm_split_kernel<EPI_CONV, 1, true, 2>), grid, dim3(256), occupancy_pad((long)grid.x * grid.z), stream, p);
     } else {
-        gemm_route_note(h, GR_CONV_F32B, EPI_CONV);
+        gemm_route_note(h, p, GR_CONV_F32B, EPI_CONV);
         hipLaunchKernelGGL((gemm_split_kernel<EPI_CONV, 1, false, 2>), grid, dim3(256), 0, stream, p);
     }
 }
@@ -1282,7 +1292,7 @@ int gemm_launch(imcui_hip_s* h, const GemmP& p, hipStream_t stream) {
             if (!split || p.Wh != nullptr || !p.st_rpm || !p.st_rps || !p.st_rpi || !p.st_cpm || !p.st_cps || !p.st_cpi || p.bias != nullptr || p.st_rpitch < p.M ||
                 p.st_cpitch < p.N || p.st_nct < cdiv(p.N, BN) || p.st_nrh < 2 * cdiv(p.M, BM))
                 return imcui_set_err(h, IMCUI_ERR_ARG, "gemm: EPI_NNSTAT needs the split mode, an f32 B operand, no bias and the six partial buffers");
-            gemm_route_note(h, GR_SPLIT_F32B, EPI_NNSTAT);
+            gemm_route_note(h, p, GR_SPLIT_F32B, EPI_NNSTAT);
             hipLaunchKernelGGL((gemm_split_kernel<EPI_NNSTAT, 0, false, 2>), dim3(cdiv(p.M, BM) * cdiv(p.N, BN), 1, p.batch), dim3(256), 0, stream, p);
             break;
         case EPI_CONV:

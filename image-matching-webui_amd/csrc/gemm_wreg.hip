@@ -546,7 +546,7 @@ bool gemm_wreg_ok(const imcui_hip_s* h, const GemmP& p) {
 // still gives every CU a workgroup
 template <int EPI, int MT>
 static void wreg_launch_small(imcui_hip_s* h, const GemmP& p, hipStream_t stream) {
-    gemm_route_note(h, MT == 2 ? GR_WREG_MT2 : GR_WREG_MT1, EPI);
+    gemm_route_note(h, p, MT == 2 ? GR_WREG_MT2 : GR_WREG_MT1, EPI);
     hipLaunchKernelGGL((gemm_wreg_kernel<EPI, false, true, MT>), dim3(cdiv(p.M, 32 * MT) * cdiv(p.N, WR_BN), 1, 1), dim3(256), 0, stream, p);
 }
 static int wreg_tile_tokens(const imcui_hip_s* h, const GemmP& p) {
@@ -564,18 +564,18 @@ static void wreg_launch(imcui_hip_s* h, const GemmP& p, hipStream_t stream) {
     const dim3 grid(cdiv(p.M, BM) * cdiv(p.N, WR_BN), 1, 1);
     const int kind = PIPE ? GR_WREG_PIPE : GR_WREG_ROLLED;
     switch (p.epi) {
-        case EPI_BIAS: gemm_route_note(h, kind, EPI_BIAS); hipLaunchKernelGGL((gemm_wreg_kernel<EPI_BIAS, false, PIPE>), grid, dim3(256), 0, stream, p); break;
-        case EPI_RELU: gemm_route_note(h, kind, EPI_RELU); hipLaunchKernelGGL((gemm_wreg_kernel<EPI_RELU, false, PIPE>), grid, dim3(256), 0, stream, p); break;
-        case EPI_RESID: gemm_route_note(h, kind, EPI_RESID); hipLaunchKernelGGL((gemm_wreg_kernel<EPI_RESID, false, PIPE>), grid, dim3(256), 0, stream, p); break;
-        case EPI_QKV: gemm_route_note(h, kind, EPI_QKV); hipLaunchKernelGGL((gemm_wreg_kernel<EPI_QKV, false, PIPE>), grid, dim3(256), 0, stream, p); break;
-        case EPI_CROSS: gemm_route_note(h, kind, EPI_CROSS); hipLaunchKernelGGL((gemm_wreg_kernel<EPI_CROSS, false, PIPE>), grid, dim3(256), 0, stream, p); break;
-        case EPI_QKV_VIT: gemm_route_note(h, kind, EPI_QKV_VIT); hipLaunchKernelGGL((gemm_wreg_kernel<EPI_QKV_VIT, false, PIPE>), grid, dim3(256), 0, stream, p); break;
+        case EPI_BIAS: gemm_route_note(h, p, kind, EPI_BIAS); hipLaunchKernelGGL((gemm_wreg_kernel<EPI_BIAS, false, PIPE>), grid, dim3(256), 0, stream, p); break;
+        case EPI_RELU: gemm_route_note(h, p, kind, EPI_RELU); hipLaunchKernelGGL((gemm_wreg_kernel<EPI_RELU, false, PIPE>), grid, dim3(256), 0, stream, p); break;
+        case EPI_RESID: gemm_route_note(h, p, kind, EPI_RESID); hipLaunchKernelGGL((gemm_wreg_kernel<EPI_RESID, false, PIPE>), grid, dim3(256), 0, stream, p); break;
+        case EPI_QKV: gemm_route_note(h, p, kind, EPI_QKV); hipLaunchKernelGGL((gemm_wreg_kernel<EPI_QKV, false, PIPE>), grid, dim3(256), 0, stream, p); break;
+        case EPI_CROSS: gemm_route_note(h, p, kind, EPI_CROSS); hipLaunchKernelGGL((gemm_wreg_kernel<EPI_CROSS, false, PIPE>), grid, dim3(256), 0, stream, p); break;
+        case EPI_QKV_VIT: gemm_route_note(h, p, kind, EPI_QKV_VIT); hipLaunchKernelGGL((gemm_wreg_kernel<EPI_QKV_VIT, false, PIPE>), grid, dim3(256), 0, stream, p); break;
         default:
             if (p.single) {
-                gemm_route_note(h, PIPE ? GR_WREG_PIPE_SINGLE : GR_WREG_ROLLED_SINGLE, EPI_CONV);
+                gemm_route_note(h, p, PIPE ? GR_WREG_PIPE_SINGLE : GR_WREG_ROLLED_SINGLE, EPI_CONV);
                 hipLaunchKernelGGL((gemm_wreg_kernel<EPI_CONV, true, PIPE>), grid, dim3(256), 0, stream, p);
             } else {
-                gemm_route_note(h, kind, EPI_CONV);
+                gemm_route_note(h, p, kind, EPI_CONV);
                 hipLaunchKernelGGL((gemm_wreg_kernel<EPI_CONV, false, PIPE>), grid, dim3(256), 0, stream, p);
             }
     }

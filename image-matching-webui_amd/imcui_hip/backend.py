@@ -2827,6 +2827,17 @@ GEMM_ROUTE_KINDS = {"none": 0, "exact": 1, "split_f32b": 2, "split_128": 3, "spl
                     "conv_f32b": 7, "conv_128": 8, "conv_256": 9, "conv_128_single": 10, "conv_256_single": 11, "wreg_rolled": 12,
                     "wreg_pipe": 13, "wreg_rolled_single": 14, "wreg_pipe_single": 15, "wreg_mt2": 16, "wreg_mt1": 17,
                     "exact_dil": 18, "convd_f32b": 19, "convd_128": 20, "convd_256": 21}  # fmt: skip
+# GemmFeature of csrc/gemm.h: what a launch ran with besides its route (imcui_hip_gemm_route_features)
+GEMM_FEATURES = {"conv_k1": 1 << 0, "conv_k3": 1 << 1, "conv_k5": 1 << 2, "conv_kother": 1 << 3, "stride2": 1 << 4, "stride_other": 1 << 5,
+                 "pad_not_same": 1 << 6, "dilated": 1 << 7, "chunk": 1 << 8, "long_k": 1 << 9, "resid": 1 << 10, "rup": 1 << 11,
+                 "act1": 1 << 12, "act2": 1 << 13, "act3": 1 << 14, "ldc": 1 << 15, "n_mod32": 1 << 16, "n_mod_tile": 1 << 17,
+                 "m_small": 1 << 18, "a2": 1 << 19, "batch": 1 << 20, "mcnt": 1 << 21, "ncnt": 1 << 22, "conv_batched": 1 << 23,
+                 "cnt": 1 << 24, "active": 1 << 25, "wsel": 1 << 26, "ln": 1 << 27, "alpha": 1 << 28, "no_bias": 1 << 29,
+                 "group_rows": 1 << 30}  # fmt: skip
+GEMM_CHUNK_MIN_K = 2048  # gemm.h: dilated launches sum in two levels from this K on, and K >= this is a "long" sum (long_k / chunk)
+GEMM_EXACT_CHUNK_MIN_K = 4096  # gemm.h: undilated launches of the exact kernel sum in two levels from this K on
+GEMM_WIDE_KINDS = ("split_256", "split_256_single", "conv_256", "conv_256_single", "convd_256", "wreg_rolled", "wreg_pipe",
+                   "wreg_rolled_single", "wreg_pipe_single", "wreg_mt2", "wreg_mt1")  # 256-column tiles; every other kind: 128
 
 
 def gemm_route(kind: str, epi: str) -> int:
@@ -2921,6 +2932,19 @@ def gemm_route_counts(device: torch.device) -> dict:
     buf = (C.c_int * n)()
     hd.lib.imcui_hip_gemm_route_counts(hd.h, buf, n)
     return {r: c for r, c in enumerate(buf) if c}
+
+
+def gemm_route_features(device: torch.device) -> dict:
+    """{route: OR of the GEMM_FEATURES bits its launches ran with} since gemm_route_reset (routes with no feature are absent)."""
+    hd = get_handle(device)
+    n = hd.lib.imcui_hip_gemm_route_features(hd.h, None, 0)
+    buf = (C.c_int * n)()
+    hd.lib.imcui_hip_gemm_route_features(hd.h, buf, n)
+    return {r: c for r, c in enumerate(buf) if c}
+
+
+def gemm_feature_names(mask: int) -> list:
+    return [k for k, v in GEMM_FEATURES.items() if mask & v]
 
 
 def gemm_route_reset(device: torch.device) -> None:

@@ -305,6 +305,7 @@ SIGNATURES = {
     "imcui_hip_gemm_desc_bytes": (C.c_size_t, []),
     "imcui_hip_gemm_last_route": (C.c_int, [C.c_void_p]),
     "imcui_hip_gemm_route_counts": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int]),
+    "imcui_hip_gemm_route_features": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int]),
     "imcui_hip_gemm_route_reset": (C.c_int, [C.c_void_p]),
     "imcui_hip_conv3x3_pack": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "imcui_hip_conv3x3_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 7 + [C.c_void_p]),

@@ -1069,9 +1069,13 @@ int imcui_hip_gemm_probe_f32(imcui_hip_t* h, const imcui_hip_gemm_desc* d, void*
 size_t imcui_hip_gemm_desc_bytes(void);
 /* Route of the last GEMM launch on this handle = 16 kind + epilogue (csrc/gemm.h GemmRouteKind, GemmEpi; 0 = nothing launched,
  * e.g. a refused call), and launches per route since imcui_hip_gemm_route_reset: route_counts copies min(n, slots) counters to
- * out and returns the slot count.  Every GEMM launch of every network records its route (one host-side store). */
+ * out and returns the slot count.  Every GEMM launch of every network records its route (one host-side store) and ORs the features
+ * it ran with (csrc/gemm.h GemmFeature: tap size, stride, padding, dilation, residual kind, activation, output stride, partial
+ * tiles, second K slab, batch and device-side counts, ...; derived from the launch parameters on the host) into its route's mask:
+ * route_features copies the masks the same way.  route_reset clears both tables. */
 int imcui_hip_gemm_last_route(const imcui_hip_t* h);
 int imcui_hip_gemm_route_counts(const imcui_hip_t* h, int* out, int n);
+int imcui_hip_gemm_route_features(const imcui_hip_t* h, int* out, int n);
 int imcui_hip_gemm_route_reset(imcui_hip_t* h);
 
 /* ---- test entry into the attention launcher (tests/test_gpu_attention_variants.py) -------------------------------------------

@@ -481,12 +481,13 @@ def _lightglue(problems):
 
 
 def test_attention_routes_of_every_network_are_covered():
-    """Reset the per-handle attention route counters, run the networks of the GEMM gate in both arithmetic modes (DUSt3R in both of its
-    arithmetics among them), one lone LightGlue pair with more than 512 keypoints per image (the key-split launch) and a batch of the
+    """The attention routes of every network of the tree in both arithmetic modes (the sweep of the GEMM gate,
+    test_gpu_gemm_variants.network_sweep: one cached pass that reads all four route recorders per network; DUSt3R in both of its
+    arithmetics among them), then, on reset counters, one lone LightGlue pair with more than 512 keypoints per image (the key-split launch) and a batch of the
     same size (unsplit; variant 7 in the cross blocks), and require every attention route they launched to be one the case table
     covers with a float64 case."""
     from parity_utils import synthetic_matching_problem
-    from test_gpu_gemm_variants import _run_networks
+    from test_gpu_gemm_variants import network_sweep
 
     be = _backend()
     seen = {}
@@ -499,10 +500,12 @@ def test_attention_routes_of_every_network_are_covered():
         return got
 
     try:
+        for (mode, name), rec in network_sweep().items():
+            if rec["attn"]:
+                print(f"[attn-gate] mode {mode} {name}: " + ", ".join(f"{be.attn_route_name(r)} x{n}" for r, n in sorted(rec["attn"].items())))
+            for r, n in rec["attn"].items():
+                seen[r] = seen.get(r, 0) + n
         be.attn_route_reset(DEV)
-        for mode in (1, 0):
-            _run_networks(mode)
-            collect()
         be.set_precision(DEV, 1)
         pr = synthetic_matching_problem(70, 700, 640, 100)
         _lightglue([pr])

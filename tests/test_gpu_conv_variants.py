@@ -16,7 +16,9 @@ case then checks:
 The point-map head is compared in two steps: `raw` with the float64 1x1 convolution of the float64 feature map (4e-6), and pts / conf
 with xyz / max(|xyz|, 1e-8) * expm1(|xyz|) and 1 + exp(c) evaluated in float64 on the DEVICE's raw, per pixel relative to |pts| and to
 conf (HEAD_BAR_PTS, HEAD_BAR_CONF), which separates the transcendental error from the convolution's.
-test_conv_routes_of_every_network_are_covered runs every network once and fails on a (route, feature) pair the table does not cover.
+test_conv_routes_of_every_network_are_covered reads the one sweep over every network of the tree (test_gpu_gemm_variants.network_sweep;
+NETWORKS below names those that launch conv.hip: SuperPoint, LoFTR, EfficientLoFTR, DUSt3R, MASt3R, D2-Net, DeDoDe, NetVLAD) and fails on a
+(route, feature) pair the table does not cover.
 
 Errors measured on MI355X against float64 (max over the cases of the variant) and the bar each is held to:
   variant                        cases  measured   bar
@@ -36,15 +38,13 @@ The head's own error is one to two f32 ulp, as expected of sqrtf, expm1f, a divi
 """
 from __future__ import annotations
 
-import contextlib
 import math
 import zlib
-from unittest import mock
 
 import pytest
 import torch
 import torch.nn.functional as F
-from test_gpu_gemm_variants import DEV, NAN_F32, _discriminates, _round_act, _round_single, _run_networks, _sentinel, _untouched
+from test_gpu_gemm_variants import DEV, NAN_F32, _discriminates, _round_act, _round_single, _sentinel, _untouched
 
 pytestmark = pytest.mark.gpu
 
@@ -530,57 +530,50 @@ def test_fused_first_layer_equals_the_two_launches_bitwise():
 
 
 # ------------------------------------------------------------------ the gate: every (route, feature) a network launches has a case above
-NETWORKS = {  # name: (module, class, the method _run_networks calls, launches kernels of conv.hip in the exact f32 mode too)
-    "SuperPoint+LightGlue": ("imcui_hip.pipeline", "SuperPointLightGluePipeline", "forward", True),
-    "LoFTR": ("imcui_hip.hloc.matchers.loftr", "LoFTR", "forward_batched", False),
-    "EfficientLoFTR": ("imcui_hip.hloc.matchers.eloftr", "ELoFTR", "forward_batched", False),
-    "DUSt3R": ("imcui_hip.hloc.matchers.duster", "Duster", "forward_pairs", False),
-    "MASt3R": ("imcui_hip.hloc.matchers.mast3r", "Mast3r", "inference_output", False),
+# Networks of the sweep (test_gpu_gemm_variants.networks) that launch kernels of conv.hip in the split mode: True when they do in the
+# exact f32 mode too.  SuperPoint, D2-Net, NetVLAD (their VGG-16 trunks) and DeDoDe (its VGG-19 encoder) call conv3x3_launch or
+# conv3x3_split_launch by the handle's mode; the dense matchers' 3x3 layers run on the GEMM in the exact mode.  A network of the sweep
+# that is not named here must launch none (the gate asserts that too).
+NETWORKS = {
+    "SuperPoint+LightGlue": True,
+    "LoFTR": False,
+    "EfficientLoFTR": False,
+    "DUSt3R": False,
+    "MASt3R": False,
+    "D2-Net ss": True,
+    "D2-Net ms": True,
+    "DeDoDe": True,
+    "NetVLAD": True,
+    "NetVLAD whitened": True,
 }
 
 
 def test_conv_routes_of_every_network_are_covered():
-    """Reset the recorder, run every network once in each arithmetic mode (the GEMM gate's _run_networks), and require every (route,
-    feature bit) pair they launched to be one a case of the table launches, and at least one convolution launch per network that has
-    3x3 convolutions in that mode (the split mode: all five; the exact mode: SuperPoint, the dense matchers' 3x3 layers run on the GEMM)."""
-    import importlib
+    """Every network of the tree once in each arithmetic mode (the sweep of the GEMM gate, test_gpu_gemm_variants.network_sweep: one
+    cached pass that reads all four route recorders per network): every (route, feature bit) pair they launched must be one a case of the
+    table launches; a network of NETWORKS must have recorded a convolution launch (the split mode: all; the exact mode: those flagged),
+    and a network that is not in NETWORKS none."""
+    from test_gpu_gemm_variants import network_sweep
 
     be = _backend()
-    launches = {}
     seen_counts, seen_pairs = {}, set()
-
-    def counted(name, fn):
-        def wrapper(*a, **k):
-            before = sum(be.conv_route_counts(DEV).values())
-            try:
-                return fn(*a, **k)
-            finally:
-                torch.cuda.synchronize()
-                launches[name] = launches.get(name, 0) + sum(be.conv_route_counts(DEV).values()) - before
-
-        return wrapper
-
-    try:
-        for mode in (1, 0):
-            be.conv_route_reset(DEV)
-            launches.clear()
-            with contextlib.ExitStack() as stack:  # count the launches of each network: its entry method, wrapped for this run
-                for name, (mod, cls, meth, _) in NETWORKS.items():
-                    klass = getattr(importlib.import_module(mod), cls)
-                    stack.enter_context(mock.patch.object(klass, meth, counted(name, getattr(klass, meth))))
-                _run_networks(mode)
-            for name, (_, _, _, in_exact) in NETWORKS.items():
-                if mode == 1 or in_exact:
-                    assert launches.get(name, 0) > 0, f"{name}: no convolution launch recorded in mode {mode}"
-            feats = be.conv_route_features(DEV)
-            for r, n in be.conv_route_counts(DEV).items():
-                seen_counts[r] = seen_counts.get(r, 0) + n
-                name = be.conv_route_name(r)
-                seen_pairs.add((name, 0))
-                seen_pairs |= {(name, bit) for bit in FEATURES.values() if feats.get(r, 0) & bit}
-            print(f"[conv-gate] mode {mode}: launches per network " + ", ".join(f"{k} {v}" for k, v in sorted(launches.items())))
-    finally:
-        be.set_precision(DEV, 1)
+    unknown = set(NETWORKS) - {name for _, name in network_sweep()}
+    assert not unknown, f"NETWORKS names no network of the sweep: {sorted(unknown)}"
+    for (mode, name), rec in network_sweep().items():
+        launches = sum(n for n, _ in rec["conv"].values())
+        if name in NETWORKS:
+            if mode == 1 or NETWORKS[name]:
+                assert launches > 0, f"{name}: no convolution launch recorded in mode {mode}"
+        else:
+            assert launches == 0, f"{name} launches conv.hip in mode {mode} ({launches} launches): add it to NETWORKS"
+        if launches:
+            print(f"[conv-gate] mode {mode} {name}: {launches} launches, " + ", ".join(
+                f"{be.conv_route_name(r)} [{' '.join(be.conv_feature_names(m)) or '-'}]" for r, (n, m) in sorted(rec["conv"].items())))  # fmt: skip
+        for r, (n, mask) in rec["conv"].items():
+            seen_counts[r] = seen_counts.get(r, 0) + n
+            rname = be.conv_route_name(r)
+            seen_pairs.add((rname, 0))
+            seen_pairs |= {(rname, bit) for bit in FEATURES.values() if mask & bit}
     cov = covered_pairs()
     bit_name = {v: k for k, v in FEATURES.items()}
     fmt = lambda pairs: ", ".join(f"{r}+{bit_name[b]}" if b else r for r, b in sorted(pairs))  # noqa: E731

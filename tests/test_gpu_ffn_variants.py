@@ -502,21 +502,30 @@ def _run_lightglue():
 
 
 def test_ffn_routes_of_every_network_are_covered():
-    """Reset the per-handle route counters, run every network once in the split arithmetic (LightGlue act 0, SuperGlue act 1,
-    EfficientLoFTR act 2, LoFTR act 3) and LightGlue again with the 128- and 64-token tiles forced, and require every fused-FFN route
+    """The fused-FFN routes of every network of the tree in the split arithmetic (the sweep of the GEMM gate,
+    test_gpu_gemm_variants.network_sweep: one cached pass that reads all four route recorders per network; LightGlue act 0, SuperGlue
+    act 1, EfficientLoFTR act 2, LoFTR act 3; no launch in the exact mode, which the gate also asserts), and LightGlue again with the 128- and 64-token tiles forced, and require every fused-FFN route
     they launched to be one the case table covers.  A new instantiation or a changed tile rule without a kernel-level case fails here.
     (The rolled 128-token variant is reachable only through the IMCUI_FFN_VARIANT=0 environment switch and has no case: were anything to
     launch it, this gate would say so.)"""
-    from test_gpu_gemm_variants import _run_networks
+    from test_gpu_gemm_variants import network_sweep
 
     be = _backend()
+    seen = {}
     try:
+        for (mode, name), rec in network_sweep().items():
+            if rec["ffn"]:
+                print(f"[ffn-gate] mode {mode} {name}: " + ", ".join(f"{be.ffn_route_name(r)} x{n}" for r, n in sorted(rec["ffn"].items())))
+            assert mode == 1 or not rec["ffn"], f"{name}: a fused-FFN launch in the exact mode"
+            for r, n in rec["ffn"].items():
+                seen[r] = seen.get(r, 0) + n
         be.ffn_route_reset(DEV)
-        _run_networks(1)
+        be.set_precision(DEV, 1)
         for tile in (128, 64):
             with be.option(DEV, ffn_tile=tile):
                 _run_lightglue()
-        seen = be.ffn_route_counts(DEV)
+        for r, n in be.ffn_route_counts(DEV).items():
+            seen[r] = seen.get(r, 0) + n
     finally:
         be.set_precision(DEV, 1)
     cov = covered_routes()

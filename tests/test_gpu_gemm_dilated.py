@@ -3,7 +3,7 @@ and compared with float64 F.conv2d(dilation=...).
 
 conv_dil > 1 selects instantiations of their own (ASRC = 2 of gemm_split_kernel: routes convd_128 / convd_256 / convd_f32b; DIL of the
 exact kernel: exact_dil); conv_dil 0 / 1 is the undilated launch, instantiation and bits.  Every case asserts
-  * the route the launch site recorded,
+  * the route the launch site recorded and the feature mask recorded with it (launch_features: what the case declares),
   * the result within the bars of tests/test_gpu_gemm_variants.py, relative to max |reference|: 2e-6 exact f32, 4e-6 split,
   * NaN sentinels (private payload) in the rows past M and the columns past N inside ldc, bitwise unchanged,
   * that plausible wrong references (undilated taps, taps transposed) miss the bar.
@@ -50,9 +50,33 @@ def _operands(cid, cin, cout, k):
     return x, w, b
 
 
-def _launch(x, w, b, k, dil, pad, act, mode, planes=True, ldc=None, expect=None, stride=1, **extra):
-    """One probe launch into a sentinel buffer [M + 3, ldc]; returns (route or refusal code, buffer, M)."""
+def launch_features(kind, k, dil, pad, cin, cout, act, ldc=None, stride=1):
+    """GEMM_FEATURES mask (csrc/gemm.h GemmFeature) a launch of this file's shape records on the route kind `kind`: B x H x W map, bias
+    given, no residual.  The gate of tests/test_gpu_gemm_variants.py counts the cases of this file through it."""
     be = _backend()
+    F_ = be.GEMM_FEATURES
+    d = max(dil or 1, 1)
+    span = (k - 1) * d + 1
+    M = B * ((H + 2 * pad - span) // stride + 1) * ((W + 2 * pad - span) // stride + 1)
+    f = F_[{1: "conv_k1", 3: "conv_k3", 5: "conv_k5"}.get(k, "conv_kother")]
+    f |= F_["stride2"] if stride == 2 else F_["stride_other"] if stride > 2 else 0
+    f |= F_["pad_not_same"] if pad != (k - 1) * d // 2 else 0
+    f |= F_["dilated"] if d > 1 else 0
+    if k * k * cin >= be.GEMM_CHUNK_MIN_K:
+        f |= F_["chunk"] if (kind == "exact" and k * k * cin >= be.GEMM_EXACT_CHUNK_MIN_K) or kind in ("exact_dil", "convd_128") else F_["long_k"]
+    f |= {0: 0, 1: F_["act1"], 2: F_["act2"], 3: F_["act3"]}[act]
+    f |= F_["ldc"] if (ldc or cout) != cout else 0
+    f |= F_["n_mod32"] if cout % 32 else 0
+    f |= F_["n_mod_tile"] if cout % (256 if kind in be.GEMM_WIDE_KINDS else 128) else 0
+    f |= F_["m_small"] if M < 128 else 0
+    return f
+
+
+def _launch(x, w, b, k, dil, pad, act, mode, planes=True, ldc=None, expect=None, stride=1, **extra):
+    """One probe launch into a sentinel buffer [M + 3, ldc]; returns (route or refusal code, buffer, M).  A launch that is not refused
+    must have recorded the feature mask of launch_features."""
+    be = _backend()
+    be.gemm_route_reset(DEV)
     cout, cin = w.shape[:2]
     span = (k - 1) * max(dil or 1, 1) + 1
     ho, wo = (H + 2 * pad - span) // stride + 1, (W + 2 * pad - span) // stride + 1
@@ -71,7 +95,21 @@ def _launch(x, w, b, k, dil, pad, act, mode, planes=True, ldc=None, expect=None,
         return rc, buf, M
     r = be.gemm_probe(DEV, **f)
     torch.cuda.synchronize()
+    kind = be.gemm_route_name(r).split("/")[0]
+    got, want = be.gemm_route_features(DEV).get(r, 0), launch_features(kind, k, dil, pad, cin, cout, act, ldc, stride)
+    assert be.gemm_route_counts(DEV) == {r: 1} and got == want, (be.gemm_feature_names(got), be.gemm_feature_names(want))
     return r, buf, M
+
+
+def table_launches():
+    """[(route kind per mode {1: .., 0: ..}, arguments of launch_features)] of every launch the two case tables below make."""
+    out = []
+    for k, dil, pad, cin, cout in LAYERS:
+        for act in (1, 0):
+            out.append(({1: "convd_128" if dil > 1 else "conv_128", 0: "exact_dil" if dil > 1 else "exact"}, (k, dil, pad, cin, cout, act, cout + 4, 1)))
+    for c in OTHER:
+        out.append((c["routes"], (c["k"], c["dil"], c["pad"], c["cin"], c["cout"], 1, None, c.get("stride", 1))))
+    return out
 
 
 def _check_sentinels(buf, M, cout):
@@ -126,6 +164,9 @@ OTHER = [
     dict(id="f32b_k3_d4_c32_64", k=3, dil=4, pad=4, cin=32, cout=64, planes=False, routes={1: "convd_f32b", 0: "exact_dil"}),
     dict(id="stride2_k3_d2_c64_64", k=3, dil=2, pad=2, cin=64, cout=64, stride=2, routes={1: "convd_128", 0: "exact_dil"}),
     dict(id="n65_scalar_stores_k2_d4", k=2, dil=4, pad=2, cin=32, cout=65, routes={1: "convd_128", 0: "exact_dil"}),
+    # K = 4608 >= GEMM_CHUNK_MIN_K: the two-level sum (D2-Net's dilated 512-channel layers); pre-split planes take the 128-column kernel whatever N
+    dict(id="chunk_k3_d2_c512_512", k=3, dil=2, pad=2, cin=512, cout=512, routes={1: "convd_128", 0: "exact_dil"}),
+    dict(id="chunk_k3_d2_c512_64", k=3, dil=2, pad=2, cin=512, cout=64, routes={1: "convd_128", 0: "exact_dil"}),
 ]
 
 
