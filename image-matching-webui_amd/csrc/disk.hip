@@ -400,6 +400,22 @@ __global__ __launch_bounds__(1024) void dk_select_kernel(const float* __restrict
     if (tid == 0) nkpts[b] = cnt;
 }
 
+// The detection stage as `forward` launches it, on the heat map: status memset, count / scan / compact of the NMS survivors, selection.
+// The one launcher of both imcui_hip_disk_forward and the test entry imcui_hip_disk_select_probe.
+static int dk_select_launch(imcui_hip_t* h, const float* heat, int B, int H, int W, int window, float threshold, int max_keypoints, int kcap, int ccap, int* blkcnt,
+                            int* blkoff, int* ncand, float* cscore, int* cidx, float* keypoints, float* scores, int* num_keypoints, int* st, hipStream_t stream) {
+    hipMemsetAsync(st, 0, sizeof(int), stream);
+    const int nchunk = cdiv(H * W, SEL_CHUNK), r = window / 2;
+    const DkKeep keep{H, W, r, threshold};
+    hipLaunchKernelGGL(cand_count_kernel<DkKeep>, dim3(nchunk, B), dim3(256), 0, stream, heat, H * W, keep, blkcnt, nchunk);
+    hipLaunchKernelGGL(exclusive_scan_kernel<int>, dim3(B), dim3(1024), 0, stream, blkcnt, blkoff, ncand, (const int*)nullptr, nchunk, (long)nchunk);
+    hipLaunchKernelGGL((cand_compact_kernel<DkKeep, EmitScoreIndex>), dim3(nchunk, B), dim3(256), 0, stream, heat, H * W, keep, blkoff, nchunk, ccap,
+                       EmitScoreIndex{cscore, cidx, ccap});
+    hipLaunchKernelGGL(dk_select_kernel, dim3(B), dim3(1024), 0, stream, cscore, cidx, ccap, ncand, max_keypoints, kcap, W, keypoints, scores, num_keypoints, st);
+    IMCUI_CHECK_LAUNCH(h);
+    return IMCUI_OK;
+}
+
 // ------------------------------------------------------------------ sparse descriptors
 // rows [r0, r0 + DK_DESC_ROWS) of the key-point list: A[b][row - r0] = the 5x5 x 96 window of X around the key-point, (tap, channel)
 // order (the GEMM weight layout of pack_conv_gemm); zero outside the padded map.  One wave per key-point; rows past the count exit.
@@ -581,17 +597,8 @@ extern "C" int imcui_hip_disk_forward(imcui_hip_t* h, const float* packed, const
     float* heat = heatmap ? heatmap : s.heat;
     hipLaunchKernelGGL(dk_heat_kernel, dim3(cdiv(W, DK_HT), cdiv(H, DK_HT), B), dim3(256), 0, stream, s.X, P + l.hw, P + l.hb, heat, H, W, Hp, Wp);
     IMCUI_CHECK_LAUNCH(h);
-    int* st = status ? status : s.status;
-    hipMemsetAsync(st, 0, sizeof(int), stream);
-    const int nchunk = cdiv(H * W, SEL_CHUNK), r = window / 2, ccap = H * W;
-    const DkKeep keep{H, W, r, threshold};
-    hipLaunchKernelGGL(cand_count_kernel<DkKeep>, dim3(nchunk, B), dim3(256), 0, stream, heat, H * W, keep, s.blkcnt, nchunk);
-    hipLaunchKernelGGL(exclusive_scan_kernel<int>, dim3(B), dim3(1024), 0, stream, s.blkcnt, s.blkoff, s.ncand, (const int*)nullptr, nchunk, (long)nchunk);
-    hipLaunchKernelGGL((cand_compact_kernel<DkKeep, EmitScoreIndex>), dim3(nchunk, B), dim3(256), 0, stream, heat, H * W, keep, s.blkoff, nchunk, ccap,
-                       EmitScoreIndex{s.cscore, s.cidx, ccap});
-    hipLaunchKernelGGL(dk_select_kernel, dim3(B), dim3(1024), 0, stream, s.cscore, s.cidx, ccap, s.ncand, max_keypoints, kcap, W, keypoints, scores,
-                       num_keypoints, st);
-    IMCUI_CHECK_LAUNCH(h);
+    IMCUI_RUN(dk_select_launch(h, heat, B, H, W, window, threshold, max_keypoints, kcap, H * W, s.blkcnt, s.blkoff, s.ncand, s.cscore, s.cidx, keypoints, scores,
+                               num_keypoints, status ? status : s.status, stream));
     // ---- descriptors at the selected pixels: gather the windows, [rows, 2400] x [2400, 128] + bias, L2 norm
     const int L = DK_NL - 1;
     for (int r0 = 0; r0 < kcap; r0 += DK_DESC_ROWS) {
@@ -616,4 +623,43 @@ extern "C" int imcui_hip_disk_forward(imcui_hip_t* h, const float* packed, const
     hipLaunchKernelGGL(dk_l2norm_kernel, dim3(cdiv(kcap, 4), B), dim3(256), 0, stream, descriptors, num_keypoints, kcap);
     IMCUI_CHECK_LAUNCH(h);
     return IMCUI_OK;
+}
+
+// test entry: the detection stage alone, through the launcher `forward` calls, on a heat map given by the caller
+struct DkSelWs {
+    int *blkcnt, *blkoff, *ncand, *cidx;
+    float* cscore;
+    size_t total;
+    bool ok;
+};
+static DkSelWs dk_select_carve(void* ws, size_t bytes, int B, int H, int W, int ccap) {
+    WsAlloc a(ws, bytes);
+    DkSelWs s;
+    const int nchunk = cdiv(H * W, SEL_CHUNK);
+    s.blkcnt = a.get<int>((size_t)B * nchunk);
+    s.blkoff = a.get<int>((size_t)B * nchunk);
+    s.ncand = a.get<int>(B);
+    s.cscore = a.get<float>((size_t)B * ccap);
+    s.cidx = a.get<int>((size_t)B * ccap);
+    s.total = a.off;
+    s.ok = a.ok;
+    return s;
+}
+static bool dk_select_shape_ok(int B, int H, int W, int ccap) {
+    return B >= 1 && B <= 1024 && H >= 1 && W >= 1 && (long)H * W <= (1L << 24) && ccap >= 1 && ccap <= (1 << 24);
+}
+extern "C" size_t imcui_hip_disk_select_workspace_bytes(int B, int H, int W, int ccap) {
+    return dk_select_shape_ok(B, H, W, ccap) ? dk_select_carve(nullptr, 0, B, H, W, ccap).total : 0;
+}
+extern "C" int imcui_hip_disk_select_probe(imcui_hip_t* h, const float* heat, int B, int H, int W, int window, float threshold, int max_keypoints, int kcap, int ccap,
+                                           float* keypoints, float* scores, int* num_keypoints, int* status, void* ws, size_t ws_bytes, void* stream_) {
+    if (!h) return IMCUI_ERR_ARG;
+    if (!dk_select_shape_ok(B, H, W, ccap) || kcap < 1 || kcap > (1 << 24))
+        return imcui_set_err(h, IMCUI_ERR_ARG, "disk select probe: B=%d map %dx%d kcap=%d ccap=%d", B, H, W, kcap, ccap);
+    if (window < 1 || window % 2 == 0) return imcui_set_err(h, IMCUI_ERR_ARG, "disk select probe: window_size=%d must be odd", window);
+    if (!heat || !keypoints || !scores || !num_keypoints || !status) return imcui_set_err(h, IMCUI_ERR_ARG, "disk select probe: null argument");
+    DkSelWs s = dk_select_carve(ws, ws_bytes, B, H, W, ccap);
+    if (!ws || !s.ok) return imcui_set_err(h, IMCUI_ERR_WS, "disk select probe: workspace too small (%zu < %zu)", ws_bytes, s.total);
+    return dk_select_launch(h, heat, B, H, W, window, threshold, max_keypoints, kcap, ccap, s.blkcnt, s.blkoff, s.ncand, s.cscore, s.cidx, keypoints, scores,
+                            num_keypoints, status, (hipStream_t)stream_);
 }

@@ -363,6 +363,33 @@ __global__ __launch_bounds__(1024) void sp_topk_kernel(const unsigned long long*
     }
 }
 
+// ------------------------------------------------------------------ a5: select
+// The selection stage as `forward` launches it, on the post-NMS map: status memset, count / scan / compact into 64-bit keys, top-k.
+// The one launcher of both imcui_hip_superpoint_forward and the test entry imcui_hip_superpoint_select_probe.
+static int sp_select_launch(imcui_hip_t* h, const float* nms, int B, int H, int W, float keypoint_threshold, int remove_borders, int max_keypoints, int kcap,
+                            int cand_cap, int* blkcnt, int* blkoff, int* ncand, unsigned long long* cand, float* keypoints, float* scores, int* num_keypoints,
+                            int* st, hipStream_t stream) {
+    const int nchunk = cdiv(H * W, SEL_CHUNK);
+    hipMemsetAsync(st, 0, sizeof(int), stream);
+    const SpIsCand is_cand{H, W, keypoint_threshold, remove_borders};
+    hipLaunchKernelGGL(cand_count_kernel<SpIsCand>, dim3(nchunk, B), dim3(256), 0, stream, nms, H * W, is_cand, blkcnt, nchunk);
+    hipLaunchKernelGGL(exclusive_scan_kernel<int>, dim3(B), dim3(1024), 0, stream, blkcnt, blkoff, ncand, (const int*)nullptr, nchunk, (long)nchunk);
+    hipLaunchKernelGGL((cand_compact_kernel<SpIsCand, SpEmitKey>), dim3(nchunk, B), dim3(256), 0, stream, nms, H * W, is_cand, blkoff, nchunk, cand_cap,
+                       SpEmitKey{cand, cand_cap});
+    {
+        int np2 = 1;
+        const int kmax = max_keypoints < 0 ? 1 : (max_keypoints < TOPK_MAX ? max_keypoints : TOPK_MAX);
+        while (np2 < kmax) np2 <<= 1;
+        const size_t smem = (size_t)np2 * sizeof(unsigned long long);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(sp_topk_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)(TOPK_MAX * sizeof(unsigned long long)));
+        hipLaunchKernelGGL(sp_topk_kernel, dim3(B), dim3(1024), smem, stream, cand, cand_cap, ncand, max_keypoints, kcap, W,
+                           keypoints, scores, num_keypoints, st);
+    }
+    IMCUI_CHECK_LAUNCH(h);
+    return IMCUI_OK;
+}
+
 // ------------------------------------------------------------------ descriptor sampling
 // One wave per key-point: bilinear interpolation (grid_sample, align_corners=True, or the
 // reference's "fix_sampling" variant) of the L2-normalised dense descriptors, then L2 norm.
@@ -571,25 +598,8 @@ extern "C" int imcui_hip_superpoint_forward(imcui_hip_t* h, const float* packed,
     IMCUI_CHECK_LAUNCH(h);
     // a4: NMS ; a5: select
     IMCUI_RUN(nms_launch(h, dense, s.nms, B, H, W, nms_radius, stream));
-    const int nchunk = cdiv(H * W, SEL_CHUNK);
-    int* st = status ? status : s.status;
-    hipMemsetAsync(st, 0, sizeof(int), stream);
-    const SpIsCand is_cand{H, W, keypoint_threshold, remove_borders};
-    hipLaunchKernelGGL(cand_count_kernel<SpIsCand>, dim3(nchunk, B), dim3(256), 0, stream, s.nms, H * W, is_cand, s.blkcnt, nchunk);
-    hipLaunchKernelGGL(exclusive_scan_kernel<int>, dim3(B), dim3(1024), 0, stream, s.blkcnt, s.blkoff, s.ncand, (const int*)nullptr, nchunk, (long)nchunk);
-    hipLaunchKernelGGL((cand_compact_kernel<SpIsCand, SpEmitKey>), dim3(nchunk, B), dim3(256), 0, stream, s.nms, H * W, is_cand, s.blkoff, nchunk, cand_cap,
-                       SpEmitKey{s.cand, cand_cap});
-    {
-        int np2 = 1;
-        const int kmax = max_keypoints < 0 ? 1 : (max_keypoints < TOPK_MAX ? max_keypoints : TOPK_MAX);
-        while (np2 < kmax) np2 <<= 1;
-        const size_t smem = (size_t)np2 * sizeof(unsigned long long);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(sp_topk_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)(TOPK_MAX * sizeof(unsigned long long)));
-        hipLaunchKernelGGL(sp_topk_kernel, dim3(B), dim3(1024), smem, stream, s.cand, cand_cap, s.ncand, max_keypoints, kcap, W,
-                           keypoints, scores, num_keypoints, st);
-    }
-    IMCUI_CHECK_LAUNCH(h);
+    IMCUI_RUN(sp_select_launch(h, s.nms, B, H, W, keypoint_threshold, remove_borders, max_keypoints, kcap, cand_cap, s.blkcnt, s.blkoff, s.ncand, s.cand, keypoints,
+                               scores, num_keypoints, status ? status : s.status, stream));
     // a6: descriptor head + sampling
     IMCUI_RUN(conv(LDA, s.feat, s.head, Hc, Wc, 0));
     IMCUI_RUN(lin(LDB, s.head, s.ddesc, 256));
@@ -617,4 +627,42 @@ extern "C" int imcui_hip_superpoint_status(imcui_hip_t* h, int B, int H, int W, 
 extern "C" int imcui_hip_simple_nms(imcui_hip_t* h, const float* scores, float* out, int B, int H, int W, int nms_radius,
                                     void* stream_) {
     return nms_launch(h, scores, out, B, H, W, nms_radius, (hipStream_t)stream_);
+}
+
+// test entry: the selection stage alone, through the launcher `forward` calls, on a post-NMS map given by the caller
+struct SpSelWs {
+    int *blkcnt, *blkoff, *ncand;
+    unsigned long long* cand;
+    size_t total;
+    bool ok;
+};
+static SpSelWs sp_select_carve(void* ws, size_t ws_bytes, int B, int H, int W, int cand_cap) {
+    WsAlloc a(ws, ws_bytes);
+    SpSelWs s;
+    const int nchunk = cdiv(H * W, SEL_CHUNK);
+    s.blkcnt = a.get<int>((size_t)B * nchunk);
+    s.blkoff = a.get<int>((size_t)B * nchunk);
+    s.ncand = a.get<int>(B);
+    s.cand = a.get<unsigned long long>((size_t)B * cand_cap);
+    s.total = a.off;
+    s.ok = a.ok;
+    return s;
+}
+static bool sp_select_shape_ok(int B, int H, int W, int cand_cap) {
+    return B >= 1 && B <= 1024 && H >= 1 && W >= 1 && (long)H * W <= (1L << 24) && cand_cap >= 1 && cand_cap <= (1 << 24);
+}
+extern "C" size_t imcui_hip_superpoint_select_workspace_bytes(int B, int H, int W, int cand_cap) {
+    return sp_select_shape_ok(B, H, W, cand_cap) ? sp_select_carve(nullptr, 0, B, H, W, cand_cap).total : 0;
+}
+extern "C" int imcui_hip_superpoint_select_probe(imcui_hip_t* h, const float* nms, int B, int H, int W, float keypoint_threshold, int remove_borders,
+                                                 int max_keypoints, int kcap, int cand_cap, float* keypoints, float* scores, int* num_keypoints, int* status,
+                                                 void* ws, size_t ws_bytes, void* stream_) {
+    if (!h) return IMCUI_ERR_ARG;
+    if (!sp_select_shape_ok(B, H, W, cand_cap) || kcap < 1 || kcap > (1 << 24))
+        return imcui_set_err(h, IMCUI_ERR_ARG, "superpoint select probe: B=%d map %dx%d kcap=%d cand_cap=%d", B, H, W, kcap, cand_cap);
+    if (!nms || !keypoints || !scores || !num_keypoints || !status) return imcui_set_err(h, IMCUI_ERR_ARG, "superpoint select probe: null argument");
+    SpSelWs s = sp_select_carve(ws, ws_bytes, B, H, W, cand_cap);
+    if (!ws || !s.ok) return imcui_set_err(h, IMCUI_ERR_WS, "superpoint select probe: workspace too small (%zu < %zu)", ws_bytes, s.total);
+    return sp_select_launch(h, nms, B, H, W, keypoint_threshold, remove_borders, max_keypoints, kcap, cand_cap, s.blkcnt, s.blkoff, s.ncand, s.cand, keypoints,
+                            scores, num_keypoints, status, (hipStream_t)stream_);
 }

@@ -233,6 +233,31 @@ class SuperPointHIP:
             out["score_map"] = smap
         return out
 
+    def select_probe(self, nms: torch.Tensor, keypoint_threshold: float, remove_borders: int, max_keypoints: int, kcap: int,
+                     cand_cap: int | None = None, out: dict | None = None, check: bool = True):
+        """Test entry: the selection stage of `forward` alone (imcui_hip_superpoint_select_probe) on the post-NMS map nms [B,H,W].
+        `out` = caller's (pre-filled) keypoints [B,kcap,2], scores [B,kcap], num_keypoints [B] int32, status [1] int32; made here
+        when None.  Returns `out`; with check=False a refused call returns its negative status instead of raising."""
+        hd = get_handle(nms.device)
+        lib = hd.lib
+        nms = nms.contiguous().float()
+        B, H, W = nms.shape
+        cand_cap = H * W if cand_cap is None else int(cand_cap)
+        if out is None:
+            kpts, scores, _, nk, status, out = _sparse_outputs(B, max(1, kcap), 1, nms.device)
+            del out["descriptors"]
+        args = (_ptr(nms), B, H, W, float(keypoint_threshold), int(remove_borders), int(max_keypoints), int(kcap), cand_cap,
+                _ptr(out["keypoints"]), _ptr(out["scores"]), _ptr(out["num_keypoints"]), _ptr(out["status"]))  # fmt: skip
+        with self._ws.use(max(256, lib.imcui_hip_superpoint_select_workspace_bytes(B, H, W, cand_cap)), nms.device) as ws:
+            if check:
+                hd.launch(lib.imcui_hip_superpoint_select_probe, *args, _ptr(ws), ws.numel())
+            else:
+                with torch.cuda.device(hd.device_index):
+                    rc = lib.imcui_hip_superpoint_select_probe(hd.h, *args, _ptr(ws), ws.numel(), _stream_ptr())
+                if rc != 0:
+                    return rc
+        return out
+
 
 # ------------------------------------------------------------------ DISK
 def disk_tensor_names() -> list[str]:
@@ -303,6 +328,32 @@ class DiskHIP:
             )  # fmt: skip
         if want_heatmap:
             out["heatmap"] = heat
+        return out
+
+    def select_probe(self, heat: torch.Tensor, window: int, threshold: float, max_keypoints: int | None, kcap: int, ccap: int | None = None,
+                     out: dict | None = None, check: bool = True):
+        """Test entry: the detection stage of `forward` alone (imcui_hip_disk_select_probe) on the heat map heat [B,H,W].  `out` = caller's
+        (pre-filled) keypoints [B,kcap,2], scores [B,kcap], num_keypoints [B] int32, status [1] int32; made here when None.  Returns
+        `out`; with check=False a refused call returns its negative status instead of raising."""
+        hd = get_handle(heat.device)
+        lib = hd.lib
+        heat = heat.contiguous().float()
+        B, H, W = heat.shape
+        ccap = H * W if ccap is None else int(ccap)
+        maxk = -1 if max_keypoints is None or int(max_keypoints) < 0 else int(max_keypoints)
+        if out is None:
+            kpts, scores, _, nk, status, out = _sparse_outputs(B, max(1, kcap), 1, heat.device)
+            del out["descriptors"]
+        args = (_ptr(heat), B, H, W, int(window), float(threshold), maxk, int(kcap), ccap,
+                _ptr(out["keypoints"]), _ptr(out["scores"]), _ptr(out["num_keypoints"]), _ptr(out["status"]))  # fmt: skip
+        with self._ws.use(max(256, lib.imcui_hip_disk_select_workspace_bytes(B, H, W, ccap)), heat.device) as ws:
+            if check:
+                hd.launch(lib.imcui_hip_disk_select_probe, *args, _ptr(ws), ws.numel())
+            else:
+                with torch.cuda.device(hd.device_index):
+                    rc = lib.imcui_hip_disk_select_probe(hd.h, *args, _ptr(ws), ws.numel(), _stream_ptr())
+                if rc != 0:
+                    return rc
         return out
 
 
@@ -3269,6 +3320,56 @@ def attention_mx_f32(q, k, v, cnt, cross=False):
     scratch = torch.empty(nbytes, dtype=torch.uint8, device=q.device)
     hd.launch(hd.lib.imcui_hip_attention_mx_f32, _ptr(q), _ptr(k), _ptr(v), _ptr(o), _ptr(cnt), S, Hh, R, int(cross), _ptr(scratch), nbytes)
     return o
+
+
+# ------------------------------------------------------------------ the list-building blocks of csrc/select.h, entered directly
+SELECT_OPS = {"compact": 0, "scan": 1, "order_key": 2, "kth32": 3, "kth64": 4, "rank4": 5, "rank16": 6, "keep": 7, "cut": 8}
+SELECT_MAXB = 8  # IMCUI_SELECT_MAXB
+SELECT_RULES = {1: "op", 2: "B", 3: "n / capacity", 4: "k", 5: "cap / limit", 6: "null pointer", 7: "nlev"}  # imcui_hip_select_desc_check
+
+
+class SelectDesc(C.Structure):
+    """ctypes mirror of imcui_hip_select_desc (include/imcui_hip.h); the CPU suite compares its size with the library's."""
+
+    _fields_ = [("op", C.c_int), ("B", C.c_int), ("n", C.c_int), ("capacity", C.c_int), ("cap", C.c_int), ("limit", C.c_int), ("filter", C.c_int),
+                ("nlev", C.c_int), ("n_row", C.c_int * SELECT_MAXB), ("k_row", C.c_int * SELECT_MAXB), ("kth", C.c_ulonglong), ("score", C.c_void_p),
+                ("thr", C.c_void_p), ("key64", C.c_void_p), ("in_i32", C.c_void_p), ("n_dev", C.c_void_p), ("out_score", C.c_void_p),
+                ("out_idx", C.c_void_p), ("out_count", C.c_void_p), ("out_i32", C.c_void_p), ("out_aux", C.c_void_p), ("out_key32", C.c_void_p),
+                ("out_key64", C.c_void_p), ("status", C.c_void_p)]  # fmt: skip
+
+
+def select_desc(**fields) -> SelectDesc:
+    """A SelectDesc from `fields`: tensors become their data pointers, `op` may be a SELECT_OPS name, n_row / k_row take sequences."""
+    d = SelectDesc()
+    for k, v in fields.items():
+        if k == "op" and isinstance(v, str):
+            v = SELECT_OPS[v]
+        if k in ("n_row", "k_row"):
+            v = [int(x) for x in v]
+            if len(v) > SELECT_MAXB:
+                raise ImcuiHipError(f"select_desc: {k} holds at most {SELECT_MAXB} rows")
+            v = (C.c_int * SELECT_MAXB)(*v)
+        elif isinstance(v, torch.Tensor):
+            v = v.data_ptr()
+        elif v is None:
+            v = 0
+        setattr(d, k, v)
+    return d
+
+
+def select_probe(device: torch.device, check: bool = True, **fields) -> int:
+    """One op of imcui_hip_select_probe with the descriptor `fields` (device tensors become pointers).  Returns 0; with check=False a
+    refused call returns its negative status instead of raising."""
+    hd = get_handle(device)
+    for k, v in fields.items():
+        if isinstance(v, torch.Tensor) and v.device.type != "cuda":
+            raise ImcuiHipError(f"select_probe: field {k} must be a device tensor")
+    d = select_desc(**fields)
+    if check:
+        hd.launch(hd.lib.imcui_hip_select_probe, C.byref(d))
+        return 0
+    with torch.cuda.device(hd.device_index):
+        return int(hd.lib.imcui_hip_select_probe(hd.h, C.byref(d), _stream_ptr()))
 
 
 def simple_nms(scores: torch.Tensor, radius: int) -> torch.Tensor:

@@ -329,6 +329,19 @@ SIGNATURES = {
     "imcui_hip_ffn_route_counts": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int]),
     "imcui_hip_ffn_route_reset": (C.c_int, [C.c_void_p]),
     "imcui_hip_attention_mx_f32": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 4 + [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "imcui_hip_select_desc_bytes": (C.c_size_t, []),
+    "imcui_hip_select_desc_check": (C.c_int, [C.c_void_p]),
+    "imcui_hip_select_probe": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "imcui_hip_superpoint_select_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
+    "imcui_hip_superpoint_select_probe": (
+        C.c_int,
+        [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_void_p, C.c_size_t, C.c_void_p],
+    ),
+    "imcui_hip_disk_select_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
+    "imcui_hip_disk_select_probe": (
+        C.c_int,
+        [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_void_p, C.c_size_t, C.c_void_p],
+    ),
 }
 
 

@@ -1189,6 +1189,88 @@ int imcui_hip_ffn_last_route(const imcui_hip_t* h);
 int imcui_hip_ffn_route_counts(const imcui_hip_t* h, int* out, int n);
 int imcui_hip_ffn_route_reset(imcui_hip_t* h);
 
+/* ---- test entry into the list-building blocks of csrc/select.h (tests/test_gpu_select.py) --------------------------------------
+ * One op = one block (or the chain of blocks its callers launch together) with the template arguments the tree uses, on arrays GIVEN
+ * by the caller.  The blocks are templates in an anonymous namespace: this entry runs the copy compiled into csrc/select_probe.hip, i.e.
+ * it tests the SOURCE of select.h, not the copies compiled into each owner (those are reached by the stage probes below and by the
+ * network tests).  Device pointers unless said otherwise; unset fields zero.  B images / rows (1 .. IMCUI_SELECT_MAXB); `capacity` =
+ * elements per row of every per-row array (the row stride).
+ *  op 0 COMPACT   cand_count_kernel -> exclusive_scan_kernel<int> -> cand_compact_kernel<., EmitScoreIndex>, predicate
+ *                 score[b][i] > thr[b] with bind(b) fetching thr[b].  n = pixels per image (>= 1), score [B][n], thr [B],
+ *                 cap <= capacity = the list's cap.  out_score / out_idx [B][capacity] (written below min(count, cap)), out_count [B]
+ *                 (the true count), out_aux / out_i32 [B][cdiv(n, 4096)] chunk counts / offsets.
+ *  op 1 SCAN      exclusive_scan_kernel<int> of in_i32 [B][capacity] -> out_i32 (may be in_i32: in place), out_count [B] totals;
+ *                 n = n_cap <= capacity, n_dev [B] optional.
+ *  op 2 ORDER_KEY out_key32[i] = order_key(score[i]), i < n <= capacity.
+ *  op 3 KTH32     radix_select_kth<1024, unsigned> over order_key(score[b][i]), one workgroup per row, i < n_row[b], k_row[b]-th
+ *                 largest -> out_key32 [B], out_count [B] = n_equal.
+ *  op 4 KTH64     radix_select_kth<1024, unsigned long long> over key64 [B][capacity] -> out_key64 [B], out_count [B].
+ *  op 5 RANK4, 6 RANK16   block_ordered_rank<4> (256 threads) / <16> (1024 threads) over the flags in_i32 [b][0 .. n_row[b]) walked in
+ *                 batches with the running base in a register -> out_idx [b][i] = position of flagged entry i, out_count [B] totals.
+ *  op 7 KEEP      keep_kth_in_order over key64 [b][0 .. n_row[b]) with `filter`, `kth`, `limit` -> out_idx [b][0 .. limit),
+ *                 out_count [B] = the returned count (not clamped).
+ *  op 8 CUT       zero_i32_kernel (base, status), advance_base_kernel once per level with the counts in_i32 [nlev][B] (nlev >= 2),
+ *                 cand_cut_kernel on score [B][capacity] (capacity = kcap) with limit_ = `limit`, then kept_rank_ascending from a
+ *                 256-thread kernel -> out_idx = kslot [B][capacity], out_count = nkept [B], out_aux = base [B] (the summed counts),
+ *                 out_i32 = rank [B][capacity] (written below nkept), status [1]. */
+#define IMCUI_SELECT_MAXB 8
+typedef struct imcui_hip_select_desc {
+    int op;
+    int B;
+    int n;
+    int capacity;
+    int cap;
+    int limit;
+    int filter;
+    int nlev;
+    int n_row[IMCUI_SELECT_MAXB]; /* host values */
+    int k_row[IMCUI_SELECT_MAXB]; /* host values */
+    unsigned long long kth;
+    const float* score;
+    const float* thr;
+    const unsigned long long* key64;
+    const int* in_i32;
+    const int* n_dev;
+    float* out_score;
+    int* out_idx;
+    int* out_count;
+    int* out_i32;
+    int* out_aux;
+    unsigned* out_key32;
+    unsigned long long* out_key64;
+    int* status;
+} imcui_hip_select_desc;
+/* Host-only check of a descriptor, the one the probe makes before it launches anything: 0 = fine, else the first violated rule:
+ * 1 op outside 0 .. 8; 2 B outside 1 .. IMCUI_SELECT_MAXB; 3 capacity outside 1 .. 2^24, n outside 0 .. capacity (COMPACT: n outside
+ * 1 .. 2^24), an n_row[b] outside 0 .. capacity; 4 a k_row[b] outside 1 .. n_row[b] (KTH32, KTH64); 5 cap < 0 or cap > capacity
+ * (COMPACT), limit < 0 (KEEP, CUT); 6 a null pointer among those the op reads or writes; 7 nlev outside 2 .. 16 (CUT).  A null
+ * descriptor is rule 6. */
+int imcui_hip_select_desc_check(const imcui_hip_select_desc* d);
+/* A null handle or a descriptor that fails the check is IMCUI_HIP_ERR_ARG; nothing is launched by a refused call. */
+int imcui_hip_select_probe(imcui_hip_t* h, const imcui_hip_select_desc* d, void* stream);
+size_t imcui_hip_select_desc_bytes(void);
+
+/* ---- test entries into two rule stages, entered through the launcher their `forward` calls ---------------------------------------
+ * SuperPoint's "a5: select": status memset, candidate count / scan / compact (nms > threshold inside the border band, 64-bit keys) and
+ * sp_topk_kernel, on a post-NMS map nms [dev, B,H,W] GIVEN by the caller.  cand_cap = room of the candidate list per image (`forward`
+ * uses H * W).  Outputs as imcui_hip_superpoint_forward: keypoints [dev, B,kcap,2], scores [dev, B,kcap], num_keypoints [dev, B],
+ * status [dev, 1] (1 = more candidates than cand_cap, 2 = more key-points than kcap, 4 = a top-k above 16384; a count under status 4 is
+ * zero).  Slots past the count are not written.  Unlike `forward` the probe does not refuse max_keypoints > 16384 on the host, so that
+ * the device's status-4 branch can be reached (it returns before any on-chip memory is touched).  H, W >= 1 with H * W <= 2^24,
+ * 1 <= B <= 1024, kcap >= 1, cand_cap >= 1, null pointers and a short workspace are refused before anything is launched. */
+size_t imcui_hip_superpoint_select_workspace_bytes(int B, int H, int W, int cand_cap);
+int imcui_hip_superpoint_select_probe(imcui_hip_t* h, const float* nms, int B, int H, int W, float keypoint_threshold, int remove_borders,
+                                      int max_keypoints, int kcap, int cand_cap, float* keypoints, float* scores, int* num_keypoints,
+                                      int* status, void* ws, size_t ws_bytes, void* stream);
+/* DISK's detection stage: status memset, candidate count / scan / compact (the window NMS and the strict threshold of `forward`) and
+ * dk_select_kernel, on a heat map heat [dev, B,H,W] GIVEN by the caller.  ccap = room of the candidate list per image (`forward` uses
+ * H * W).  Outputs as imcui_hip_disk_forward without the descriptors (zero past the count; status 2 = more key-points than kcap).
+ * window odd >= 1, otherwise the refusals of the SuperPoint entry. */
+size_t imcui_hip_disk_select_workspace_bytes(int B, int H, int W, int ccap);
+int imcui_hip_disk_select_probe(imcui_hip_t* h, const float* heat, int B, int H, int W, int window, float threshold, int max_keypoints, int kcap,
+                                int ccap, float* keypoints, float* scores, int* num_keypoints, int* status, void* ws, size_t ws_bytes,
+                                void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,6 +21,24 @@ pytestmark = pytest.mark.gpu
 SD = superpoint_state_dict(0)
 
 
+def _assert_deterministic_selection(out, b, full, w):
+    """The key-points and scores of image b equal the exact rule of tests/select_reference.py (ties at the cut to the lower flat index,
+    order by (score bits descending, index ascending)) applied to the HIP post-NMS map: what an exact score tie at the cut leaves open
+    in the oracle's top-k is decided here."""
+    import numpy as np
+    import select_reference as R
+
+    from imcui_hip import backend
+
+    nms = backend.simple_nms(out["score_map"][b : b + 1], full["nms_radius"])[0].cpu().numpy()
+    kcap = out["scores"].shape[1]
+    idx, sb, k, _ = R.superpoint_select(nms, full["keypoint_threshold"], full["remove_borders"], full["max_keypoints"], kcap)
+    assert int(out["num_keypoints"][b]) == k
+    kp = out["keypoints"][b, :k].cpu().numpy()
+    assert np.array_equal((kp[:, 1] * w + kp[:, 0]).astype(np.int64), idx), "membership / order under the deterministic tie rule"
+    assert np.array_equal(R.bits(out["scores"][b, :k].cpu().numpy()), sb)
+
+
 def _model(conf):
     from imcui_hip.hloc.extractors.superpoint import SuperPoint
 
@@ -62,6 +80,7 @@ def test_superpoint_vs_oracle(h, w, conf, precision):
             else:
                 assert torch.equal(flat_hip, flat_sel), "row-major candidate order"
             assert torch.equal(sc, sc_sel)
+        _assert_deterministic_selection(out, b, full, w)  # (with or without a tie at the cut)
         # (3) end-to-end vs the pure oracle: same key-points up to round-off ties
         kp_ref = ref["keypoints"][0]
         flat_ref = (kp_ref[:, 1] * w + kp_ref[:, 0]).long()
@@ -107,6 +126,18 @@ def test_superpoint_flat_image_is_handled():
     with torch.no_grad():
         pred = model({"image": torch.full((1, 1, 64, 96), 0.5).cuda()})
     assert pred["keypoints"][0].shape[0] <= 200
+    # the exact expected list: the deterministic rule on the HIP post-NMS map of the same image
+    import numpy as np
+    import select_reference as R
+
+    from imcui_hip import backend
+
+    out = model.forward_batched(torch.full((1, 1, 64, 96), 0.5).cuda(), want_score_map=True)
+    nms = backend.simple_nms(out["score_map"], model.conf["nms_radius"])[0].cpu().numpy()
+    idx, sb, k, _ = R.superpoint_select(nms, model.conf["keypoint_threshold"], model.conf["remove_borders"], 200, 200)
+    kp = pred["keypoints"][0].cpu().numpy()
+    assert kp.shape[0] == k
+    assert np.array_equal((kp[:, 1] * 96 + kp[:, 0]).astype(np.int64), idx) and np.array_equal(R.bits(pred["scores"][0].cpu().numpy()), sb)
 
 
 def test_superpoint_large_topk_and_rejects_oversize():
@@ -129,6 +160,7 @@ def test_superpoint_large_topk_and_rejects_oversize():
     if not tie:
         assert torch.equal((kp[:, 1] * 640 + kp[:, 0]).long(), flat_sel)
         assert torch.equal(out["scores"][0, :n].cpu(), sc_sel)
+    _assert_deterministic_selection(out, 0, full, 640)  # (with or without a tie at the cut)
     model.conf["max_keypoints"] = 20000
     with pytest.raises(ImcuiHipError, match="top-k sorter"):
         model.forward_batched(img0.cuda())
