@@ -977,6 +977,211 @@ class D2NetHIP:
         return out
 
 
+# ------------------------------------------------------------------ LANet
+LANET_DIM = 256
+LANET_MIN_SIDE = 8  # one 8 x 8 cell
+LANET_ACTIVATIONS = {"relu": 1, "leaky_relu": 2}
+LANET_LAYERS = ("1a", "1b", "2a", "2b", "3a", "3b", "4a", "4b", "Da", "Pa")  # the BatchNorm'd 3x3 layers: trunk, score / location head
+_BN_KEYS = ("weight", "bias", "running_mean", "running_var")
+
+
+def lanet_config(sd: dict, activation: str = "relu") -> dict:
+    """What a LANet state dict (under the library's names, `lanet_tensor_names`) decides: widths, kernel size / bias / BatchNorm of the
+    two level convolutions, bias on the BatchNorm'd convolutions.  Nothing is guessed: a missing key or an unexpected shape raises."""
+    if activation not in LANET_ACTIVATIONS:
+        raise ImcuiHipError(f"LANet: activation '{activation}' is not served ({', '.join(LANET_ACTIVATIONS)})")
+
+    def shape(name, ndim):
+        if name not in sd:
+            raise ImcuiHipError(f"LANet state dict: '{name}' is missing")
+        s = tuple(sd[name].shape)
+        if len(s) != ndim:
+            raise ImcuiHipError(f"LANet state dict: '{name}' has shape {s}, expected {ndim} dimensions")
+        return s
+
+    widths = tuple(shape(f"conv{i}b.weight", 4)[0] for i in (1, 2, 3, 4))
+    for c in widths:
+        if c % 32 or not 32 <= c <= 512:
+            raise ImcuiHipError(f"LANet: trunk widths {widths} must be multiples of 32 (up to 512)")
+    if widths[3] != LANET_DIM:
+        raise ImcuiHipError(f"LANet: c4={widths[3]}, but level 4 of the descriptor is x4 itself and has to be {LANET_DIM} wide")
+    ks = []
+    for lvl in (2, 3):
+        s = shape(f"des_conv{lvl}.weight", 4)
+        if s[2] != s[3] or s[2] not in (1, 3):
+            raise ImcuiHipError(f"LANet: des_conv{lvl}.weight has shape {s}: the kernel must be 1x1 or 3x3")
+        ks.append(s[2])
+    return {"widths": widths, "k": tuple(ks), "bias": tuple(int(f"des_conv{l}.bias" in sd) for l in (2, 3)),
+            "bn": tuple(int(f"des_bn{l}.weight" in sd) for l in (2, 3)), "activation": activation, "conv_bias": int("conv1a.bias" in sd)}  # fmt: skip
+
+
+def lanet_cfg_array(cfg: dict):
+    """The 12 ints of include/imcui_hip.h's `cfg`."""
+    return (C.c_int * 12)(*cfg["widths"], *cfg["k"], *cfg["bias"], *cfg["bn"], LANET_ACTIVATIONS[cfg["activation"]], cfg["conv_bias"])
+
+
+def lanet_tensor_names(cfg: dict) -> list[str]:
+    lib, ca = load_library(), lanet_cfg_array(cfg)
+    return [lib.imcui_hip_lanet_tensor_name(ca, i).decode() for i in range(lib.imcui_hip_lanet_num_tensors(ca))]
+
+
+def lanet_tensor_shapes(cfg: dict) -> dict:
+    c1, c2, c3, c4 = cfg["widths"]
+    shapes = {}
+    chans = {"1a": (3, c1), "1b": (c1, c1), "2a": (c1, c2), "2b": (c2, c2), "3a": (c2, c3), "3b": (c3, c3), "4a": (c3, c4), "4b": (c4, c4),
+             "Da": (c4, LANET_DIM), "Pa": (c4, LANET_DIM)}  # fmt: skip
+    for name in LANET_LAYERS:
+        cin, cout = chans[name]
+        shapes[f"conv{name}.weight"] = (cout, cin, 3, 3)
+        if cfg["conv_bias"]:
+            shapes[f"conv{name}.bias"] = (cout,)
+        for k in _BN_KEYS:
+            shapes[f"bn{name}.{k}"] = (cout,)
+    shapes["convDb.weight"], shapes["convDb.bias"] = (4, LANET_DIM, 3, 3), (4,)
+    shapes["convPb.weight"], shapes["convPb.bias"] = (2, LANET_DIM, 3, 3), (2,)
+    for i, (lvl, cin) in enumerate(((2, c2), (3, c3))):
+        shapes[f"des_conv{lvl}.weight"] = (LANET_DIM, cin, cfg["k"][i], cfg["k"][i])
+        if cfg["bias"][i]:
+            shapes[f"des_conv{lvl}.bias"] = (LANET_DIM,)
+        if cfg["bn"][i]:
+            for k in _BN_KEYS:
+                shapes[f"des_bn{lvl}.{k}"] = (LANET_DIM,)
+    return shapes
+
+
+def pack_lanet(state_dict: dict, activation: str = "relu"):
+    """LANet state dict under the library's names (the plugin maps a checkpoint's keys) -> (packed float32 buffer (host), cfg).  BatchNorm
+    (eval) is folded by the packer.  Strict: `num_batches_tracked` counters are ignored, every other key is consumed exactly once and
+    every shape checked; an unknown or missing key raises."""
+    lib = load_library()
+    sd = {k: t for k, t in state_dict.items() if not k.endswith("num_batches_tracked")}
+    cfg = lanet_config(sd, activation)
+    ca = lanet_cfg_array(cfg)
+    n = lib.imcui_hip_lanet_packed_floats(ca)
+    if n == 0:
+        raise ImcuiHipError(f"LANet: the library refuses the configuration {cfg}")
+    return _pack_named("LANet", "the PointModel (network_v0)", lanet_tensor_names(cfg), lanet_tensor_shapes(cfg), sd, n, lib.imcui_hip_lanet_pack_weights, ca), cfg
+
+
+def lanet_check_args(image_shape, max_keypoints: int = 0) -> None:
+    """Refusals raised before anything is launched."""
+    if len(image_shape) != 4 or image_shape[1] != 3:
+        raise ValueError(f"LANet expects an RGB image [B,3,H,W], got shape {tuple(image_shape)}")
+    if image_shape[2] < LANET_MIN_SIDE or image_shape[3] < LANET_MIN_SIDE:
+        raise ValueError(f"LANet needs images of at least {LANET_MIN_SIDE} x {LANET_MIN_SIDE} (one cell), got {tuple(image_shape[2:])}")
+    if int(max_keypoints) < 0:  # (the reference's slice `[-k or None:]` would silently DROP the |k| lowest scores)
+        raise ValueError(f"LANet: max_keypoints={max_keypoints} is negative; 0 keeps every key-point")
+
+
+class LanetHIP:
+    def __init__(self, cfg: dict):
+        self.cfg = cfg
+        self._ca = lanet_cfg_array(cfg)
+        self._ws = _Workspace()
+
+    def forward(self, packed: torch.Tensor, image: torch.Tensor, conf: dict, want_maps: bool = False):
+        """image [B,3,H,W] float32 RGB in [0,1] on the GPU -> fixed-stride outputs, no host synchronisation: keypoints [B,K,2] (x, y in
+        pixels), scores [B,K], descriptors [B,K,256], num_keypoints [B] int32, status [1] int32 (always 0), rows in ascending (score,
+        cell) order, rows past the count zero.  K = min(max_keypoints or all, cells).  want_maps adds x2 / x3 / x4 (NHWC) and the per-cell
+        cell_score [B,Hc*Wc], cell_coord / cell_tanh [B,Hc*Wc,2], cell_aware [B,Hc*Wc,3]."""
+        maxk = int(conf["max_keypoints"] or 0)
+        lanet_check_args(tuple(image.shape), maxk)
+        hd = get_handle(image.device)
+        _same_device(packed, image)
+        lib = hd.lib
+        image = image.contiguous().float()
+        B, _, H, W = image.shape
+        dev = image.device
+        np_ = (H // 8) * (W // 8)
+        kout = np_ if maxk == 0 else min(maxk, np_)
+        kpts, scores, desc, nk, status, out = _sparse_outputs(B, kout, LANET_DIM, dev)
+        maps = {}
+        if want_maps:
+            f32 = dict(dtype=torch.float32, device=dev)
+            c2, c3 = self.cfg["widths"][1:3]
+            maps = dict(x2=torch.empty((B, H // 2, W // 2, c2), **f32), x3=torch.empty((B, H // 4, W // 4, c3), **f32),
+                        x4=torch.empty((B, H // 8, W // 8, LANET_DIM), **f32), cell_score=torch.empty((B, np_), **f32),
+                        cell_coord=torch.empty((B, np_, 2), **f32), cell_aware=torch.empty((B, np_, 3), **f32), cell_tanh=torch.empty((B, np_, 2), **f32))  # fmt: skip
+        with self._ws.use(lib.imcui_hip_lanet_workspace_bytes(self._ca, B, H, W, kout), dev) as ws:
+            hd.launch(
+                lib.imcui_hip_lanet_forward, self._ca, _ptr(packed), _ptr(image), B, H, W, float(conf["keypoint_threshold"]), maxk, kout, _ptr(kpts),
+                _ptr(scores), _ptr(desc), _ptr(nk), _ptr(status), _ptr(maps.get("x2")), _ptr(maps.get("x3")), _ptr(maps.get("x4")),
+                _ptr(maps.get("cell_score")), _ptr(maps.get("cell_coord")), _ptr(maps.get("cell_aware")), _ptr(maps.get("cell_tanh")), _ptr(ws), ws.numel(),
+            )  # fmt: skip
+        out.update(maps)
+        return out
+
+    def stem_probe(self, packed: torch.Tensor, image: torch.Tensor) -> torch.Tensor:
+        """Test entry: conv1a with the normalisation, image [B,3,H,W] -> [B,H,W,c1]."""
+        hd = get_handle(image.device)
+        image = image.contiguous().float()
+        B, _, H, W = image.shape
+        out = torch.empty((B, H, W, self.cfg["widths"][0]), dtype=torch.float32, device=image.device)
+        scratch = torch.empty((B, H, W, 32), dtype=torch.float32, device=image.device)
+        hd.launch(hd.lib.imcui_hip_lanet_stem_probe, self._ca, _ptr(packed), _ptr(image), B, H, W, _ptr(out), _ptr(scratch))
+        return out
+
+    def tail_probe(self, packed: torch.Tensor, s1: torch.Tensor, p1: torch.Tensor, H: int, W: int) -> dict:
+        """Test entry: the two tails and the decode on hidden maps s1, p1 [B,Hc,Wc,256] of an H x W image."""
+        hd = get_handle(s1.device)
+        s1, p1 = s1.contiguous().float(), p1.contiguous().float()
+        B, Hc, Wc, _ = s1.shape
+        f32 = dict(dtype=torch.float32, device=s1.device)
+        o = dict(cell_score=torch.empty((B, Hc * Wc), **f32), cell_coord=torch.empty((B, Hc * Wc, 2), **f32), cell_tanh=torch.empty((B, Hc * Wc, 2), **f32),
+                 cell_aware=torch.empty((B, Hc * Wc, 3), **f32))  # fmt: skip
+        hd.launch(hd.lib.imcui_hip_lanet_tail_probe, self._ca, _ptr(packed), _ptr(s1), _ptr(p1), B, Hc, Wc, H, W, _ptr(o["cell_score"]), _ptr(o["cell_coord"]),
+                  _ptr(o["cell_tanh"]), _ptr(o["cell_aware"]))  # fmt: skip
+        return o
+
+    def select_probe(self, raw: torch.Tensor, H: int, W: int, threshold: float, max_keypoints: int = 0) -> dict:
+        """Test entry: decode and selection from head outputs raw [B,Hc,Wc,6] (score head 0..3, location head 4..5) of an H x W image."""
+        lanet_check_args((raw.shape[0], 3, H, W), max_keypoints)
+        hd = get_handle(raw.device)
+        lib = hd.lib
+        raw = raw.contiguous().float()
+        B, Hc, Wc, _ = raw.shape
+        np_, maxk, dev = Hc * Wc, int(max_keypoints), raw.device
+        kout = np_ if maxk == 0 else min(maxk, np_)
+        f32 = dict(dtype=torch.float32, device=dev)
+        kpts, scores, _, nk, status, out = _sparse_outputs(B, kout, 1, dev)
+        out.pop("descriptors")
+        o = dict(cell_score=torch.empty((B, np_), **f32), cell_coord=torch.empty((B, np_, 2), **f32), cell_aware=torch.empty((B, np_, 3), **f32),
+                 cell_tanh=torch.empty((B, np_, 2), **f32))  # fmt: skip
+        with self._ws.use(lib.imcui_hip_lanet_select_workspace_bytes(B, Hc, Wc, kout), dev) as ws:
+            hd.launch(lib.imcui_hip_lanet_select_probe, _ptr(raw), B, Hc, Wc, H, W, float(threshold), maxk, kout, _ptr(kpts), _ptr(scores), _ptr(nk), _ptr(status),
+                      _ptr(o["cell_score"]), _ptr(o["cell_coord"]), _ptr(o["cell_aware"]), _ptr(o["cell_tanh"]), _ptr(ws), ws.numel())  # fmt: skip
+        out.update(o)
+        return out
+
+    def desc_probe(self, packed: torch.Tensor, x2: torch.Tensor, x3: torch.Tensor, x4: torch.Tensor, H: int, W: int, coords: torch.Tensor,
+                   aware: torch.Tensor) -> torch.Tensor:
+        """Test entry: the sparse descriptor head of ONE image at positions coords [n,2] (pixels of the H x W image) with level weights
+        aware [n,3], from maps x2 [h2,w2,c2], x3 [h3,w3,c3], x4 [h4,w4,256] (NHWC) -> [n,256]."""
+        hd = get_handle(x2.device)
+        x2, x3, x4 = x2.contiguous().float(), x3.contiguous().float(), x4.contiguous().float()
+        coords, aware = coords.contiguous().float(), aware.contiguous().float()
+        c2, c3 = self.cfg["widths"][1:3]
+        if x2.shape[-1] != c2 or x3.shape[-1] != c3 or x4.shape[-1] != LANET_DIM or coords.shape[0] != aware.shape[0] or coords.shape[0] < 1:
+            raise ValueError("desc_probe: map widths or the number of positions do not match")
+        n = coords.shape[0]
+        desc = torch.empty((n, LANET_DIM), dtype=torch.float32, device=x2.device)
+        hd.launch(hd.lib.imcui_hip_lanet_desc_probe, self._ca, _ptr(packed), _ptr(x2), x2.shape[0], x2.shape[1], _ptr(x3), x3.shape[0], x3.shape[1], _ptr(x4),
+                  x4.shape[0], x4.shape[1], H, W, _ptr(coords), _ptr(aware), n, _ptr(desc))  # fmt: skip
+        return desc
+
+    def dense_levels(self, packed: torch.Tensor, x2: torch.Tensor, x3: torch.Tensor):
+        """Test entry: des_conv2(x2) and des_conv3(x3) as dense maps on the shared GEMM, x2 [B,h2,w2,c2], x3 [B,h3,w3,c3] (NHWC) ->
+        ([B,h2,w2,256], [B,h3,w3,256]).  The forward never runs this form."""
+        hd = get_handle(x2.device)
+        x2, x3 = x2.contiguous().float(), x3.contiguous().float()
+        B, h2, w2, _ = x2.shape
+        _, h3, w3, _ = x3.shape
+        d2 = torch.empty((B, h2, w2, LANET_DIM), dtype=torch.float32, device=x2.device)
+        d3 = torch.empty((B, h3, w3, LANET_DIM), dtype=torch.float32, device=x2.device)
+        hd.launch(hd.lib.imcui_hip_lanet_dense_levels, self._ca, _ptr(packed), _ptr(x2), B, h2, w2, _ptr(x3), h3, w3, _ptr(d2), _ptr(d3))
+        return d2, d3
+
+
 # ------------------------------------------------------------------ NetVLAD
 # (cin, cout, index in torchvision's vgg16().features): VGG-16 to conv5_3, csrc/netvlad.hip
 NETVLAD_LAYERS = ((3, 64, 0), (64, 64, 2), (64, 128, 5), (128, 128, 7), (128, 256, 10), (256, 256, 12), (256, 256, 14), (256, 512, 17), (512, 512, 19),

@@ -66,6 +66,12 @@ confs = {
         "model": {"name": "dog", "descriptor": "hardnet", "max_keypoints": 5000},
         "preprocessing": {"grayscale": True, "resize_max": 1600, "force_resize": True, "width": 640, "height": 480, "dfactor": 8},
     },
+    # imcui/hloc/configs/extractors.py:288-299: LANet (the `lanet` plugin), RGB
+    "lanet": {
+        "output": "feats-lanet-n5000-r1600",
+        "model": {"name": "lanet", "keypoint_threshold": 0.1, "max_keypoints": 5000},
+        "preprocessing": {"grayscale": False, "resize_max": 1600},
+    },
 }
 
 

@@ -101,6 +101,18 @@ SIGNATURES = {
     "imcui_hip_d2net_layer_probe": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_void_p]),
     "imcui_hip_d2net_probe_workspace_bytes": (C.c_size_t, [C.c_int] * 5),
     "imcui_hip_d2net_detect_probe": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 7 + [C.c_void_p] * 5 + [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "imcui_hip_lanet_packed_floats": (C.c_size_t, [C.c_void_p]),
+    "imcui_hip_lanet_num_tensors": (C.c_int, [C.c_void_p]),
+    "imcui_hip_lanet_tensor_name": (C.c_char_p, [C.c_void_p, C.c_int]),
+    "imcui_hip_lanet_pack_weights": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p]),
+    "imcui_hip_lanet_workspace_bytes": (C.c_size_t, [C.c_void_p] + [C.c_int] * 4),
+    "imcui_hip_lanet_forward": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_float] + [C.c_int] * 2 + [C.c_void_p] * 12 + [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "imcui_hip_lanet_stem_probe": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_void_p] * 3),
+    "imcui_hip_lanet_tail_probe": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 5 + [C.c_void_p] * 5),
+    "imcui_hip_lanet_select_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
+    "imcui_hip_lanet_select_probe": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 5 + [C.c_float] + [C.c_int] * 2 + [C.c_void_p] * 8 + [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "imcui_hip_lanet_desc_probe": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 2 + [C.c_void_p] + [C.c_int] * 2 + [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 2 + [C.c_int] + [C.c_void_p] * 2),
+    "imcui_hip_lanet_dense_levels": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_void_p] + [C.c_int] * 2 + [C.c_void_p] * 3),
     "imcui_hip_dedode_packed_floats": (C.c_size_t, [C.c_void_p]),
     "imcui_hip_dedode_num_tensors": (C.c_int, [C.c_void_p]),
     "imcui_hip_dedode_tensor_name": (C.c_char_p, [C.c_void_p, C.c_int]),

@@ -978,3 +978,72 @@ def hardnet_synth_state(seed: int = 0) -> dict:
 def sosnet_synth_state(seed: int = 0) -> dict:
     """The same for kornia.feature.SOSNet (`layers.N.*`; `layers.0` is the parameter-free InstanceNorm2d)."""
     return _patchdesc_synth_state(seed, "layers", SOSNET_CONV_OPS)
+
+
+LANET_WIDTHS = (32, 64, 128, 256)
+LANET_PREFIX = "interestpoint_module."
+
+
+def lanet_synth_state(seed: int = 0, k: int = 3, bias: bool = True, bn: bool = False, widths=LANET_WIDTHS, conv_bias: bool = False,
+                      score_gain: float = 2.0, loc_gain: float = 0.6, aware_gain: float = 0.5) -> dict:
+    """Seeded LANet (network_v0 PointModel) weights under the key names tests/lanet_reference.py restates (`interestpoint_module.*`,
+    the `num_batches_tracked` counters included, a loader has to skip them).  Convolutions are He-initialised, BatchNorm statistics are
+    away from (0, 1).  The two tails see ReLU outputs, all positive and growing with depth, so a plain draw leaves their outputs far
+    from zero: every tail row is calibrated on a seeded 64 x 64 uniform image (drawn from the same generator, evaluated here with
+    torch's own convolutions) to zero mean and a chosen standard deviation -- `score_gain` spreads the sigmoid over (0, 1), `loc_gain`
+    keeps the tanh out of saturation on most cells, `aware_gain` keeps the three level weights well away from one-hot
+    (tests/test_lanet_cpu.py asserts the three).  `k`, `bias`, `bn`: the kernel size of des_conv2 / des_conv3, whether they carry a bias, whether a BatchNorm follows."""
+    c1, c2, c3, c4 = widths
+    g = torch.Generator().manual_seed(seed)
+    sd = {}
+    p = LANET_PREFIX
+
+    def rn(*shape, scale=1.0):
+        return torch.randn(*shape, generator=g) * scale
+
+    def conv(name, cout, cin, kk, gain=math.sqrt(2.0), with_bias=False):
+        sd[f"{p}{name}.weight"] = rn(cout, cin, kk, kk, scale=gain / math.sqrt(cin * kk * kk))
+        if with_bias:
+            sd[f"{p}{name}.bias"] = 0.1 * rn(cout)
+
+    def norm(name, c):
+        sd[f"{p}{name}.weight"] = 1.0 + 0.2 * rn(c)
+        sd[f"{p}{name}.bias"] = 0.1 * rn(c)
+        sd[f"{p}{name}.running_mean"] = 0.2 * rn(c)
+        sd[f"{p}{name}.running_var"] = 0.5 + torch.rand(c, generator=g)
+        sd[f"{p}{name}.num_batches_tracked"] = torch.tensor(1000, dtype=torch.long)
+
+    for name, cin, cout in (("1a", 3, c1), ("1b", c1, c1), ("2a", c1, c2), ("2b", c2, c2), ("3a", c2, c3), ("3b", c3, c3), ("4a", c3, c4), ("4b", c4, c4),
+                            ("Da", c4, 256), ("Pa", c4, 256)):  # fmt: skip
+        conv("conv" + name, cout, cin, 3, gain=2.0 * math.sqrt(2.0) if name == "1a" else math.sqrt(2.0), with_bias=conv_bias)
+        norm("bn" + name, cout)
+
+    # the hidden maps of the two heads on a seeded 64 x 64 uniform image, with the weights drawn so far (eval BatchNorm, ReLU)
+    import torch.nn.functional as F
+
+    def layer(name, x):
+        x = F.conv2d(x, sd[f"{p}conv{name}.weight"], sd.get(f"{p}conv{name}.bias"), padding=1)
+        x = F.batch_norm(x, sd[f"{p}bn{name}.running_mean"], sd[f"{p}bn{name}.running_var"], sd[f"{p}bn{name}.weight"], sd[f"{p}bn{name}.bias"], False, 0.0, 1e-5)
+        return F.relu(x)
+
+    x = (torch.rand(1, 3, 64, 64, generator=g) - 0.5) / 0.225
+    for name in ("1a", "1b", "2a", "2b", "3a", "3b", "4a", "4b"):
+        x = layer(name, x)
+        if name in ("1b", "2b", "3b"):
+            x = F.max_pool2d(x, 2, 2)
+
+    def tail(name, hidden, stds):
+        w = rn(len(stds), 256, 3, 3, scale=1.0 / math.sqrt(256 * 9))
+        raw = F.conv2d(hidden, w, None, padding=1)[0]
+        mean, std = raw.mean(dim=(1, 2)), raw.std(dim=(1, 2))
+        scale = torch.tensor(stds) / std
+        sd[f"{p}{name}.weight"] = w * scale.view(-1, 1, 1, 1)
+        sd[f"{p}{name}.bias"] = -mean * scale + 0.05 * rn(len(stds))
+
+    tail("convDb", layer("Da", x), [aware_gain] * 3 + [score_gain])
+    tail("convPb", layer("Pa", x), [loc_gain] * 2)
+    for lvl, cin in ((2, c2), (3, c3)):
+        conv(f"des_conv{lvl}", 256, cin, k, gain=1.0, with_bias=bias)
+        if bn:
+            norm(f"des_bn{lvl}", 256)
+    return sd

@@ -306,6 +306,58 @@ int imcui_hip_d2net_detect_probe(imcui_hip_t* h, const float* feat, int B, int f
                                  float* keypoints, float* scores, float* descriptors, int* num_keypoints, int* status, void* ws, size_t ws_bytes,
                                  void* stream);
 
+/* ---- LANet (zoo entry lanet: `feature: lanet` + NN-mutual; imcui/hloc/extractors/lanet.py) ------------------------------ */
+/* lanet.network_v0.model.PointModel(is_test=True) (replaces lanet.py:34-36) is not part of the reference checkout: the network is
+ * restated from its description (tests/lanet_reference.py) and parity with upstream's code is NOT pinned.  What the
+ * checkpoint decides is READ from it by the binding and handed over as cfg [host, 12 ints]:
+ *   c1, c2, c3, c4 (multiples of 32; c4 = 256), k of des_conv2 and of des_conv3 (1 or 3), bias present on des_conv2 / des_conv3,
+ *   BatchNorm present behind des_conv2 / des_conv3, activation (1 ReLU, 2 LeakyReLU(0.01)), bias on the convolutions in front of a
+ *   BatchNorm.
+ * The packed buffer starts with a 64-float header: magic, the 12 values, Normalize's mean (0.5) and std (0.225).  Tensors in
+ * imcui_hip_lanet_tensor_name order, under this library's own names (conv1a .. conv4b / bn1a .. bn4b, convDa / bnDa / convDb: the score
+ * head, convPa / bnPa / convPb: the location head, des_conv2 / des_bn2, des_conv3 / des_bn3); the plugin maps a checkpoint's keys. */
+size_t imcui_hip_lanet_packed_floats(const int* cfg);
+int imcui_hip_lanet_num_tensors(const int* cfg);
+const char* imcui_hip_lanet_tensor_name(const int* cfg, int i);
+int imcui_hip_lanet_pack_weights(const int* cfg, const float* const* tensors, float* packed);
+/* Scratch of imcui_hip_lanet_forward: B images of H x W (H, W >= 8), kout output rows per image. */
+size_t imcui_hip_lanet_workspace_bytes(const int* cfg, int B, int H, int W, int kout);
+/* lanet.py:39-63 `_forward` around `self.net(image)`: image [dev, B,3,H,W] RGB in [0,1].  Cells of 8 x 8 pixels, Hc x Wc = H/8 x W/8 in
+ * row-major order; per cell score = sigmoid (0 on the first / last row and column), position = (c * 8 + 3.5) + tanh * 7.0 clamped to
+ * the image, level weights = soft-max of three channels.  A cell is kept when score > threshold (:49-50, strict); more than
+ * max_keypoints (> 0; 0 = all, :54 `or None`; negative refused): the highest scores stay, among equal scores the later cells; output
+ * in ASCENDING (score, cell) order, a STABLE form of :54's argsort (torch.argsort leaves ties open).  descriptor = the three levels
+ * des_conv2(x2), des_conv3(x3), x4 sampled bilinearly at the key-point (F.grid_sample defaults), weighted, divided by the norm -- the two
+ * level convolutions are evaluated at the key-points only.  kout >= min(max_keypoints or all cells, Hc Wc).  Outputs, first
+ * num_keypoints[b] rows valid, the rest zero:
+ *   keypoints [dev, B,kout,2] (x, y);  scores [dev, B,kout];  descriptors [dev, B,kout,256];  num_keypoints [dev, B] int32
+ *   status [dev, 1] int32 optional: always 0 (the candidate list holds every cell)
+ *   optional debug outputs: dbg_x2 [B,H/2,W/2,c2], dbg_x3 [B,H/4,W/4,c3], dbg_x4 [B,Hc,Wc,256], dbg_score [B,Hc Wc], dbg_coord and
+ *   dbg_tanh [B,Hc Wc,2], dbg_aware [B,Hc Wc,3]
+ * Zero key-points is a valid result.  No host synchronisation; a row's bits do not depend on the batch. */
+int imcui_hip_lanet_forward(imcui_hip_t* h, const int* cfg, const float* packed, const float* image, int B, int H, int W, float threshold,
+                            int max_keypoints, int kout, float* keypoints, float* scores, float* descriptors, int* num_keypoints, int* status,
+                            float* dbg_x2, float* dbg_x3, float* dbg_x4, float* dbg_score, float* dbg_coord, float* dbg_aware, float* dbg_tanh,
+                            void* ws, size_t ws_bytes, void* stream);
+/* Test entries.  stem_probe: conv1a with the normalisation, image [dev, B,3,H,W] -> out [dev, B,H,W,c1]; scratch [dev, B,H,W,32] is
+ * needed when the layer runs on the GEMM (LeakyReLU, or c1 other than 32 / 64).  tail_probe: the two tails and the decode on given
+ * hidden maps s1, p1 [dev, B,Hc,Wc,256].  select_probe: decode and selection from given head outputs raw [dev, B,Hc Wc,6] (score head
+ * 0..3, location head 4..5); ws: imcui_hip_lanet_select_workspace_bytes.  desc_probe: the sparse descriptor head of ONE image at n
+ * given positions coords [dev, n,2] (pixels of the H x W image) and level weights aw [dev, n,3] from given maps -> [dev, n,256].
+ * dense_levels: des_conv2(x2) -> d2 [dev, B,h2,w2,256] and des_conv3(x3) -> d3 on the shared GEMM, the form the forward never runs. */
+int imcui_hip_lanet_stem_probe(imcui_hip_t* h, const int* cfg, const float* packed, const float* image, int B, int H, int W, float* out, float* scratch,
+                               void* stream);
+int imcui_hip_lanet_tail_probe(imcui_hip_t* h, const int* cfg, const float* packed, const float* s1, const float* p1, int B, int Hc, int Wc, int H, int W,
+                               float* score, float* coord, float* tanhv, float* aware, void* stream);
+size_t imcui_hip_lanet_select_workspace_bytes(int B, int Hc, int Wc, int kout);
+int imcui_hip_lanet_select_probe(imcui_hip_t* h, const float* raw, int B, int Hc, int Wc, int H, int W, float threshold, int max_keypoints, int kout,
+                                 float* keypoints, float* scores, int* num_keypoints, int* status, float* dbg_score, float* dbg_coord, float* dbg_aware,
+                                 float* dbg_tanh, void* ws, size_t ws_bytes, void* stream);
+int imcui_hip_lanet_desc_probe(imcui_hip_t* h, const int* cfg, const float* packed, const float* x2, int h2, int w2, const float* x3, int h3, int w3,
+                               const float* x4, int h4, int w4, int H, int W, const float* coords, const float* aw, int n, float* descriptors, void* stream);
+int imcui_hip_lanet_dense_levels(imcui_hip_t* h, const int* cfg, const float* packed, const float* x2, int B, int h2, int w2, const float* x3, int h3, int w3,
+                                 float* d2, float* d3, void* stream);
+
 /* ---- DeDoDe (zoo entry dedode: `feature: dedode` + Dual-Softmax; imcui/hloc/extractors/dedode.py) ----------------------- */
 /* dedode_detector_L (vgg19_bn encoder) and dedode_descriptor_B (vgg11_bn encoder) of Parskatt/DeDoDe, each with a decoder of four
  * ConvRefiners (scales 8, 4, 2, 1).  The refiners' shapes are READ from the checkpoint by the binding and handed over as
