@@ -1182,6 +1182,223 @@ class LanetHIP:
         return d2, d3
 
 
+# ------------------------------------------------------------------ DarkFeat
+DARKFEAT_DIM = 128
+DARKFEAT_MIN_SIDE = 16
+DARKFEAT_STATUS_FLAT = 4  # status bit: an image of the batch is flat (std == 0)
+# upstream's `det` config (THU-LYJ-Lab/DarkFeat; the reference's wrapper hands none of its conf to the network): backend-only conf keys
+DARKFEAT_DET_DEFAULTS = {"score_thld": 0.5, "edge_thld": 10, "nms_size": 3, "eof_mask": 5, "kpt_n": 5000}
+_DARKFEAT_DROPPED = ("running_mean", "running_var", "num_batches_tracked")  # upstream drops these before load_state_dict
+
+
+def darkfeat_layers() -> list[dict]:
+    """The backbone as the library's ONE table states it (csrc/darkfeat.hip, DF_LAYERS): name, cin, cout, stride, norm (InstanceNorm +
+    ReLU behind the convolution), tap (the score level its raw output feeds, -1 none)."""
+    lib = load_library()
+    out = []
+    for i in range(lib.imcui_hip_darkfeat_num_layers()):
+        v = (C.c_int * 5)()
+        name = lib.imcui_hip_darkfeat_layer(i, v).decode()
+        out.append({"name": name, "cin": v[0], "cout": v[1], "stride": v[2], "norm": bool(v[3]), "tap": v[4]})
+    return out
+
+
+def darkfeat_tensor_names() -> list[str]:
+    lib = load_library()
+    return [lib.imcui_hip_darkfeat_tensor_name(i).decode() for i in range(lib.imcui_hip_darkfeat_num_tensors())]
+
+
+def darkfeat_tensor_shapes() -> dict:
+    shapes = {}
+    for L in darkfeat_layers():
+        shapes[f"{L['name']}.0.weight"] = (L["cout"], L["cin"], 3, 3)
+        shapes[f"{L['name']}.0.bias"] = (L["cout"],)
+    shapes["clf.weight"], shapes["clf.bias"] = (2, DARKFEAT_DIM, 1, 1), (2,)
+    for i in range(3):
+        shapes[f"moving_avg_params.{i}"] = (1,)
+    return shapes
+
+
+def pack_darkfeat(state_dict: dict) -> torch.Tensor:
+    """DarkFeat state dict (upstream's keys: `convN.0.weight`, optional `convN.0.bias`, `clf.*`, `moving_avg_params.{0,1,2}`) -> packed
+    float32 buffer (host).  Strict: the BatchNorm-statistics keys upstream drops before loading (`running_mean`, `running_var`,
+    `num_batches_tracked`) are ignored, a convolution bias the checkpoint does not carry is zero, every other key is consumed exactly
+    once and every shape checked; an unknown or missing key raises."""
+    lib = load_library()
+    sd = {k: t for k, t in state_dict.items() if not k.endswith(_DARKFEAT_DROPPED)}
+    shapes = darkfeat_tensor_shapes()
+    for L in darkfeat_layers():
+        sd.setdefault(f"{L['name']}.0.bias", torch.zeros(L["cout"]))
+    for i in range(3):  # scalars: 0-d or [1]
+        k = f"moving_avg_params.{i}"
+        if k in sd:
+            sd[k] = torch.as_tensor(sd[k]).reshape(-1)
+    n = lib.imcui_hip_darkfeat_packed_floats()
+    if n == 0:
+        raise ImcuiHipError("DarkFeat: the library refuses its own layer table")
+    return _pack_named("DarkFeat", "the DarkFeat", darkfeat_tensor_names(), shapes, sd, n, lib.imcui_hip_darkfeat_pack_weights)
+
+
+def darkfeat_map_sizes(H: int, W: int) -> tuple:
+    """(h2, w2, h4, w4): a stride-2 layer leaves (n - 1) // 2 + 1 rows / columns."""
+    h2, w2 = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    return h2, w2, (h2 - 1) // 2 + 1, (w2 - 1) // 2 + 1
+
+
+def darkfeat_det_conf(conf: dict) -> dict:
+    """The detector settings of a conf: upstream's values unless the conf carries the backend-only keys; refusals by name."""
+    if conf.get("multi_scale"):
+        raise ValueError("DarkFeat: multi_scale is not served by the HIP backend")
+    if conf.get("multi_level", True) is False:
+        raise ValueError("DarkFeat: multi_level=False is not served by the HIP backend (the score is the three-level sum)")
+    if conf.get("use_peakiness", True) is False:
+        raise ValueError("DarkFeat: use_peakiness=False is not served by the HIP backend")
+    d = {k: conf.get(k, v) for k, v in DARKFEAT_DET_DEFAULTS.items()}
+    if int(d["nms_size"]) not in (0, 3):
+        raise ValueError(f"DarkFeat: nms_size={d['nms_size']} is not served (0 or 3)")
+    if int(d["eof_mask"]) < 0 or int(d["kpt_n"]) < 1 or not float(d["edge_thld"]) > 0:
+        raise ValueError(f"DarkFeat: eof_mask={d['eof_mask']} (>= 0), kpt_n={d['kpt_n']} (>= 1), edge_thld={d['edge_thld']} (> 0)")
+    return d
+
+
+def darkfeat_check_args(image_shape, max_keypoints: int = 0) -> None:
+    """Refusals raised before anything is launched."""
+    if len(image_shape) != 4 or image_shape[1] != 3:
+        raise ValueError(f"DarkFeat expects an RGB image [B,3,H,W], got shape {tuple(image_shape)}")
+    if image_shape[2] < DARKFEAT_MIN_SIDE or image_shape[3] < DARKFEAT_MIN_SIDE:
+        raise ValueError(f"DarkFeat needs images of at least {DARKFEAT_MIN_SIDE} x {DARKFEAT_MIN_SIDE}, got {tuple(image_shape[2:])}")
+    if int(max_keypoints) < 0:  # (the reference's slice `[-k or None:]` would silently DROP the |k| lowest scores)
+        raise ValueError(f"DarkFeat: max_keypoints={max_keypoints} is negative; 0 keeps every key-point")
+
+
+def _darkfeat_kout(np_: int, det: dict, maxk: int) -> int:
+    return max(1, min(np_, int(det["kpt_n"]), maxk if maxk > 0 else np_))
+
+
+class DarkFeatHIP:
+    def __init__(self):
+        self._ws = _Workspace()
+
+    def forward(self, packed: torch.Tensor, image: torch.Tensor, conf: dict, want_maps: bool = False, layer: int = -1):
+        """image [B,3,H,W] float32 on the GPU -> fixed-stride outputs, no host synchronisation: keypoints [B,K,2] (x, y in pixels,
+        integer-valued), scores [B,K], descriptors [B,K,128], num_keypoints [B] int32, status [1] int32 (bit 4: a flat image), rows in
+        ascending (score, pixel) order, rows past the count zero.  K = min(kpt_n, max_keypoints or all, H W).  want_maps adds score
+        [B,H,W], desc_map [B,h4,w4,128], peak0 / peak1 / peak2 and prob; `layer` adds layer_raw / layer_norm of that layer (NHWC)."""
+        maxk = int(conf.get("max_keypoints") or 0)
+        darkfeat_check_args(tuple(image.shape), maxk)
+        det = darkfeat_det_conf(conf)
+        hd = get_handle(image.device)
+        _same_device(packed, image)
+        lib = hd.lib
+        image = image.contiguous().float()
+        B, Cc, H, W = image.shape
+        dev = image.device
+        kout = _darkfeat_kout(H * W, det, maxk)
+        kpts, scores, desc, nk, status, out = _sparse_outputs(B, kout, DARKFEAT_DIM, dev)
+        f32 = dict(dtype=torch.float32, device=dev)
+        h2, w2, h4, w4 = darkfeat_map_sizes(H, W)
+        maps = {}
+        if want_maps:
+            maps = dict(score=torch.empty((B, H, W), **f32), desc_map=torch.empty((B, h4, w4, DARKFEAT_DIM), **f32), peak0=torch.empty((B, H, W), **f32),
+                        peak1=torch.empty((B, h2, w2), **f32), peak2=torch.empty((B, h4, w4), **f32), prob=torch.empty((B, h4, w4), **f32))  # fmt: skip
+        if layer >= 0:
+            sizes, hh, ww = [], H, W
+            for L in darkfeat_layers():
+                if L["stride"] == 2:
+                    hh, ww = (hh - 1) // 2 + 1, (ww - 1) // 2 + 1
+                sizes.append((B, hh, ww, L["cout"]))
+            maps["layer_raw"], maps["layer_norm"] = torch.empty(sizes[layer], **f32), torch.empty(sizes[layer], **f32)
+        with self._ws.use(lib.imcui_hip_darkfeat_workspace_bytes(B, H, W), dev) as ws:
+            hd.launch(
+                lib.imcui_hip_darkfeat_forward, _ptr(packed), _ptr(image), B, Cc, H, W, float(det["score_thld"]), float(det["edge_thld"]), int(det["nms_size"]),
+                int(det["eof_mask"]), int(det["kpt_n"]), maxk, kout, _ptr(kpts), _ptr(scores), _ptr(desc), _ptr(nk), _ptr(status), _ptr(maps.get("score")),
+                _ptr(maps.get("desc_map")), _ptr(maps.get("peak0")), _ptr(maps.get("peak1")), _ptr(maps.get("peak2")), _ptr(maps.get("prob")), int(layer),
+                _ptr(maps.get("layer_raw")), _ptr(maps.get("layer_norm")), _ptr(ws), ws.numel(),
+            )  # fmt: skip
+        out.update(maps)
+        return out
+
+    def _probe_ws(self, lib, B, H, W, dev):
+        return self._ws.use(lib.imcui_hip_darkfeat_probe_workspace_bytes(B, H, W), dev)
+
+    def stem_probe(self, packed: torch.Tensor, image: torch.Tensor) -> dict:
+        """Test entry: image statistics and layer 0, image [B,3,H,W] -> raw [B,H,W,32] (before InstanceNorm), imstat [B,2], status [1]."""
+        hd = get_handle(image.device)
+        image = image.contiguous().float()
+        B, _, H, W = image.shape
+        f32 = dict(dtype=torch.float32, device=image.device)
+        o = dict(raw=torch.empty((B, H, W, 32), **f32), imstat=torch.empty((B, 2), **f32), status=torch.zeros((1,), dtype=torch.int32, device=image.device))
+        with self._probe_ws(hd.lib, B, H, W, image.device) as ws:
+            hd.launch(hd.lib.imcui_hip_darkfeat_stem_probe, _ptr(packed), _ptr(image), B, H, W, _ptr(o["raw"]), _ptr(o["imstat"]), _ptr(o["status"]), _ptr(ws), ws.numel())
+        return o
+
+    def inorm_probe(self, x: torch.Tensor):
+        """Test entry: InstanceNorm + ReLU of x [B,H,W,C] (NHWC, C = 32 / 64 / 128) -> (out [B,H,W,C], stat [B,C,2] = mean, rsqrt(var + eps))."""
+        hd = get_handle(x.device)
+        x = x.contiguous().float()
+        B, H, W, Cc = x.shape
+        out, stat = torch.empty_like(x), torch.empty((B, Cc, 2), dtype=torch.float32, device=x.device)
+        with self._probe_ws(hd.lib, B, H, W, x.device) as ws:
+            hd.launch(hd.lib.imcui_hip_darkfeat_inorm_probe, _ptr(x), B, H, W, Cc, _ptr(out), _ptr(stat), _ptr(ws), ws.numel())
+        return out, stat
+
+    def peak_probe(self, x: torch.Tensor, d: int, mavg: float) -> torch.Tensor:
+        """Test entry: the peakiness pass on a raw map x [B,H,W,C] with dilation d and divisor mavg -> [B,H,W]."""
+        hd = get_handle(x.device)
+        x = x.contiguous().float()
+        B, H, W, Cc = x.shape
+        m = torch.tensor([mavg], dtype=torch.float32, device=x.device)
+        out = torch.empty((B, H, W), dtype=torch.float32, device=x.device)
+        hd.launch(hd.lib.imcui_hip_darkfeat_peak_probe, _ptr(x), _ptr(m), B, H, W, Cc, int(d), _ptr(out))
+        return out
+
+    def score_probe(self, packed: torch.Tensor, pk0: torch.Tensor, pk1: torch.Tensor, pk2: torch.Tensor, dmap: torch.Tensor) -> torch.Tensor:
+        """Test entry: the score assembly from level maps pk0 [B,H,W], pk1 [B,h2,w2], pk2 [B,h4,w4] and dmap [B,h4,w4,128] -> [B,H,W]."""
+        hd = get_handle(pk0.device)
+        pk0, pk1, pk2, dmap = (t.contiguous().float() for t in (pk0, pk1, pk2, dmap))
+        B, H, W = pk0.shape
+        h2, w2, h4, w4 = darkfeat_map_sizes(H, W)
+        if tuple(pk1.shape) != (B, h2, w2) or tuple(pk2.shape) != (B, h4, w4) or tuple(dmap.shape) != (B, h4, w4, DARKFEAT_DIM):
+            raise ValueError("score_probe: the level maps do not have the sizes of the stride-2 chain")
+        out = torch.empty((B, H, W), dtype=torch.float32, device=pk0.device)
+        with self._probe_ws(hd.lib, B, H, W, pk0.device) as ws:
+            hd.launch(hd.lib.imcui_hip_darkfeat_score_probe, _ptr(packed), _ptr(pk0), _ptr(pk1), _ptr(pk2), _ptr(dmap), B, H, W, _ptr(out), _ptr(ws), ws.numel())
+        return out
+
+    def detect_probe(self, score: torch.Tensor, conf: dict | None = None) -> dict:
+        """Test entry: the detector, the cut and the ranked rows on a score map [B,H,W]; conf: max_keypoints and the detector keys."""
+        conf = dict(conf or {})
+        maxk = int(conf.get("max_keypoints") or 0)
+        if maxk < 0:
+            raise ValueError(f"DarkFeat: max_keypoints={maxk} is negative; 0 keeps every key-point")
+        det = darkfeat_det_conf(conf)
+        hd = get_handle(score.device)
+        score = score.contiguous().float()
+        B, H, W = score.shape
+        dev = score.device
+        kout = _darkfeat_kout(H * W, det, maxk)
+        kpts, scores, _, nk, status, out = _sparse_outputs(B, kout, 1, dev)
+        out.pop("descriptors")
+        out["num_candidates"] = torch.empty((B,), dtype=torch.int32, device=dev)
+        out["det_map"] = torch.empty((B, H, W), dtype=torch.float32, device=dev)
+        with self._probe_ws(hd.lib, B, H, W, dev) as ws:
+            hd.launch(hd.lib.imcui_hip_darkfeat_detect_probe, _ptr(score), B, H, W, float(det["score_thld"]), float(det["edge_thld"]), int(det["nms_size"]),
+                      int(det["eof_mask"]), int(det["kpt_n"]), maxk, kout, _ptr(kpts), _ptr(scores), _ptr(nk), _ptr(out["num_candidates"]), _ptr(status),
+                      _ptr(out["det_map"]), _ptr(ws), ws.numel())  # fmt: skip
+        return out
+
+    def describe_probe(self, dmap: torch.Tensor, keypoints: torch.Tensor, nkpts: torch.Tensor) -> torch.Tensor:
+        """Test entry: descriptors at keypoints [B,K,2] (x, y in image pixels; nkpts [B] valid rows) of a map dmap [B,h4,w4,128]."""
+        hd = get_handle(dmap.device)
+        dmap, keypoints = dmap.contiguous().float(), keypoints.contiguous().float()
+        nkpts = nkpts.to(dmap.device, torch.int32).contiguous()
+        B, h4, w4, _ = dmap.shape
+        K = keypoints.shape[1]
+        out = torch.empty((B, K, DARKFEAT_DIM), dtype=torch.float32, device=dmap.device)
+        hd.launch(hd.lib.imcui_hip_darkfeat_describe_probe, _ptr(dmap), B, h4, w4, _ptr(keypoints), _ptr(nkpts), K, _ptr(out))
+        return out
+
+
 # ------------------------------------------------------------------ NetVLAD
 # (cin, cout, index in torchvision's vgg16().features): VGG-16 to conv5_3, csrc/netvlad.hip
 NETVLAD_LAYERS = ((3, 64, 0), (64, 64, 2), (64, 128, 5), (128, 128, 7), (128, 256, 10), (256, 256, 12), (256, 256, 14), (256, 512, 17), (512, 512, 19),

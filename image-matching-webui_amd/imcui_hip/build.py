@@ -12,7 +12,7 @@ CSRC = os.path.normpath(os.path.join(PKG_DIR, "..", "csrc"))
 INCLUDE = os.path.normpath(os.path.join(PKG_DIR, "..", "..", "include"))
 LIB_DIR = os.path.join(PKG_DIR, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libimcui_hip.so")
-SOURCES = ["api.hip", "preprocess.hip", "jpeg.hip", "png.hip", "geometry.hip", "gemm.hip", "gemm_wreg.hip", "ffn.hip", "simred.hip", "conv.hip", "attention.hip", "attention_mx.hip", "superpoint.hip", "disk.hip", "aliked.hip", "alike.hip", "r2d2.hip", "d2net.hip", "lanet.hip", "dedode.hip", "netvlad.hip", "places.hip", "dog.hip", "sift.hip", "xfeat.hip", "lightglue.hip", "superglue.hip", "nn.hip", "dual_softmax.hip", "loftr.hip", "eloftr.hip", "dust3r.hip", "select_probe.hip"]
+SOURCES = ["api.hip", "preprocess.hip", "jpeg.hip", "png.hip", "geometry.hip", "gemm.hip", "gemm_wreg.hip", "ffn.hip", "simred.hip", "conv.hip", "attention.hip", "attention_mx.hip", "superpoint.hip", "disk.hip", "aliked.hip", "alike.hip", "r2d2.hip", "d2net.hip", "lanet.hip", "darkfeat.hip", "dedode.hip", "netvlad.hip", "places.hip", "dog.hip", "sift.hip", "xfeat.hip", "lightglue.hip", "superglue.hip", "nn.hip", "dual_softmax.hip", "loftr.hip", "eloftr.hip", "dust3r.hip", "select_probe.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value", f"-I{INCLUDE}", f"-I{CSRC}"]
 # Per-source code-generation switches.  preprocess.hip restates host float32 arithmetic that rounds after every
@@ -23,7 +23,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-val
 # gemm.hip (round 4): the same switch for the round-2 GEMM, whose rotary epilogue (EPI_QKV, taken when gemm_wreg_ok says no) compiled to the
 # same class of in-place v_pk_fma_f32 with op_sel (16 per kernel, seen in the ISA); measured performance-neutral on one box (headline
 # 945.6 -> 950.2 pairs/s, LoFTR 100.98 -> 101.04, DUSt3R 89.98 -> 89.83), all kernel tests unchanged.
-EXTRA_FLAGS: dict = {"preprocess.hip": ["-ffp-contract=off"], "d2net.hip": ["-ffp-contract=off"], "lanet.hip": ["-ffp-contract=off"], "dedode.hip": ["-ffp-contract=off"], "gemm_wreg.hip": ["-fno-slp-vectorize"], "gemm.hip": ["-fno-slp-vectorize"]}
+EXTRA_FLAGS: dict = {"preprocess.hip": ["-ffp-contract=off"], "d2net.hip": ["-ffp-contract=off"], "lanet.hip": ["-ffp-contract=off"], "darkfeat.hip": ["-ffp-contract=off"], "dedode.hip": ["-ffp-contract=off"], "gemm_wreg.hip": ["-fno-slp-vectorize"], "gemm.hip": ["-fno-slp-vectorize"]}
 
 
 def _newest_source_mtime() -> float:

@@ -72,6 +72,12 @@ confs = {
         "model": {"name": "lanet", "keypoint_threshold": 0.1, "max_keypoints": 5000},
         "preprocessing": {"grayscale": False, "resize_max": 1600},
     },
+    # imcui/hloc/configs/extractors.py:300-316: DarkFeat (the `darkfeat` plugin), RGB; the two *_threshold keys are read by nobody
+    "darkfeat": {
+        "output": "feats-darkfeat-n5000-r1600",
+        "model": {"name": "darkfeat", "max_keypoints": 5000, "reliability_threshold": 0.7, "repetability_threshold": 0.7},
+        "preprocessing": {"grayscale": False, "force_resize": True, "resize_max": 1600, "width": 640, "height": 480, "dfactor": 8},
+    },
 }
 
 

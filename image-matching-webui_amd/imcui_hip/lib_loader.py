@@ -113,6 +113,23 @@ SIGNATURES = {
     "imcui_hip_lanet_select_probe": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 5 + [C.c_float] + [C.c_int] * 2 + [C.c_void_p] * 8 + [C.c_void_p, C.c_size_t, C.c_void_p]),
     "imcui_hip_lanet_desc_probe": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 2 + [C.c_void_p] + [C.c_int] * 2 + [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 2 + [C.c_int] + [C.c_void_p] * 2),
     "imcui_hip_lanet_dense_levels": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_void_p] + [C.c_int] * 2 + [C.c_void_p] * 3),
+    "imcui_hip_darkfeat_num_layers": (C.c_int, []),
+    "imcui_hip_darkfeat_layer": (C.c_char_p, [C.c_int, C.c_void_p]),
+    "imcui_hip_darkfeat_num_tensors": (C.c_int, []),
+    "imcui_hip_darkfeat_tensor_name": (C.c_char_p, [C.c_int]),
+    "imcui_hip_darkfeat_packed_floats": (C.c_size_t, []),
+    "imcui_hip_darkfeat_pack_weights": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p]),
+    "imcui_hip_darkfeat_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
+    "imcui_hip_darkfeat_forward": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_float] * 2 + [C.c_int] * 5 + [C.c_void_p] * 11 + [C.c_int] + [C.c_void_p] * 2
+                                   + [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "imcui_hip_darkfeat_probe_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
+    "imcui_hip_darkfeat_stem_probe": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_void_p] * 3 + [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "imcui_hip_darkfeat_inorm_probe": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 4 + [C.c_void_p] * 2 + [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "imcui_hip_darkfeat_peak_probe": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 5 + [C.c_void_p] * 2),
+    "imcui_hip_darkfeat_score_probe": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 3 + [C.c_void_p] + [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "imcui_hip_darkfeat_detect_probe": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 3 + [C.c_float] * 2 + [C.c_int] * 5 + [C.c_void_p] * 6
+                                        + [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "imcui_hip_darkfeat_describe_probe": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 3 + [C.c_void_p] * 2 + [C.c_int] + [C.c_void_p] * 2),
     "imcui_hip_dedode_packed_floats": (C.c_size_t, [C.c_void_p]),
     "imcui_hip_dedode_num_tensors": (C.c_int, [C.c_void_p]),
     "imcui_hip_dedode_tensor_name": (C.c_char_p, [C.c_void_p, C.c_int]),

@@ -1047,3 +1047,76 @@ def lanet_synth_state(seed: int = 0, k: int = 3, bias: bool = True, bn: bool = F
         if bn:
             norm(f"des_bn{lvl}", 256)
     return sd
+
+
+# name, cin, cout, stride, InstanceNorm + ReLU behind it, score level of the raw output: the backbone tests/darkfeat_reference.py restates
+DARKFEAT_LAYERS = (("conv0", 3, 32, 1, True, -1), ("conv1", 32, 32, 1, True, 0), ("conv2", 32, 64, 2, True, -1), ("conv3", 64, 64, 1, True, 1),
+                   ("conv4", 64, 128, 2, True, -1), ("conv5", 128, 128, 1, True, -1), ("conv6_0", 128, 128, 1, True, -1),
+                   ("conv6_1", 128, 128, 1, True, -1), ("conv6_2", 128, 128, 1, False, 2))  # fmt: skip
+
+
+def darkfeat_synth_state(seed: int = 0, bias: bool = False, peak_gain: float = 1.0, share: float = 0.5) -> dict:
+    """Seeded DarkFeat weights under upstream's key names (`convN.0.weight`, with `bias` also `convN.0.bias`; `clf.*`; the 0-d
+    `moving_avg_params.{0,1,2}`), plus the BatchNorm-statistics keys of a `conv0.1` that upstream drops before loading (a loader has to
+    skip them).  Convolutions are He-initialised.  A plain draw leaves every score near softplus(0)^2 = 0.48 times the classifier's
+    probability, far below the 0.5 threshold, and such a network tests nothing.  So the rest is calibrated on a seeded 64 x 64 uniform
+    image (drawn from the same generator, evaluated here with torch's own operations): `moving_avg_params[i]` = the standard deviation
+    of raw map i / `peak_gain` (the peakiness sees unit-variance input), the classifier's logit difference gets unit standard deviation,
+    and its bias is bisected so that `share` of the 3x3 maxima of the score map inside the 5-pixel border band lie above 0.5 on that
+    image.  At the sizes the tests use (32x48, 50x70, 96x128 and 40x56, seed 0) 70 %, 53 %, 47 % and 62 % of those maxima (10, 36, 207
+    and 21 of them) lie above 0.5; tests/test_darkfeat_cpu.py asserts 40 % .. 75 %."""
+    import torch.nn.functional as F
+
+    g = torch.Generator().manual_seed(seed)
+    sd = {}
+
+    def rn(*shape, scale=1.0):
+        return torch.randn(*shape, generator=g) * scale
+
+    for name, cin, cout, _, _, _ in DARKFEAT_LAYERS:
+        sd[f"{name}.0.weight"] = rn(cout, cin, 3, 3, scale=math.sqrt(2.0) / math.sqrt(cin * 9))
+        if bias:
+            sd[f"{name}.0.bias"] = 0.1 * rn(cout)
+    sd["conv0.1.running_mean"], sd["conv0.1.running_var"] = 0.2 * rn(32), 0.5 + torch.rand(32, generator=g)
+    sd["conv0.1.num_batches_tracked"] = torch.tensor(1000, dtype=torch.long)
+
+    # ---- the calibration image through the backbone
+    img = torch.rand(1, 3, 64, 64, generator=g)
+    H, W = img.shape[-2:]
+    x = (img - img.mean()) / img.std()
+    peaks = [None] * 3
+
+    def peak(x, d):
+        h, w = x.shape[-2:]
+        xp = F.pad(x, (d, d, d, d), mode="reflect")
+        box = sum(xp[..., i * d : i * d + h, j * d : j * d + w] for i in range(3) for j in range(3)) / 9.0
+        return (F.softplus(x - box) * F.softplus(x - x.mean(dim=1, keepdim=True))).max(dim=1, keepdim=True).values
+
+    for name, _, _, stride, norm, tap in DARKFEAT_LAYERS:
+        x = F.conv2d(x, sd[f"{name}.0.weight"], sd.get(f"{name}.0.bias"), stride=stride, padding=1)
+        if tap >= 0:
+            m = x.std() / peak_gain
+            sd[f"moving_avg_params.{tap}"] = m.clone()
+            peaks[tap] = F.interpolate(peak(x / m, (3, 2, 1)[tap]), size=(H, W), mode="bilinear", align_corners=True)
+        if norm:
+            x = F.relu(F.instance_norm(x, eps=1e-5))
+    level_sum = (peaks[0] / 6.0 + peaks[1] * (2.0 / 6.0)) + peaks[2] * (3.0 / 6.0)
+    w = rn(2, 128, 1, 1, scale=1.0 / math.sqrt(128))
+    logit = F.conv2d(x * x, w)
+    diff = logit[:, 1] - logit[:, 0]
+    w = w / diff.std()
+    logit = F.conv2d(x * x, w)
+
+    def share_above(b1):
+        prob = torch.softmax(logit + torch.tensor([0.0, b1]).view(1, 2, 1, 1), dim=1)[:, 1:2]
+        score = (level_sum * F.interpolate(prob, size=(H, W), mode="bilinear", align_corners=True))[0, 0]
+        peaks_ = (score == F.max_pool2d(score[None, None], 3, 1, 1)[0, 0])[5:-5, 5:-5]
+        return (score[5:-5, 5:-5][peaks_] > 0.5).float().mean().item()
+
+    lo, hi = -30.0, 30.0
+    for _ in range(40):
+        mid = (lo + hi) / 2
+        lo, hi = (mid, hi) if share_above(mid) < share else (lo, mid)
+    sd["clf.weight"] = w
+    sd["clf.bias"] = torch.tensor([0.0, (lo + hi) / 2])
+    return sd

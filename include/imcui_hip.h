@@ -358,6 +358,64 @@ int imcui_hip_lanet_desc_probe(imcui_hip_t* h, const int* cfg, const float* pack
 int imcui_hip_lanet_dense_levels(imcui_hip_t* h, const int* cfg, const float* packed, const float* x2, int B, int h2, int w2, const float* x3, int h3, int w3,
                                  float* d2, float* d3, void* stream);
 
+/* ---- DarkFeat (zoo entry darkfeat: `feature: darkfeat` + NN-mutual; imcui/hloc/extractors/darkfeat.py) -------------------- */
+/* darkfeat.DarkFeat(model_path) (replaces darkfeat.py:28) is not part of the reference checkout (third_party/DarkFeat is an empty
+ * submodule): the network is restated from its description (tests/darkfeat_reference.py) and parity with upstream's code is NOT pinned
+ * ("DarkFeat: what is pinned").  The backbone is ONE table in csrc/darkfeat.hip (DF_LAYERS), readable through
+ * imcui_hip_darkfeat_layer: name, and out5 = cin, cout, stride, InstanceNorm + ReLU behind it, score level its RAW output feeds (-1 none).
+ * Tensors in imcui_hip_darkfeat_tensor_name order: `<layer>.0.weight` [cout,cin,3,3], `<layer>.0.bias` [cout] (zeros when the checkpoint
+ * has none), clf.weight [2,128,1,1], clf.bias [2], moving_avg_params.0..2 [1]. */
+int imcui_hip_darkfeat_num_layers(void);
+const char* imcui_hip_darkfeat_layer(int i, int* out5);
+int imcui_hip_darkfeat_num_tensors(void);
+const char* imcui_hip_darkfeat_tensor_name(int i);
+size_t imcui_hip_darkfeat_packed_floats(void);
+int imcui_hip_darkfeat_pack_weights(const float* const* tensors, float* packed);
+/* Scratch of imcui_hip_darkfeat_forward: B images of H x W (H, W >= 16). */
+size_t imcui_hip_darkfeat_workspace_bytes(int B, int H, int W);
+/* darkfeat.py:31-44 `_forward` around `self.net({"image": image})` (:32): image [dev, B,C,H,W] with C == 3 (anything else is refused),
+ * H, W >= 16.  Per image (x - mean) / std over its 3 H W values (std unbiased); 3x3 convolutions with a non-affine InstanceNorm
+ * (eps 1e-5, biased variance) and ReLU; per score level max_c softplus(x - box3x3_d(x)) softplus(x - mean_c(x)) of the raw map divided by
+ * its moving average (d = 3, 2, 1, reflect padding); score = (sum_l (l + 1) / 6 up(s_l)) up(soft-max(clf(desc^2))[1]), up = bilinear,
+ * align_corners=True.  Detector: score > score_thld (strict), 3x3 maximum (nms_size 3; 0 = off), not within eof_mask pixels of the
+ * border, det > 0 and tr^2 / det <= (edge_thld + 1)^2 / edge_thld of the dilation-3 Hessian (zero padding), every operation rounded
+ * once.  Candidates in row-major order; the min(kpt_n, max_keypoints or all) highest scores stay (:36 `[-max_keypoints or None:]`; a
+ * negative max_keypoints is refused), among equal scores the later pixels; output in ASCENDING (score, pixel) order, a STABLE form of
+ * :36's argsort.  descriptor = the last layer's 1/4-resolution map at (y, x) / 4 (floor / ceil corners clamped, weights from the
+ * unclamped fractions) / max(norm, 1e-12).  kout >= min(kpt_n, max_keypoints or all, H W).  Outputs, first num_keypoints[b] rows valid,
+ * the rest zero:
+ *   keypoints [dev, B,kout,2] (x, y), integer-valued;  scores [dev, B,kout];  descriptors [dev, B,kout,128];  num_keypoints [dev, B] int32
+ *   status [dev, 1] int32 optional: bit 4 = an image of the batch is flat (std == 0: NaN upstream; here that image has zero key-points).
+ *   The candidate list holds every pixel, so it cannot overflow (bit 2 never shows).
+ *   optional debug outputs: dbg_score [B,H,W], dbg_desc [B,h4,w4,128], dbg_peak0 [B,H,W], dbg_peak1 [B,h2,w2], dbg_peak2 and dbg_prob
+ *   [B,h4,w4] (h2 = (H-1)/2+1, h4 = (h2-1)/2+1); dbg_raw / dbg_norm: the output of layer dbg_layer before / behind its InstanceNorm
+ * No host synchronisation; a row's bits do not depend on the batch. */
+int imcui_hip_darkfeat_forward(imcui_hip_t* h, const float* packed, const float* image, int B, int C, int H, int W, float score_thld, float edge_thld,
+                               int nms_size, int eof_mask, int kpt_n, int max_keypoints, int kout, float* keypoints, float* scores, float* descriptors,
+                               int* num_keypoints, int* status, float* dbg_score, float* dbg_desc, float* dbg_peak0, float* dbg_peak1, float* dbg_peak2,
+                               float* dbg_prob, int dbg_layer, float* dbg_raw, float* dbg_norm, void* ws, size_t ws_bytes, void* stream);
+/* Test entries; ws: imcui_hip_darkfeat_probe_workspace_bytes(B, H, W) of the map the probe is given.  stem_probe: the image statistics
+ * and layer 0, image [dev, B,3,H,W] -> out [dev, B,H,W,32] RAW, imstat [dev, B,2] = mean, std (1 when flat), status OR-ed with bit 4
+ * (the caller zeroes it).  inorm_probe: InstanceNorm + ReLU of x [dev, B,H,W,C], C = 32 / 64 / 128 -> out, stat [dev, B,C,2] = mean,
+ * 1 / sqrt(var + eps) (optional).  peak_probe: the peakiness pass, (C, d) = (32, 3), (64, 2), (128, 1), H, W >= d + 1, mavg [dev, 1].
+ * score_probe: the assembly from given level maps pk0 [B,H,W], pk1 [B,h2,w2], pk2 [B,h4,w4] and dmap [B,h4,w4,128].  detect_probe: the
+ * detector, the cut and the ranked rows on a given score map [dev, B,H,W]; num_candidates [dev, B] and det_map [dev, B,H,W] (the score
+ * at candidates, -inf elsewhere) optional.  describe_probe: descriptors at keypoints [dev, B,K,2] (nkpts [dev, B] valid rows) of a
+ * given map dmap [dev, B,h4,w4,128]. */
+size_t imcui_hip_darkfeat_probe_workspace_bytes(int B, int H, int W);
+int imcui_hip_darkfeat_stem_probe(imcui_hip_t* h, const float* packed, const float* image, int B, int H, int W, float* out, float* imstat, int* status,
+                                  void* ws, size_t ws_bytes, void* stream);
+int imcui_hip_darkfeat_inorm_probe(imcui_hip_t* h, const float* x, int B, int H, int W, int C, float* out, float* stat, void* ws, size_t ws_bytes,
+                                   void* stream);
+int imcui_hip_darkfeat_peak_probe(imcui_hip_t* h, const float* x, const float* mavg, int B, int H, int W, int C, int d, float* out, void* stream);
+int imcui_hip_darkfeat_score_probe(imcui_hip_t* h, const float* packed, const float* pk0, const float* pk1, const float* pk2, const float* dmap, int B, int H,
+                                   int W, float* score, void* ws, size_t ws_bytes, void* stream);
+int imcui_hip_darkfeat_detect_probe(imcui_hip_t* h, const float* score, int B, int H, int W, float score_thld, float edge_thld, int nms_size, int eof_mask,
+                                    int kpt_n, int max_keypoints, int kout, float* keypoints, float* scores, int* num_keypoints, int* num_candidates,
+                                    int* status, float* det_map, void* ws, size_t ws_bytes, void* stream);
+int imcui_hip_darkfeat_describe_probe(imcui_hip_t* h, const float* dmap, int B, int h4, int w4, const float* keypoints, const int* nkpts, int K,
+                                      float* descriptors, void* stream);
+
 /* ---- DeDoDe (zoo entry dedode: `feature: dedode` + Dual-Softmax; imcui/hloc/extractors/dedode.py) ----------------------- */
 /* dedode_detector_L (vgg19_bn encoder) and dedode_descriptor_B (vgg11_bn encoder) of Parskatt/DeDoDe, each with a decoder of four
  * ConvRefiners (scales 8, 4, 2, 1).  The refiners' shapes are READ from the checkpoint by the binding and handed over as
