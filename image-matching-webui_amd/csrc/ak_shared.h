@@ -207,28 +207,27 @@ static void ak_conv3(const AkConvP& p, int B, hipStream_t stream) {
 // candidates leave in row-major order in cscore / cidx [B][H W], their counts in ncand [B].  *status is zeroed first.
 struct AkDkdWs {
     float *mean, *thr;
-    int *blkcnt, *blkoff, *ncand;
-    float* cscore;
-    int* cidx;
+    CandScan scan;        // (total = ncand)
+    ScoreIndexList cand;  // [B][H W]: every pixel is a candidate of a flat score map
+    void carve(WsAlloc& a, int B, int H, int W) {
+        mean = a.get<float>(B);
+        thr = a.get<float>(B);
+        scan.carve(a, B, (size_t)H * W);
+        cand.carve(a, B, H * W);
+    }
 };
 static int ak_dkd_candidates(imcui_hip_s* h, const float* smap, const float* nms, int H, int W, int B, int band_lo, int band_hi, float threshold, bool topk,
                              const AkDkdWs& s, int* status, hipStream_t stream) {
     hipMemsetAsync(status, 0, sizeof(int), stream);
-    const int nchunk = cdiv(H * W, SEL_CHUNK), ccap = H * W;
     hipLaunchKernelGGL(ak_mean_kernel, dim3(B), dim3(1024), 0, stream, smap, H * W, s.mean);
-    hipLaunchKernelGGL(ak_thr_kernel, dim3(1), dim3(1024), 0, stream, s.thr, s.mean, s.ncand, topk ? 0.0f : threshold, (topk || threshold > 0.0f) ? 0 : 1, B);
+    hipLaunchKernelGGL(ak_thr_kernel, dim3(1), dim3(1024), 0, stream, s.thr, s.mean, s.scan.total, topk ? 0.0f : threshold, (topk || threshold > 0.0f) ? 0 : 1, B);
     const AkIsCand is_cand{H, W, band_lo, band_hi, s.thr};
-    auto count = [&]() {
-        hipLaunchKernelGGL(cand_count_kernel<AkIsCand>, dim3(nchunk, B), dim3(256), 0, stream, nms, H * W, is_cand, s.blkcnt, nchunk);
-        hipLaunchKernelGGL(exclusive_scan_kernel<int>, dim3(B), dim3(1024), 0, stream, s.blkcnt, s.blkoff, s.ncand, (const int*)nullptr, nchunk, (long)nchunk);
-    };
-    count();
+    cand_count_scan(stream, nms, H * W, B, is_cand, s.scan);
     if (!topk && threshold > 0.0f) {  // no candidate above the threshold: the mean of the score map takes its place (per image)
-        hipLaunchKernelGGL(ak_thr_kernel, dim3(1), dim3(1024), 0, stream, s.thr, s.mean, s.ncand, 0.0f, 2, B);
-        count();
+        hipLaunchKernelGGL(ak_thr_kernel, dim3(1), dim3(1024), 0, stream, s.thr, s.mean, s.scan.total, 0.0f, 2, B);
+        cand_count_scan(stream, nms, H * W, B, is_cand, s.scan);
     }
-    hipLaunchKernelGGL((cand_compact_kernel<AkIsCand, EmitScoreIndex>), dim3(nchunk, B), dim3(256), 0, stream, nms, H * W, is_cand, s.blkoff, nchunk, ccap,
-                       EmitScoreIndex{s.cscore, s.cidx, ccap});
+    cand_compact(stream, nms, H * W, B, is_cand, s.scan, s.cand.cap, s.cand.emit());
     IMCUI_CHECK_LAUNCH(h);
     return IMCUI_OK;
 }

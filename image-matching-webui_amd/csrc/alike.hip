@@ -575,8 +575,9 @@ __global__ __launch_bounds__(256) void al_desc_kernel(AlMaps m, const float* __r
 // ------------------------------------------------------------------ workspace
 struct AlWs {
     float *a1, *x1, *p1, *t2, *x2, *f2, *g2, *p2, *t3, *x3, *f3, *g3, *p3, *t4, *x4, *f4, *g4;
-    float *score, *nms, *mean, *thr, *cscore, *kscore, *knorm;
-    int *blkcnt, *blkoff, *ncand, *cidx, *kidx, *nkept, *sorted, *status;
+    float *score, *nms, *kscore, *knorm;
+    AkDkdWs dkd;
+    int *kidx, *nkept, *sorted, *status;
     size_t total;
     bool ok;
 };
@@ -603,14 +604,7 @@ static AlWs al_carve(void* ws, size_t bytes, const AlDims& d, int B, int h, int 
     s.g4 = a.get<float>(B * P5);
     s.score = a.get<float>((size_t)B * h * w);
     s.nms = a.get<float>((size_t)B * h * w);
-    s.mean = a.get<float>(B);
-    s.thr = a.get<float>(B);
-    const int nchunk = cdiv(h * w, SEL_CHUNK);
-    s.blkcnt = a.get<int>((size_t)B * nchunk);
-    s.blkoff = a.get<int>((size_t)B * nchunk);
-    s.ncand = a.get<int>(B);
-    s.cscore = a.get<float>((size_t)B * h * w);  // every pixel is a candidate of a flat score map
-    s.cidx = a.get<int>((size_t)B * h * w);
+    s.dkd.carve(a, B, h, w);
     s.kscore = a.get<float>((size_t)B * h * w);
     s.kidx = a.get<int>((size_t)B * h * w);
     s.nkept = a.get<int>(B);
@@ -763,10 +757,9 @@ extern "C" int imcui_hip_alike_forward(imcui_hip_t* h, int variant, const float*
     if (topk) limit = min(limit, top_k);
     if (n_limit > 0) limit = min(limit, n_limit);
     // (the band: rows / columns [0, r] and [h - r, h) are zeroed)
-    const AkDkdWs cw{s.mean, s.thr, s.blkcnt, s.blkoff, s.ncand, s.cscore, s.cidx};
-    const int rc2 = ak_dkd_candidates(h, smap, s.nms, H, W, B, AL_R + 1, AL_R, threshold, topk, cw, st, stream);
+    const int rc2 = ak_dkd_candidates(h, smap, s.nms, H, W, B, AL_R + 1, AL_R, threshold, topk, s.dkd, st, stream);
     if (rc2 != IMCUI_OK) return rc2;
-    hipLaunchKernelGGL(al_cut_kernel, dim3(B), dim3(1024), 0, stream, s.cscore, s.cidx, ccap, s.ncand, limit, topk ? 1 : 0, s.kscore, s.kidx, s.nkept, s.sorted);
+    hipLaunchKernelGGL(al_cut_kernel, dim3(B), dim3(1024), 0, stream, s.dkd.cand.cscore, s.dkd.cand.cidx, ccap, s.dkd.scan.total, limit, topk ? 1 : 0, s.kscore, s.kidx, s.nkept, s.sorted);
     hipLaunchKernelGGL(al_emit_kernel, dim3(cdiv(limit, 256), B), dim3(256), 0, stream, s.kscore, s.kidx, ccap, s.nkept, s.sorted, kcap, smap, H, W,
                        sub_pixel ? 1 : 0, keypoints, s.knorm, scores, num_keypoints, st);
     IMCUI_CHECK_LAUNCH(h);

@@ -600,8 +600,9 @@ __global__ __launch_bounds__(1024) void ak_select_kernel(const float* __restrict
 // ------------------------------------------------------------------ workspace
 struct AkWs {
     float *a16, *x1, *p1, *t2, *x2, *f2, *g2, *p2, *off3, *A3, *t3, *x3, *f3, *g3, *p3, *off4, *A4, *t4, *x4, *f4, *g4;
-    float *score, *nms, *mean, *thr, *cscore, *knorm;
-    int *blkcnt, *blkoff, *ncand, *cidx, *status;
+    float *score, *nms, *knorm;
+    AkDkdWs dkd;
+    int* status;
     size_t total;
     bool ok;
 };
@@ -633,14 +634,7 @@ static AkWs ak_carve(void* ws, size_t bytes, int B, int h, int w, int kcap) {
     s.g4 = a.get<float>(B * P5 * 8);
     s.score = a.get<float>((size_t)B * h * w);
     s.nms = a.get<float>((size_t)B * h * w);
-    s.mean = a.get<float>(B);
-    s.thr = a.get<float>(B);
-    const int nchunk = cdiv(h * w, SEL_CHUNK);
-    s.blkcnt = a.get<int>((size_t)B * nchunk);
-    s.blkoff = a.get<int>((size_t)B * nchunk);
-    s.ncand = a.get<int>(B);
-    s.cscore = a.get<float>((size_t)B * h * w);  // every pixel is a candidate of a flat score map
-    s.cidx = a.get<int>((size_t)B * h * w);
+    s.dkd.carve(a, B, h, w);
     s.knorm = a.get<float>((size_t)B * kcap * 2);
     s.status = a.get<int>(1);
     s.total = a.off;
@@ -778,10 +772,9 @@ extern "C" int imcui_hip_aliked_forward(imcui_hip_t* h, const float* packed, con
     const bool topk = !(threshold > 0.0f) && max_keypoints > 0;
     const int limit = max_keypoints > 0 ? max_keypoints : AK_NLIMIT;
     const int ccap = H * W;
-    const AkDkdWs cw{s.mean, s.thr, s.blkcnt, s.blkoff, s.ncand, s.cscore, s.cidx};
-    IMCUI_RUN(ak_dkd_candidates(h, smap, s.nms, H, W, B, r, r, threshold, topk, cw, st, stream));
+    IMCUI_RUN(ak_dkd_candidates(h, smap, s.nms, H, W, B, r, r, threshold, topk, s.dkd, st, stream));
     float* kn = keypoints_norm ? keypoints_norm : s.knorm;
-    hipLaunchKernelGGL(ak_select_kernel, dim3(B), dim3(1024), 0, stream, s.cscore, s.cidx, ccap, s.ncand, limit, kcap, smap, H, W, r, keypoints, kn, scores,
+    hipLaunchKernelGGL(ak_select_kernel, dim3(B), dim3(1024), 0, stream, s.dkd.cand.cscore, s.dkd.cand.cidx, ccap, s.dkd.scan.total, limit, kcap, smap, H, W, r, keypoints, kn, scores,
                        num_keypoints, st);
     IMCUI_CHECK_LAUNCH(h);
     // ---- SDDH: two launches per batch, whatever kcap is

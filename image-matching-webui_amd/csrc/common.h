@@ -262,3 +262,7 @@ struct WsAlloc {
         return r;
     }
 };
+// an optional output (a debug map, a probe's result): copied when the caller gave a destination
+static inline void copy_if(void* dst, const void* src, size_t bytes, hipStream_t stream) {
+    if (dst) hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, stream);
+}

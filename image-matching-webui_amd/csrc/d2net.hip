@@ -301,74 +301,72 @@ struct D2Emit {
     }
 };
 
-// One workgroup = 256 kept candidates: the rank of each in ascending (score, slot) order (the kept list is in slot order), then one wave
-// per key-point: the step again (d2_eval: the same arithmetic as the detector's), interpolate_dense_features' four corners with
+// The rows of ranked_rows_kernel (ascending (score, slot) order: the kept list is in slot order), one wave each: the step again (d2_eval: the same arithmetic as the detector's), interpolate_dense_features' four corners with
 // weights (1 - di)(1 - dj) .. di dj summed tl, tr, bl, br, F.normalize (eps 1e-12), upscale_positions (twice p * 2 + 0.5) and the
 // level's factors.  feat0 = the first level's maps; keypoints (x, y): d2net.py:49 swaps the columns.  Rows past the count are zero.
-__global__ __launch_bounds__(256) void d2_emit_kernel(const float* __restrict__ cscore, const int* __restrict__ clc, const int* __restrict__ cpix,
-                                                      const float* __restrict__ feat0, const int* __restrict__ kslot, const int* __restrict__ nkept, int kcap,
-                                                      int kout, D2Levels lv, int C, float* __restrict__ kpts, float* __restrict__ scores,
-                                                      float* __restrict__ desc, int* __restrict__ nkpts) {
-    __shared__ int rank_s[256];
-    const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, nk = C >> 6;
-    const float* cs = cscore + (long)b * kcap;
-    const int* ks = kslot + (long)b * kcap;
-    const int n = min(nkept[b], kout);
-    if (blockIdx.x == 0 && tid == 0) nkpts[b] = n;
-    float* kp = kpts + (long)b * kout * 2;
-    float* sc = scores + (long)b * kout;
-    float* de = desc + (long)b * kout * C;
-    const int i0 = blockIdx.x * 256;
-    for (int i = i0 + tid; i < min(i0 + 256, kout); i += 256)
-        if (i >= n) kp[2 * i] = kp[2 * i + 1] = sc[i] = 0.0f;
-    for (int i = i0 + wv; i < min(i0 + 256, kout); i += 4)
-        if (i >= n)
+struct D2Row {
+    const int *clc, *cpix;
+    const float* feat0;
+    int kcap, kout;
+    D2Levels lv;
+    int C;
+    float *kpts, *scores, *desc;
+    __device__ void clear(int b, int lo, int hi) const {
+        const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, nk = C >> 6;
+        float* kp = kpts + (long)b * kout * 2;
+        float* de = desc + (long)b * kout * C;
+        for (int i = lo + tid; i < hi; i += 256) kp[2 * i] = kp[2 * i + 1] = scores[(long)b * kout + i] = 0.0f;
+        for (int i = lo + wv; i < hi; i += 4)
             for (int k = 0; k < nk; ++k) de[(long)i * C + k * 64 + lane] = 0.0f;
-    if (i0 >= n) return;  // (uniform)
-    rank_s[tid] = kept_rank_ascending(cs, ks, n, i0 + tid);
-    __syncthreads();
-    for (int q = wv; q < min(256, n - i0); q += 4) {
-        const int slot = ks[i0 + q], r = rank_s[q];
-        const int lc = clc[(long)b * kcap + slot], pix = cpix[(long)b * kcap + slot];
-        const int l = lc >> 9, c = lc & 511;
-        const int h = lv.h[l], w = lv.w[l];
-        const float* x = feat0 + lv.off[l] + (long)b * h * w * C;
-        const int pi_ = pix / w, pj_ = pix - pi_ * w;
-        bool det, kept;
-        float p_i, p_j;
-        d2_eval(x, h, w, C, pi_, pj_, c, x[(long)pix * C + c], &det, &kept, &p_i, &p_j);
-        // (a listed candidate is kept: its corners lie inside the map; the clamps keep a wrong list from reading outside it)
-        const int it = min(max((int)floorf(p_i), 0), h - 1), ib = min(max((int)ceilf(p_i), 0), h - 1);
-        const int jl = min(max((int)floorf(p_j), 0), w - 1), jr = min(max((int)ceilf(p_j), 0), w - 1);
-        const float di = __fsub_rn(p_i, floorf(p_i)), dj = __fsub_rn(p_j, floorf(p_j));
-        const float wtl = __fmul_rn(__fsub_rn(1.0f, di), __fsub_rn(1.0f, dj)), wtr = __fmul_rn(__fsub_rn(1.0f, di), dj),
-                    wbl = __fmul_rn(di, __fsub_rn(1.0f, dj)), wbr = __fmul_rn(di, dj);
-        const float *ptl = x + ((long)it * w + jl) * C, *ptr = x + ((long)it * w + jr) * C, *pbl = x + ((long)ib * w + jl) * C,
-                    *pbr = x + ((long)ib * w + jr) * C;
-        float d[8];
-        float ss = 0.0f;
+    }
+    __device__ void emit(int b, int i0, int m, const int* ks, const int* rank, const float* cs) const {
+        const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nk = C >> 6;
+        float* kp = kpts + (long)b * kout * 2;
+        float* sc = scores + (long)b * kout;
+        float* de = desc + (long)b * kout * C;
+        for (int q = wv; q < m; q += 4) {
+            const int slot = ks[i0 + q], r = rank[q];
+            const int lc = clc[(long)b * kcap + slot], pix = cpix[(long)b * kcap + slot];
+            const int l = lc >> 9, c = lc & 511;
+            const int h = lv.h[l], w = lv.w[l];
+            const float* x = feat0 + lv.off[l] + (long)b * h * w * C;
+            const int pi_ = pix / w, pj_ = pix - pi_ * w;
+            bool det, kept;
+            float p_i, p_j;
+            d2_eval(x, h, w, C, pi_, pj_, c, x[(long)pix * C + c], &det, &kept, &p_i, &p_j);
+            // (a listed candidate is kept: its corners lie inside the map; the clamps keep a wrong list from reading outside it)
+            const int it = min(max((int)floorf(p_i), 0), h - 1), ib = min(max((int)ceilf(p_i), 0), h - 1);
+            const int jl = min(max((int)floorf(p_j), 0), w - 1), jr = min(max((int)ceilf(p_j), 0), w - 1);
+            const float di = __fsub_rn(p_i, floorf(p_i)), dj = __fsub_rn(p_j, floorf(p_j));
+            const float wtl = __fmul_rn(__fsub_rn(1.0f, di), __fsub_rn(1.0f, dj)), wtr = __fmul_rn(__fsub_rn(1.0f, di), dj),
+                        wbl = __fmul_rn(di, __fsub_rn(1.0f, dj)), wbr = __fmul_rn(di, dj);
+            const float *ptl = x + ((long)it * w + jl) * C, *ptr = x + ((long)it * w + jr) * C, *pbl = x + ((long)ib * w + jl) * C,
+                        *pbr = x + ((long)ib * w + jr) * C;
+            float d[8];
+            float ss = 0.0f;
 #pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            d[k] = 0.0f;
-            if (k < nk) {
-                const int ch = k * 64 + lane;
-                d[k] = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(wtl, ptl[ch]), __fmul_rn(wtr, ptr[ch])), __fmul_rn(wbl, pbl[ch])), __fmul_rn(wbr, pbr[ch]));
-                ss += d[k] * d[k];
+            for (int k = 0; k < 8; ++k) {
+                d[k] = 0.0f;
+                if (k < nk) {
+                    const int ch = k * 64 + lane;
+                    d[k] = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(wtl, ptl[ch]), __fmul_rn(wtr, ptr[ch])), __fmul_rn(wbl, pbl[ch])), __fmul_rn(wbr, pbr[ch]));
+                    ss += d[k] * d[k];
+                }
+            }
+            const float nrm = fmaxf(sqrtf(wave_sum(ss)), 1e-12f);
+#pragma unroll
+            for (int k = 0; k < 8; ++k)
+                if (k < nk) de[(long)r * C + k * 64 + lane] = d[k] / nrm;
+            if (lane == 0) {
+                const float ui = __fadd_rn(__fmul_rn(__fadd_rn(__fmul_rn(p_i, 2.0f), 0.5f), 2.0f), 0.5f);
+                const float uj = __fadd_rn(__fmul_rn(__fadd_rn(__fmul_rn(p_j, 2.0f), 0.5f), 2.0f), 0.5f);
+                kp[2 * r] = __fmul_rn(uj, lv.cs[l]);
+                kp[2 * r + 1] = __fmul_rn(ui, lv.rs[l]);
+                sc[r] = cs[slot];
             }
         }
-        const float nrm = fmaxf(sqrtf(wave_sum(ss)), 1e-12f);
-#pragma unroll
-        for (int k = 0; k < 8; ++k)
-            if (k < nk) de[(long)r * C + k * 64 + lane] = d[k] / nrm;
-        if (lane == 0) {
-            const float ui = __fadd_rn(__fmul_rn(__fadd_rn(__fmul_rn(p_i, 2.0f), 0.5f), 2.0f), 0.5f);
-            const float uj = __fadd_rn(__fmul_rn(__fadd_rn(__fmul_rn(p_j, 2.0f), 0.5f), 2.0f), 0.5f);
-            kp[2 * r] = __fmul_rn(uj, lv.cs[l]);
-            kp[2 * r + 1] = __fmul_rn(ui, lv.rs[l]);
-            sc[r] = cs[slot];
-        }
     }
-}
+};
 
 }  // namespace
 
@@ -390,7 +388,9 @@ struct D2Ws {
     float *img, *fa, *fb, *feat, *cscore;
     unsigned long long* planes;
     unsigned char* ban[2];
-    int *blkcnt, *blkoff, *nlev, *base, *clc, *cpix, *kslot, *nkept, *status;
+    CandScan scan;  // (total = this level's count)
+    CutList cut;
+    int *base, *clc, *cpix, *status;
     size_t total;
     bool ok;
 };
@@ -405,16 +405,12 @@ static D2Ws d2_carve(void* ws, size_t bytes, int B, size_t imgpix, size_t fpix_s
     s.planes = a.get<unsigned long long>((size_t)B * (C / 64) * fpix_max);
     s.ban[0] = a.get<unsigned char>((size_t)B * fpix_max);
     s.ban[1] = a.get<unsigned char>((size_t)B * fpix_max);
-    const size_t nchunk = (fpix_max * C + SEL_CHUNK - 1) / SEL_CHUNK;
-    s.blkcnt = a.get<int>((size_t)B * nchunk);
-    s.blkoff = a.get<int>((size_t)B * nchunk);
-    s.nlev = a.get<int>(B);
+    s.scan.carve(a, B, fpix_max * C);
     s.base = a.get<int>(B);
     s.cscore = a.get<float>((size_t)B * kcap);
     s.clc = a.get<int>((size_t)B * kcap);
     s.cpix = a.get<int>((size_t)B * kcap);
-    s.kslot = a.get<int>((size_t)B * kcap);
-    s.nkept = a.get<int>(B);
+    s.cut.carve(a, B, kcap);
     s.status = a.get<int>(1);
     s.total = a.off;
     s.ok = a.ok;
@@ -518,15 +514,13 @@ static int d2_detect_level(imcui_hip_t* h, const D2Ws& s, const float* feat, int
     hipLaunchKernelGGL(d2_detect_kernel, dim3((unsigned)((total + 3) / 4)), dim3(256), 0, stream, feat, fh, fw, C, ban_prev, ph, pw,
                        ban_prev ? (float)ph / (float)fh : 0.0f, ban_prev ? (float)pw / (float)fw : 0.0f, ban_out, s.planes, total);
     IMCUI_CHECK_LAUNCH(h);
-    const int dom = npix * C, nchunk = cdiv(dom, SEL_CHUNK);
+    const int dom = npix * C;
     const D2Pred pred{s.planes, nullptr, npix, C / 64};
     const D2Emit emit{s.base, feat, s.cscore, s.clc, s.cpix, kcap, level, npix, C};
     // (the `map` argument of the shared kernels is read at a candidate's index and handed to the emit functor, which ignores it: the
     // level's own maps have exactly `dom` floats per image)
-    hipLaunchKernelGGL((cand_count_kernel<D2Pred>), dim3(nchunk, B), dim3(256), 0, stream, feat, dom, pred, s.blkcnt, nchunk);
-    hipLaunchKernelGGL((exclusive_scan_kernel<int>), dim3(B), dim3(1024), 0, stream, s.blkcnt, s.blkoff, s.nlev, (const int*)nullptr, nchunk, (long)nchunk);
-    hipLaunchKernelGGL((cand_compact_kernel<D2Pred, D2Emit>), dim3(nchunk, B), dim3(256), 0, stream, feat, dom, pred, s.blkoff, nchunk, dom, emit);
-    hipLaunchKernelGGL(advance_base_kernel<>, dim3(cdiv(B, 256)), dim3(256), 0, stream, s.base, s.nlev, B);
+    cand_list(stream, feat, dom, B, pred, s.scan, dom, emit);
+    hipLaunchKernelGGL(advance_base_kernel<>, dim3(cdiv(B, 256)), dim3(256), 0, stream, s.base, s.scan.total, B);
     IMCUI_CHECK_LAUNCH(h);
     return IMCUI_OK;
 }
@@ -578,15 +572,14 @@ extern "C" int imcui_hip_d2net_forward(imcui_hip_t* h, const float* packed, cons
                                d2_ac_scale(ph, fh), d2_ac_scale(pw, fw), nf / 4);
             IMCUI_CHECK_LAUNCH(h);
         }
-        if (dbg_feat) hipMemcpyAsync(dbg_feat + off, f, nf * sizeof(float), hipMemcpyDeviceToDevice, stream);
+        copy_if(dbg_feat ? dbg_feat + off : nullptr, f, nf * sizeof(float), stream);
         IMCUI_RUN(d2_detect_level(h, s, f, B, fh, fw, D2_DIM, lev, lev > 0 ? s.ban[(lev - 1) & 1] : nullptr, ph, pw, s.ban[lev & 1], kcap, stream));
         off += nf;
         ph = fh;
         pw = fw;
     }
-    hipLaunchKernelGGL(cand_cut_kernel<>, dim3(B), dim3(1024), 0, stream, s.cscore, s.base, kcap, max_keypoints, s.kslot, s.nkept, st);
-    hipLaunchKernelGGL(d2_emit_kernel, dim3(cdiv(kout, 256), B), dim3(256), 0, stream, s.cscore, s.clc, s.cpix, s.feat, s.kslot, s.nkept, kcap, kout, lv,
-                       D2_DIM, keypoints, scores, descriptors, num_keypoints);
+    cand_cut(stream, s.cscore, s.base, kcap, max_keypoints, s.cut, st, B);
+    ranked_rows(stream, s.cscore, kcap, s.cut, kout, num_keypoints, D2Row{s.clc, s.cpix, s.feat, kcap, kout, lv, D2_DIM, keypoints, scores, descriptors}, B);
     IMCUI_CHECK_LAUNCH(h);
     return IMCUI_OK;
 }
@@ -644,9 +637,8 @@ extern "C" int imcui_hip_d2net_detect_probe(imcui_hip_t* h, const float* feat, i
     lv.h[0] = fh;
     lv.w[0] = fw;
     IMCUI_RUN(d2_detect_level(h, s, feat, B, fh, fw, C, 0, nullptr, 0, 0, s.ban[0], kcap, stream));
-    hipLaunchKernelGGL(cand_cut_kernel<>, dim3(B), dim3(1024), 0, stream, s.cscore, s.base, kcap, max_keypoints, s.kslot, s.nkept, st);
-    hipLaunchKernelGGL(d2_emit_kernel, dim3(cdiv(kout, 256), B), dim3(256), 0, stream, s.cscore, s.clc, s.cpix, feat, s.kslot, s.nkept, kcap, kout, lv, C,
-                       keypoints, scores, descriptors, num_keypoints);
+    cand_cut(stream, s.cscore, s.base, kcap, max_keypoints, s.cut, st, B);
+    ranked_rows(stream, s.cscore, kcap, s.cut, kout, num_keypoints, D2Row{s.clc, s.cpix, feat, kcap, kout, lv, C, keypoints, scores, descriptors}, B);
     IMCUI_CHECK_LAUNCH(h);
     return IMCUI_OK;
 }

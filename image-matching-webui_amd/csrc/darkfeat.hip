@@ -18,9 +18,9 @@
 //   score       df_clf_kernel (soft-max(clf(desc^2))[1] at the 1/4 resolution it lives at) and df_score_kernel: the align_corners=True
 //               up-samplings of the three level maps and of that map, the weights 1/6, 2/6, 3/6 and the product, one float per pixel
 //   detector    df_detect_kernel: score > thld, 3x3 maximum, border band, dilation-3 Hessian edge test (IEEE, no FMA: build.py compiles
-//               this file with -ffp-contract=off) -> the score where all hold, -inf elsewhere; select.h count / scan / compact in
-//               row-major order over a list that holds every pixel; cand_cut_kernel to min(kpt_n, max_keypoints or all);
-//               kept_rank_ascending: ascending stable (score, pixel) order
+//               this file with -ffp-contract=off) -> the score where all hold, -inf elsewhere; select.h cand_list in row-major order
+//               over a list that holds every pixel; cand_cut to min(kpt_n, max_keypoints or all); ranked_rows_kernel with DfRow:
+//               ascending stable (score, pixel) order
 //   describe    one wave per key-point: ASLFeat's bilinear rule on the 1/4-resolution map (floor / ceil corners clamped, weights from the
 //               unclamped fractions), d / max(|d|, 1e-12)
 // Fixed summation orders, no float atomics, grids sized by shapes or capacities: a row's bits do not depend on its batch or on replay;
@@ -480,28 +480,27 @@ struct DfPred {
     __device__ bool operator()(const float* img, int idx) const { return img[idx] > -INFINITY; }
 };
 
-// One workgroup = 256 kept candidates: the rank of each in ascending (score, pixel) order, then its row: (x, y) and the score.  Rows
-// past the count are zero.
-__global__ __launch_bounds__(256) void df_emit_kernel(const float* __restrict__ cscore, const int* __restrict__ cidx, const int* __restrict__ kslot,
-                                                      const int* __restrict__ nkept, int np, int W, int kout, float* __restrict__ kpts,
-                                                      float* __restrict__ scores, int* __restrict__ nkpts) {
-    const int b = blockIdx.y, tid = threadIdx.x;
-    const float* cs = cscore + (long)b * np;
-    const int* ks = kslot + (long)b * np;
-    const int n = min(nkept[b], kout);
-    if (blockIdx.x == 0 && tid == 0) nkpts[b] = n;
-    float* kp = kpts + (long)b * kout * 2;
-    float* sc = scores + (long)b * kout;
-    const int i0 = blockIdx.x * 256, i = i0 + tid;
-    if (i < kout && i >= n) kp[2 * i] = kp[2 * i + 1] = sc[i] = 0.0f;
-    if (i0 >= n) return;  // (uniform)
-    const int r = kept_rank_ascending(cs, ks, n, i);
-    if (i >= n) return;
-    const int slot = ks[i], pix = cidx[(long)b * np + slot];
-    kp[2 * r] = (float)(pix % W);
-    kp[2 * r + 1] = (float)(pix / W);
-    sc[r] = cs[slot];
-}
+// The rows of ranked_rows_kernel (ascending (score, pixel) order), one thread each: (x, y) and the score.  Rows past the count are zero.
+struct DfRow {
+    const int* cidx;
+    int np, W, kout;
+    float *kpts, *scores;
+    __device__ void clear(int b, int lo, int hi) const {
+        const int i = lo + threadIdx.x;
+        if (i >= hi) return;
+        float* kp = kpts + (long)b * kout * 2;
+        kp[2 * i] = kp[2 * i + 1] = scores[(long)b * kout + i] = 0.0f;
+    }
+    __device__ void emit(int b, int i0, int m, const int* ks, const int* rank, const float* cs) const {
+        const int j = threadIdx.x;
+        if (j >= m) return;
+        const int slot = ks[i0 + j], r = rank[j], pix = cidx[(long)b * np + slot];
+        float* kp = kpts + (long)b * kout * 2;
+        kp[2 * r] = (float)(pix % W);
+        kp[2 * r + 1] = (float)(pix / W);
+        scores[(long)b * kout + r] = cs[slot];
+    }
+};
 
 // ------------------------------------------------------------------ describe
 // One wave per key-point row (grid (cdiv(kcap, 4), B)): pos = (y, x) / 4 on the map dmap [B, h, w, 128]; corners floor / ceil clamped to
@@ -633,46 +632,34 @@ static int df_det_check(imcui_hip_t* h, const DfDet& d, int np, int max_keypoint
 }
 
 struct DfSel {
-    float *det, *cscore;
-    int *blkcnt, *blkoff, *ncand, *cidx, *kslot, *nkept;
+    float* det;
+    CandScan scan;
+    ScoreIndexList cand;  // (holds every pixel)
+    CutList cut;
 };
 static void df_carve_sel(WsAlloc& a, DfSel& s, int B, int np) {
-    const size_t nchunk = ((size_t)np + SEL_CHUNK - 1) / SEL_CHUNK;
     s.det = a.get<float>((size_t)B * np);
-    s.blkcnt = a.get<int>(B * nchunk);
-    s.blkoff = a.get<int>(B * nchunk);
-    s.ncand = a.get<int>(B);
-    s.cscore = a.get<float>((size_t)B * np);
-    s.cidx = a.get<int>((size_t)B * np);
-    s.kslot = a.get<int>((size_t)B * np);
-    s.nkept = a.get<int>(B);
+    s.scan.carve(a, B, (size_t)np);
+    s.cand.carve(a, B, np);
+    s.cut.carve(a, B, np);
 }
 // the detector on score [B, H, W], the candidate list (every pixel fits: it cannot overflow), the cut, the ranked rows
 static int df_detect(imcui_hip_t* h, const DfSel& s, const float* score, const int* flat, int B, int H, int W, const DfDet& d, int max_keypoints, int kout,
                      float* keypoints, float* scores, int* num_keypoints, int* status, hipStream_t stream) {
-    const int np = H * W, nchunk = cdiv(np, SEL_CHUNK);
+    const int np = H * W;
     const long npix = (long)B * np;
     const float ethr = (float)(((double)d.edge_thld + 1.0) * ((double)d.edge_thld + 1.0) / (double)d.edge_thld);
     const int limit = max_keypoints > 0 ? std::min(max_keypoints, d.kpt_n) : d.kpt_n;
-    const DfPred pred;
-    const EmitScoreIndex emit{s.cscore, s.cidx, np};
     hipLaunchKernelGGL(df_detect_kernel, dim3(blocks_256(npix)), dim3(256), 0, stream, score, flat, H, W, d.score_thld, d.nms_size, d.eof_mask, ethr, s.det, npix);
-    hipLaunchKernelGGL((cand_count_kernel<DfPred>), dim3(nchunk, B), dim3(256), 0, stream, s.det, np, pred, s.blkcnt, nchunk);
-    hipLaunchKernelGGL((exclusive_scan_kernel<int>), dim3(B), dim3(1024), 0, stream, s.blkcnt, s.blkoff, s.ncand, (const int*)nullptr, nchunk, (long)nchunk);
-    hipLaunchKernelGGL((cand_compact_kernel<DfPred, EmitScoreIndex>), dim3(nchunk, B), dim3(256), 0, stream, s.det, np, pred, s.blkoff, nchunk, np, emit);
-    hipLaunchKernelGGL(cand_cut_kernel<>, dim3(B), dim3(1024), 0, stream, s.cscore, s.ncand, np, limit, s.kslot, s.nkept, status);
-    hipLaunchKernelGGL(df_emit_kernel, dim3(cdiv(kout, 256), B), dim3(256), 0, stream, s.cscore, s.cidx, s.kslot, s.nkept, np, W, kout, keypoints, scores,
-                       num_keypoints);
+    cand_list(stream, s.det, np, B, DfPred{}, s.scan, np, s.cand.emit());
+    cand_cut(stream, s.cand.cscore, s.scan.total, np, limit, s.cut, status, B);
+    ranked_rows(stream, s.cand.cscore, np, s.cut, kout, num_keypoints, DfRow{s.cand.cidx, np, W, kout, keypoints, scores}, B);
     IMCUI_CHECK_LAUNCH(h);
     return IMCUI_OK;
 }
 
 static void df_describe(const float* dmap, int h4, int w4, const float* kpts, const int* nkpts, int nprobe, int kcap, int B, float* desc, hipStream_t stream) {
     hipLaunchKernelGGL(df_describe_kernel, dim3(cdiv(kcap, 4), B), dim3(256), 0, stream, dmap, h4, w4, kpts, nkpts, nprobe, kcap, desc);
-}
-
-static void df_copy(void* dst, const void* src, size_t bytes, hipStream_t stream) {
-    if (dst) hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, stream);
 }
 
 struct DfWs {
@@ -767,21 +754,21 @@ extern "C" int imcui_hip_darkfeat_forward(imcui_hip_t* h, const float* packed, c
             cur = dst;
         }
         const size_t nmap = (size_t)B * hh * ww * L.cout * sizeof(float);
-        if (i == dbg_layer) df_copy(dbg_raw, cur, nmap, stream);
+        if (i == dbg_layer) copy_if(dbg_raw, cur, nmap, stream);
         if (L.tap >= 0) IMCUI_RUN(df_peak(h, cur, P + l.hdr + 1 + L.tap, s.pk[L.tap], B, hh, ww, L.cout, DF_DIL[L.tap], stream));
         if (L.norm) IMCUI_RUN(df_inorm(h, cur, cur, B, hh * ww, L.cout, s.inpart, s.stat, stream));
-        if (i == dbg_layer) df_copy(dbg_norm, cur, nmap, stream);
+        if (i == dbg_layer) copy_if(dbg_norm, cur, nmap, stream);
     }
     const float* dmap = cur;  // [B, h4, w4, 128]
     const int h1 = df_down(H), w1 = df_down(W), h4 = hh, w4 = ww;
     // ---- score, detector, descriptors
     IMCUI_RUN(df_assemble(h, l, P, s.pk[0], s.pk[1], s.pk[2], dmap, B, H, W, s.prob, s.score, stream));
-    df_copy(dbg_score, s.score, (size_t)B * H * W * sizeof(float), stream);
-    df_copy(dbg_desc, dmap, (size_t)B * h4 * w4 * DF_DIM * sizeof(float), stream);
-    df_copy(dbg_peak0, s.pk[0], (size_t)B * H * W * sizeof(float), stream);
-    df_copy(dbg_peak1, s.pk[1], (size_t)B * h1 * w1 * sizeof(float), stream);
-    df_copy(dbg_peak2, s.pk[2], (size_t)B * h4 * w4 * sizeof(float), stream);
-    df_copy(dbg_prob, s.prob, (size_t)B * h4 * w4 * sizeof(float), stream);
+    copy_if(dbg_score, s.score, (size_t)B * H * W * sizeof(float), stream);
+    copy_if(dbg_desc, dmap, (size_t)B * h4 * w4 * DF_DIM * sizeof(float), stream);
+    copy_if(dbg_peak0, s.pk[0], (size_t)B * H * W * sizeof(float), stream);
+    copy_if(dbg_peak1, s.pk[1], (size_t)B * h1 * w1 * sizeof(float), stream);
+    copy_if(dbg_peak2, s.pk[2], (size_t)B * h4 * w4 * sizeof(float), stream);
+    copy_if(dbg_prob, s.prob, (size_t)B * h4 * w4 * sizeof(float), stream);
     IMCUI_RUN(df_detect(h, s.sel, s.score, s.flat, B, H, W, det, max_keypoints, kout, keypoints, scores, num_keypoints, st, stream));
     df_describe(dmap, h4, w4, keypoints, num_keypoints, 0, kout, B, descriptors, stream);
     IMCUI_CHECK_LAUNCH(h);
@@ -837,7 +824,7 @@ extern "C" int imcui_hip_darkfeat_inorm_probe(imcui_hip_t* h, const float* x, in
     if (!x || !out) return imcui_set_err(h, IMCUI_ERR_ARG, "darkfeat inorm probe: null argument");
     int rc;
     IMCUI_RUN(df_inorm(h, x, out, B, H * W, C, s.part, s.stat, stream));
-    df_copy(stat, s.stat, (size_t)B * C * 2 * sizeof(float), stream);
+    copy_if(stat, s.stat, (size_t)B * C * 2 * sizeof(float), stream);
     return IMCUI_OK;
 }
 // the peakiness pass on x [B, H, W, C] with dilation d and the divisor *mavg (device) -> out [B, H, W]
@@ -864,8 +851,8 @@ extern "C" int imcui_hip_darkfeat_detect_probe(imcui_hip_t* h, const float* scor
     if (!score || !keypoints || !scores || !num_keypoints || !status) return imcui_set_err(h, IMCUI_ERR_ARG, "darkfeat detect probe: null argument");
     hipLaunchKernelGGL(zero_i32_kernel<>, dim3(1), dim3(64), 0, stream, status, 1);
     IMCUI_RUN(df_detect(h, s.sel, score, nullptr, B, H, W, det, max_keypoints, kout, keypoints, scores, num_keypoints, status, stream));
-    df_copy(det_map, s.sel.det, (size_t)B * H * W * sizeof(float), stream);
-    df_copy(num_candidates, s.sel.ncand, (size_t)B * sizeof(int), stream);
+    copy_if(det_map, s.sel.det, (size_t)B * H * W * sizeof(float), stream);
+    copy_if(num_candidates, s.sel.scan.total, (size_t)B * sizeof(int), stream);
     return IMCUI_OK;
 }
 // describe on a given 1/4-resolution map dmap [B, h4, w4, 128] at keypoints [B, K, 2] (x, y in image pixels), nkpts [B] -> [B, K, 128]

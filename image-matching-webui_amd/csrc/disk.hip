@@ -402,16 +402,11 @@ __global__ __launch_bounds__(1024) void dk_select_kernel(const float* __restrict
 
 // The detection stage as `forward` launches it, on the heat map: status memset, count / scan / compact of the NMS survivors, selection.
 // The one launcher of both imcui_hip_disk_forward and the test entry imcui_hip_disk_select_probe.
-static int dk_select_launch(imcui_hip_t* h, const float* heat, int B, int H, int W, int window, float threshold, int max_keypoints, int kcap, int ccap, int* blkcnt,
-                            int* blkoff, int* ncand, float* cscore, int* cidx, float* keypoints, float* scores, int* num_keypoints, int* st, hipStream_t stream) {
+static int dk_select_launch(imcui_hip_t* h, const float* heat, int B, int H, int W, int window, float threshold, int max_keypoints, int kcap,
+                            const CandScan& scan, const ScoreIndexList& c, float* keypoints, float* scores, int* num_keypoints, int* st, hipStream_t stream) {
     hipMemsetAsync(st, 0, sizeof(int), stream);
-    const int nchunk = cdiv(H * W, SEL_CHUNK), r = window / 2;
-    const DkKeep keep{H, W, r, threshold};
-    hipLaunchKernelGGL(cand_count_kernel<DkKeep>, dim3(nchunk, B), dim3(256), 0, stream, heat, H * W, keep, blkcnt, nchunk);
-    hipLaunchKernelGGL(exclusive_scan_kernel<int>, dim3(B), dim3(1024), 0, stream, blkcnt, blkoff, ncand, (const int*)nullptr, nchunk, (long)nchunk);
-    hipLaunchKernelGGL((cand_compact_kernel<DkKeep, EmitScoreIndex>), dim3(nchunk, B), dim3(256), 0, stream, heat, H * W, keep, blkoff, nchunk, ccap,
-                       EmitScoreIndex{cscore, cidx, ccap});
-    hipLaunchKernelGGL(dk_select_kernel, dim3(B), dim3(1024), 0, stream, cscore, cidx, ccap, ncand, max_keypoints, kcap, W, keypoints, scores, num_keypoints, st);
+    cand_list(stream, heat, H * W, B, DkKeep{H, W, window / 2, threshold}, scan, c.cap, c.emit());
+    hipLaunchKernelGGL(dk_select_kernel, dim3(B), dim3(1024), 0, stream, c.cscore, c.cidx, c.cap, scan.total, max_keypoints, kcap, W, keypoints, scores, num_keypoints, st);
     IMCUI_CHECK_LAUNCH(h);
     return IMCUI_OK;
 }
@@ -458,9 +453,11 @@ __global__ __launch_bounds__(256) void dk_l2norm_kernel(float* __restrict__ desc
 
 // ------------------------------------------------------------------ workspace
 struct DkWs {
-    float *cat3, *cat2, *cat1, *cat0, *f5, *u0, *u1, *u2, *X, *pool, *mean, *rstd, *heat, *cscore, *gA;
+    float *cat3, *cat2, *cat1, *cat0, *f5, *u0, *u1, *u2, *X, *pool, *mean, *rstd, *heat, *gA;
     double* part;
-    int *blkcnt, *blkoff, *ncand, *cidx, *rows, *status;
+    CandScan scan;
+    ScoreIndexList cand;
+    int *rows, *status;
     size_t total;
     bool ok;
 };
@@ -485,12 +482,8 @@ static DkWs dk_carve(void* ws, size_t bytes, int B, int h, int w, int Hp, int Wp
     s.rstd = a.get<float>((size_t)B * 128);
     s.part = a.get<double>((size_t)B * cdiv((int)P0, DK_STAT_CHUNK) * 128 * 2);
     s.heat = a.get<float>((size_t)B * h * w);
-    const int nchunk = cdiv(h * w, SEL_CHUNK);
-    s.blkcnt = a.get<int>((size_t)B * nchunk);
-    s.blkoff = a.get<int>((size_t)B * nchunk);
-    s.ncand = a.get<int>(B);
-    s.cscore = a.get<float>((size_t)B * h * w);  // every pixel can be a candidate when window = 1
-    s.cidx = a.get<int>((size_t)B * h * w);
+    s.scan.carve(a, B, (size_t)h * w);
+    s.cand.carve(a, B, h * w);  // every pixel can be a candidate when window = 1
     s.gA = a.get<float>((size_t)B * DK_DESC_ROWS * 25 * 96);
     s.rows = a.get<int>(B);
     s.status = a.get<int>(1);
@@ -597,7 +590,7 @@ extern "C" int imcui_hip_disk_forward(imcui_hip_t* h, const float* packed, const
     float* heat = heatmap ? heatmap : s.heat;
     hipLaunchKernelGGL(dk_heat_kernel, dim3(cdiv(W, DK_HT), cdiv(H, DK_HT), B), dim3(256), 0, stream, s.X, P + l.hw, P + l.hb, heat, H, W, Hp, Wp);
     IMCUI_CHECK_LAUNCH(h);
-    IMCUI_RUN(dk_select_launch(h, heat, B, H, W, window, threshold, max_keypoints, kcap, H * W, s.blkcnt, s.blkoff, s.ncand, s.cscore, s.cidx, keypoints, scores,
+    IMCUI_RUN(dk_select_launch(h, heat, B, H, W, window, threshold, max_keypoints, kcap, s.scan, s.cand, keypoints, scores,
                                num_keypoints, status ? status : s.status, stream));
     // ---- descriptors at the selected pixels: gather the windows, [rows, 2400] x [2400, 128] + bias, L2 norm
     const int L = DK_NL - 1;
@@ -627,20 +620,16 @@ extern "C" int imcui_hip_disk_forward(imcui_hip_t* h, const float* packed, const
 
 // test entry: the detection stage alone, through the launcher `forward` calls, on a heat map given by the caller
 struct DkSelWs {
-    int *blkcnt, *blkoff, *ncand, *cidx;
-    float* cscore;
+    CandScan scan;
+    ScoreIndexList cand;
     size_t total;
     bool ok;
 };
 static DkSelWs dk_select_carve(void* ws, size_t bytes, int B, int H, int W, int ccap) {
     WsAlloc a(ws, bytes);
     DkSelWs s;
-    const int nchunk = cdiv(H * W, SEL_CHUNK);
-    s.blkcnt = a.get<int>((size_t)B * nchunk);
-    s.blkoff = a.get<int>((size_t)B * nchunk);
-    s.ncand = a.get<int>(B);
-    s.cscore = a.get<float>((size_t)B * ccap);
-    s.cidx = a.get<int>((size_t)B * ccap);
+    s.scan.carve(a, B, (size_t)H * W);
+    s.cand.carve(a, B, ccap);
     s.total = a.off;
     s.ok = a.ok;
     return s;
@@ -660,6 +649,6 @@ extern "C" int imcui_hip_disk_select_probe(imcui_hip_t* h, const float* heat, in
     if (!heat || !keypoints || !scores || !num_keypoints || !status) return imcui_set_err(h, IMCUI_ERR_ARG, "disk select probe: null argument");
     DkSelWs s = dk_select_carve(ws, ws_bytes, B, H, W, ccap);
     if (!ws || !s.ok) return imcui_set_err(h, IMCUI_ERR_WS, "disk select probe: workspace too small (%zu < %zu)", ws_bytes, s.total);
-    return dk_select_launch(h, heat, B, H, W, window, threshold, max_keypoints, kcap, ccap, s.blkcnt, s.blkoff, s.ncand, s.cscore, s.cidx, keypoints, scores,
+    return dk_select_launch(h, heat, B, H, W, window, threshold, max_keypoints, kcap, s.scan, s.cand, keypoints, scores,
                             num_keypoints, status, (hipStream_t)stream_);
 }

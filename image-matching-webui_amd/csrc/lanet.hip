@@ -11,8 +11,8 @@
 //   tail        one wave per cell: the 256 -> 4 and 256 -> 2 3x3 layers on the two hidden maps, soft-max of channels 0..2 (aware),
 //               sigmoid of channel 3 with the border cells multiplied by 0 (score), tanh and the cell-relative position (coord).  The
 //               6-channel maps are not written.
-//   selection   score > threshold in row-major cell order (select.h count / scan / compact), the cut and the ascending stable rank
-//               R2D2 and D2-Net use (cand_cut_kernel, kept_rank_ascending); the list holds every cell, so it cannot overflow
+//   selection   score > threshold in row-major cell order (select.h cand_list), the cut and the ascending stable rank
+//               R2D2 and D2-Net use (cand_cut, ranked_rows_kernel with LaRow); the list holds every cell, so it cannot overflow
 //   descriptor  only at the kept key-points.  des_conv2(x2) and des_conv3(x3) are never written: convolution, folded BatchNorm and
 //               bilinear sampling are linear, so the k x k x C neighbourhoods of the up to four corners grid_sample touches are blended
 //               into one patch per key-point and level and that patch is multiplied by the level's [k k C][256] weights on
@@ -322,37 +322,36 @@ struct LaPred {
     __device__ bool operator()(const float* img, int idx) const { return img[idx] > thr; }
 };
 
-// One workgroup = 256 kept candidates: the rank of each in ascending (score, cell) order (lanet.py:54 with equal scores in cell order),
-// then its row: key-point, score and the cell's level weights (kaw, for the descriptor kernel).  Rows past the count are zero.
-__global__ __launch_bounds__(256) void la_emit_kernel(const float* __restrict__ cscore, const int* __restrict__ cidx, const float* __restrict__ coord,
-                                                      const float* __restrict__ aware, const int* __restrict__ kslot, const int* __restrict__ nkept, int np,
-                                                      int kout, float* __restrict__ kpts, float* __restrict__ scores, float* __restrict__ kaw,
-                                                      int* __restrict__ nkpts) {
-    const int b = blockIdx.y, tid = threadIdx.x;
-    const float* cs = cscore + (long)b * np;
-    const int* ks = kslot + (long)b * np;
-    const int n = min(nkept[b], kout);
-    if (blockIdx.x == 0 && tid == 0) nkpts[b] = n;
-    float* kp = kpts + (long)b * kout * 2;
-    float* sc = scores + (long)b * kout;
-    float* ka = kaw + (long)b * kout * 3;
-    const int i0 = blockIdx.x * 256, i = i0 + tid;
-    if (i < kout && i >= n) {
-        kp[2 * i] = kp[2 * i + 1] = sc[i] = 0.0f;
+// The rows of ranked_rows_kernel (ascending (score, cell) order: lanet.py:54 with equal scores in cell order), one thread each:
+// key-point, score and the cell's level weights (kaw, for the descriptor kernel).  Rows past the count are zero.
+struct LaRow {
+    const int* cidx;
+    const float *coord, *aware;
+    int np, kout;
+    float *kpts, *scores, *kaw;
+    __device__ void clear(int b, int lo, int hi) const {
+        const int i = lo + threadIdx.x;
+        if (i >= hi) return;
+        float* kp = kpts + (long)b * kout * 2;
+        float* ka = kaw + (long)b * kout * 3;
+        kp[2 * i] = kp[2 * i + 1] = scores[(long)b * kout + i] = 0.0f;
         ka[3 * i] = ka[3 * i + 1] = ka[3 * i + 2] = 0.0f;
     }
-    if (i0 >= n) return;  // (uniform)
-    const int r = kept_rank_ascending(cs, ks, n, i);
-    if (i >= n) return;
-    const int slot = ks[i];
-    const long cell = (long)b * np + cidx[(long)b * np + slot];
-    kp[2 * r] = coord[2 * cell];
-    kp[2 * r + 1] = coord[2 * cell + 1];
-    sc[r] = cs[slot];
-    ka[3 * r] = aware[3 * cell];
-    ka[3 * r + 1] = aware[3 * cell + 1];
-    ka[3 * r + 2] = aware[3 * cell + 2];
-}
+    __device__ void emit(int b, int i0, int m, const int* ks, const int* rank, const float* cs) const {
+        const int j = threadIdx.x;
+        if (j >= m) return;
+        const int slot = ks[i0 + j], r = rank[j];
+        const long cell = (long)b * np + cidx[(long)b * np + slot];
+        float* kp = kpts + (long)b * kout * 2;
+        float* ka = kaw + (long)b * kout * 3;
+        kp[2 * r] = coord[2 * cell];
+        kp[2 * r + 1] = coord[2 * cell + 1];
+        scores[(long)b * kout + r] = cs[slot];
+        ka[3 * r] = aware[3 * cell];
+        ka[3 * r + 1] = aware[3 * cell + 1];
+        ka[3 * r + 2] = aware[3 * cell + 2];
+    }
+};
 
 // ------------------------------------------------------------------ the sparse level-aware descriptor head
 // F.grid_sample(map [h, w], g) at its defaults (bilinear, zeros, align_corners=False) for the key-point at pixel position c of the
@@ -567,8 +566,11 @@ static int la_stem(imcui_hip_t* h, const LaCfg& c, const LaLayout& l, const floa
 }
 
 struct LaWs {
-    float *fa, *fb, *x2, *x3, *x4, *s1, *p1, *score, *coord, *tanhv, *aware, *cscore, *kaw;
-    int *blkcnt, *blkoff, *ncand, *cidx, *kslot, *nkept, *status;
+    float *fa, *fb, *x2, *x3, *x4, *s1, *p1, *score, *coord, *tanhv, *aware, *kaw;
+    CandScan scan;
+    ScoreIndexList cand;  // (holds every cell)
+    CutList cut;
+    int* status;
     size_t total;
     bool ok;
 };
@@ -596,14 +598,9 @@ static LaWs la_carve(void* ws, size_t bytes, const LaCfg* c, int B, int H, int W
     s.coord = a.get<float>(B * np * 2);
     s.tanhv = a.get<float>(B * np * 2);
     s.aware = a.get<float>(B * np * 3);
-    const size_t nchunk = (np + SEL_CHUNK - 1) / SEL_CHUNK;
-    s.blkcnt = a.get<int>(B * nchunk);
-    s.blkoff = a.get<int>(B * nchunk);
-    s.ncand = a.get<int>(B);
-    s.cscore = a.get<float>(B * np);
-    s.cidx = a.get<int>(B * np);
-    s.kslot = a.get<int>(B * np);
-    s.nkept = a.get<int>(B);
+    s.scan.carve(a, B, np);
+    s.cand.carve(a, B, (int)np);
+    s.cut.carve(a, B, (int)np);
     s.kaw = a.get<float>((size_t)B * kout * 3);
     s.status = a.get<int>(1);
     s.total = a.off;
@@ -643,16 +640,10 @@ extern "C" size_t imcui_hip_lanet_select_workspace_bytes(int B, int Hc, int Wc, 
 // threshold compaction in cell order, the cut, the ranked rows
 static int la_select(imcui_hip_t* h, const LaWs& s, int B, int np, float threshold, int max_keypoints, int kout, float* keypoints, float* scores,
                      int* num_keypoints, int* st, hipStream_t stream) {
-    const int nchunk = cdiv(np, SEL_CHUNK);
-    const LaPred pred{threshold};
-    const EmitScoreIndex emit{s.cscore, s.cidx, np};
     hipLaunchKernelGGL(zero_i32_kernel<>, dim3(1), dim3(64), 0, stream, st, 1);
-    hipLaunchKernelGGL((cand_count_kernel<LaPred>), dim3(nchunk, B), dim3(256), 0, stream, s.score, np, pred, s.blkcnt, nchunk);
-    hipLaunchKernelGGL((exclusive_scan_kernel<int>), dim3(B), dim3(1024), 0, stream, s.blkcnt, s.blkoff, s.ncand, (const int*)nullptr, nchunk, (long)nchunk);
-    hipLaunchKernelGGL((cand_compact_kernel<LaPred, EmitScoreIndex>), dim3(nchunk, B), dim3(256), 0, stream, s.score, np, pred, s.blkoff, nchunk, np, emit);
-    hipLaunchKernelGGL(cand_cut_kernel<>, dim3(B), dim3(1024), 0, stream, s.cscore, s.ncand, np, max_keypoints, s.kslot, s.nkept, st);
-    hipLaunchKernelGGL(la_emit_kernel, dim3(cdiv(kout, 256), B), dim3(256), 0, stream, s.cscore, s.cidx, s.coord, s.aware, s.kslot, s.nkept, np, kout, keypoints,
-                       scores, s.kaw, num_keypoints);
+    cand_list(stream, s.score, np, B, LaPred{threshold}, s.scan, np, s.cand.emit());
+    cand_cut(stream, s.cand.cscore, s.scan.total, np, max_keypoints, s.cut, st, B);
+    ranked_rows(stream, s.cand.cscore, np, s.cut, kout, num_keypoints, LaRow{s.cand.cidx, s.coord, s.aware, np, kout, keypoints, scores, s.kaw}, B);
     IMCUI_CHECK_LAUNCH(h);
     return IMCUI_OK;
 }
@@ -662,10 +653,6 @@ static void la_desc(const LaCfg& c, const LaLayout& l, const float* P, const flo
     const LaLevel L2{x2, P + l.dw[0], P + l.db[0], h2, w2, c.c[2], c.k[0]}, L3{x3, P + l.dw[1], P + l.db[1], h3, w3, c.c[3], c.k[1]};
     hipLaunchKernelGGL(la_desc_kernel, dim3(std::min(cdiv(kcap, LA_KB), 1024), B), dim3(256), 0, stream, L2, L3, x4, h4, w4, coords, aw, nkpts, nprobe, kcap, H, W,
                        desc);
-}
-
-static void la_copy(float* dst, const float* src, size_t n, hipStream_t stream) {
-    if (dst) hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyDeviceToDevice, stream);
 }
 
 extern "C" int imcui_hip_lanet_forward(imcui_hip_t* h, const int* cfg, const float* packed, const float* image, int B, int H, int W, float threshold,
@@ -712,13 +699,13 @@ extern "C" int imcui_hip_lanet_forward(imcui_hip_t* h, const int* cfg, const flo
     hipLaunchKernelGGL(la_tail_kernel, dim3((unsigned)((ncell + 3) / 4)), dim3(256), 0, stream, s.s1, s.p1, P + l.tws, P + l.twp, P + l.tb, Hc, Wc, H, W, s.score,
                        s.coord, s.tanhv, s.aware, ncell);
     IMCUI_CHECK_LAUNCH(h);
-    la_copy(dbg_x2, s.x2, (size_t)B * (H / 2) * (W / 2) * c.c[2], stream);
-    la_copy(dbg_x3, s.x3, (size_t)B * (H / 4) * (W / 4) * c.c[3], stream);
-    la_copy(dbg_x4, s.x4, (size_t)ncell * LA_DIM, stream);
-    la_copy(dbg_score, s.score, ncell, stream);
-    la_copy(dbg_coord, s.coord, ncell * 2, stream);
-    la_copy(dbg_aware, s.aware, ncell * 3, stream);
-    la_copy(dbg_tanh, s.tanhv, ncell * 2, stream);
+    copy_if(dbg_x2, s.x2, (size_t)B * (H / 2) * (W / 2) * c.c[2] * sizeof(float), stream);
+    copy_if(dbg_x3, s.x3, (size_t)B * (H / 4) * (W / 4) * c.c[3] * sizeof(float), stream);
+    copy_if(dbg_x4, s.x4, (size_t)ncell * LA_DIM * sizeof(float), stream);
+    copy_if(dbg_score, s.score, ncell * sizeof(float), stream);
+    copy_if(dbg_coord, s.coord, ncell * 2 * sizeof(float), stream);
+    copy_if(dbg_aware, s.aware, ncell * 3 * sizeof(float), stream);
+    copy_if(dbg_tanh, s.tanhv, ncell * 2 * sizeof(float), stream);
     // ---- selection and descriptors
     IMCUI_RUN(la_select(h, s, B, np, threshold, max_keypoints, kout, keypoints, scores, num_keypoints, status ? status : s.status, stream));
     la_desc(c, l, P, s.x2, H / 2, W / 2, s.x3, H / 4, W / 4, s.x4, Hc, Wc, keypoints, s.kaw, num_keypoints, 0, kout, B, H, W, descriptors, stream);
@@ -773,10 +760,10 @@ extern "C" int imcui_hip_lanet_select_probe(imcui_hip_t* h, const float* raw, in
     const long ncell = (long)B * np;
     hipLaunchKernelGGL(la_decode_kernel, dim3(blocks_256(ncell)), dim3(256), 0, stream, raw, Hc, Wc, H, W, s.score, s.coord, s.tanhv, s.aware, ncell);
     IMCUI_CHECK_LAUNCH(h);
-    la_copy(dbg_score, s.score, ncell, stream);
-    la_copy(dbg_coord, s.coord, ncell * 2, stream);
-    la_copy(dbg_aware, s.aware, ncell * 3, stream);
-    la_copy(dbg_tanh, s.tanhv, ncell * 2, stream);
+    copy_if(dbg_score, s.score, ncell * sizeof(float), stream);
+    copy_if(dbg_coord, s.coord, ncell * 2 * sizeof(float), stream);
+    copy_if(dbg_aware, s.aware, ncell * 3 * sizeof(float), stream);
+    copy_if(dbg_tanh, s.tanhv, ncell * 2 * sizeof(float), stream);
     return la_select(h, s, B, np, threshold, max_keypoints, kout, keypoints, scores, num_keypoints, status ? status : s.status, stream);
 }
 

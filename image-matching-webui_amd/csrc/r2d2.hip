@@ -277,43 +277,41 @@ __device__ __forceinline__ float2 r2_normalize(float2 v) {
     return make_float2(v.x / d, v.y / d);
 }
 
-// One workgroup = 256 kept candidates: the rank of each in ascending (score, slot) order (the kept list is in slot order), then one wave
-// per key-point: x W / nw, y H / nh as float32 (x * W) / nw, the score, the normalised parked vector.  Rows past the count are zero.
-__global__ __launch_bounds__(256) void r2_emit_kernel(const float* __restrict__ cscore, const int* __restrict__ clev, const int* __restrict__ cidx,
-                                                      const float* __restrict__ cvec, const int* __restrict__ kslot, const int* __restrict__ nkept,
-                                                      int kcap, int kout, R2Levels lv, int H, int W, float* __restrict__ kpts,
-                                                      float* __restrict__ scores, float* __restrict__ desc, int* __restrict__ nkpts) {
-    __shared__ int rank_s[256];
-    const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const float* cs = cscore + (long)b * kcap;
-    const int* ks = kslot + (long)b * kcap;
-    const int n = min(nkept[b], kout);
-    if (blockIdx.x == 0 && tid == 0) nkpts[b] = n;
-    float* kp = kpts + (long)b * kout * 2;
-    float* sc = scores + (long)b * kout;
-    float* de = desc + (long)b * kout * R2_DIM;
-    const int i0 = blockIdx.x * 256;
-    for (int i = i0 + tid; i < min(i0 + 256, kout); i += 256)
-        if (i >= n) kp[2 * i] = kp[2 * i + 1] = sc[i] = 0.0f;
-    for (int i = i0 + wv; i < min(i0 + 256, kout); i += 4)
-        if (i >= n) *reinterpret_cast<float2*>(de + (long)i * R2_DIM + 2 * lane) = make_float2(0.0f, 0.0f);
-    if (i0 >= n) return;  // (uniform)
-    rank_s[tid] = kept_rank_ascending(cs, ks, n, i0 + tid);
-    __syncthreads();
-    for (int j = wv; j < min(256, n - i0); j += 4) {
-        const int slot = ks[i0 + j], r = rank_s[j];
-        const float2 v = r2_normalize(*reinterpret_cast<const float2*>(cvec + ((long)b * kcap + slot) * R2_DIM + 2 * lane));
-        *reinterpret_cast<float2*>(de + (long)r * R2_DIM + 2 * lane) = v;
-        if (lane == 0) {
-            const int l = clev[(long)b * kcap + slot], idx = cidx[(long)b * kcap + slot];
-            const int nw = lv.nw[l], nh = lv.nh[l];
-            const int y = idx / nw, x = idx - y * nw;
-            kp[2 * r] = __fdiv_rn(__fmul_rn((float)x, (float)W), (float)nw);
-            kp[2 * r + 1] = __fdiv_rn(__fmul_rn((float)y, (float)H), (float)nh);
-            sc[r] = cs[slot];
+// The rows of ranked_rows_kernel (ascending (score, slot) order: the kept list is in slot order), one wave each: x W / nw, y H / nh as
+// float32 (x * W) / nw, the score, the normalised parked vector.  Rows past the count are zero.
+struct R2Row {
+    const int *clev, *cidx;
+    const float* cvec;
+    int kcap, kout;
+    R2Levels lv;
+    int H, W;
+    float *kpts, *scores, *desc;
+    __device__ void clear(int b, int lo, int hi) const {
+        const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+        float* kp = kpts + (long)b * kout * 2;
+        float* de = desc + (long)b * kout * R2_DIM;
+        for (int i = lo + tid; i < hi; i += 256) kp[2 * i] = kp[2 * i + 1] = scores[(long)b * kout + i] = 0.0f;
+        for (int i = lo + wv; i < hi; i += 4) *reinterpret_cast<float2*>(de + (long)i * R2_DIM + 2 * lane) = make_float2(0.0f, 0.0f);
+    }
+    __device__ void emit(int b, int i0, int m, const int* ks, const int* rank, const float* cs) const {
+        const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+        float* kp = kpts + (long)b * kout * 2;
+        float* de = desc + (long)b * kout * R2_DIM;
+        for (int j = wv; j < m; j += 4) {
+            const int slot = ks[i0 + j], r = rank[j];
+            const float2 v = r2_normalize(*reinterpret_cast<const float2*>(cvec + ((long)b * kcap + slot) * R2_DIM + 2 * lane));
+            *reinterpret_cast<float2*>(de + (long)r * R2_DIM + 2 * lane) = v;
+            if (lane == 0) {
+                const int l = clev[(long)b * kcap + slot], idx = cidx[(long)b * kcap + slot];
+                const int nw = lv.nw[l], nh = lv.nh[l];
+                const int y = idx / nw, x = idx - y * nw;
+                kp[2 * r] = __fdiv_rn(__fmul_rn((float)x, (float)W), (float)nw);
+                kp[2 * r + 1] = __fdiv_rn(__fmul_rn((float)y, (float)H), (float)nh);
+                scores[(long)b * kout + r] = cs[slot];
+            }
         }
     }
-}
+};
 
 // test entry: F.normalize of the final map at n given pixels of one image
 __global__ __launch_bounds__(256) void r2_probe_kernel(const float* __restrict__ x, int w, const int* __restrict__ xy, int n, float* __restrict__ desc) {
@@ -329,7 +327,9 @@ __global__ __launch_bounds__(256) void r2_probe_kernel(const float* __restrict__
 // ------------------------------------------------------------------ workspace
 struct R2Ws {
     float *lev[2], *fa, *fb, *rel, *rep, *cscore, *cvec;
-    int *blkcnt, *blkoff, *nlev, *base, *clev, *cidx, *kslot, *nkept, *status;
+    CandScan scan;  // (total = this level's count)
+    CutList cut;
+    int *base, *clev, *cidx, *status;
     size_t total;
     bool ok;
 };
@@ -342,17 +342,13 @@ static R2Ws r2_carve(void* ws, size_t bytes, int B, size_t npix_max, int kcap) {
     s.fb = a.get<float>((size_t)B * npix_max * R2_DIM);
     s.rel = a.get<float>((size_t)B * npix_max);
     s.rep = a.get<float>((size_t)B * npix_max);
-    const size_t nchunk = (npix_max + SEL_CHUNK - 1) / SEL_CHUNK;
-    s.blkcnt = a.get<int>((size_t)B * nchunk);
-    s.blkoff = a.get<int>((size_t)B * nchunk);
-    s.nlev = a.get<int>(B);
+    s.scan.carve(a, B, npix_max);
     s.base = a.get<int>(B);
     s.cscore = a.get<float>((size_t)B * kcap);
     s.clev = a.get<int>((size_t)B * kcap);
     s.cidx = a.get<int>((size_t)B * kcap);
-    s.kslot = a.get<int>((size_t)B * kcap);
+    s.cut.carve(a, B, kcap);
     s.cvec = a.get<float>((size_t)B * kcap * R2_DIM);
-    s.nkept = a.get<int>(B);
     s.status = a.get<int>(1);
     s.total = a.off;
     s.ok = a.ok;
@@ -460,26 +456,22 @@ extern "C" int imcui_hip_r2d2_forward(imcui_hip_t* h, const float* packed, const
         hipLaunchKernelGGL(r2_head_kernel, dim3((unsigned)std::min<long>((np + 7) / 8, 65536)), dim3(256), 0, stream, s.fa, packed + l.hw, packed + l.hb, s.rel,
                            s.rep, np);
         IMCUI_CHECK_LAUNCH(h);
-        if (dbg_rel) hipMemcpyAsync(dbg_rel + dbg_off, s.rel, np * sizeof(float), hipMemcpyDeviceToDevice, stream);
-        if (dbg_rep) hipMemcpyAsync(dbg_rep + dbg_off, s.rep, np * sizeof(float), hipMemcpyDeviceToDevice, stream);
-        if (dbg_map) hipMemcpyAsync(dbg_map + dbg_off * R2_DIM, s.fa, np * R2_DIM * sizeof(float), hipMemcpyDeviceToDevice, stream);
+        copy_if(dbg_rel ? dbg_rel + dbg_off : nullptr, s.rel, np * sizeof(float), stream);
+        copy_if(dbg_rep ? dbg_rep + dbg_off : nullptr, s.rep, np * sizeof(float), stream);
+        copy_if(dbg_map ? dbg_map + dbg_off * R2_DIM : nullptr, s.fa, np * R2_DIM * sizeof(float), stream);
         dbg_off += (size_t)np;
         // ---- detector: this level's candidates append to the image's list
-        const int nchunk = cdiv(npix, SEL_CHUNK);
         const R2Pred pred{s.rel, nullptr, ch, cw, rel_thr, rep_thr};
         const R2Emit emit{s.base, s.rel, s.cscore, s.clev, s.cidx, kcap, lev, npix};
-        hipLaunchKernelGGL((cand_count_kernel<R2Pred>), dim3(nchunk, B), dim3(256), 0, stream, s.rep, npix, pred, s.blkcnt, nchunk);
-        hipLaunchKernelGGL((exclusive_scan_kernel<int>), dim3(B), dim3(1024), 0, stream, s.blkcnt, s.blkoff, s.nlev, (const int*)nullptr, nchunk, (long)nchunk);
-        hipLaunchKernelGGL((cand_compact_kernel<R2Pred, R2Emit>), dim3(nchunk, B), dim3(256), 0, stream, s.rep, npix, pred, s.blkoff, nchunk, npix, emit);
-        hipLaunchKernelGGL(r2_park_kernel, dim3(std::min(cdiv(std::min(npix, kcap), 4), 4096), B), dim3(256), 0, stream, s.fa, s.base, s.nlev, s.cidx, kcap, npix,
-                           s.cvec);
-        hipLaunchKernelGGL(advance_base_kernel<>,dim3(cdiv(B, 256)), dim3(256), 0, stream, s.base, s.nlev, B);
+        cand_list(stream, s.rep, npix, B, pred, s.scan, npix, emit);
+        hipLaunchKernelGGL(r2_park_kernel, dim3(std::min(cdiv(std::min(npix, kcap), 4), 4096), B), dim3(256), 0, stream, s.fa, s.base, s.scan.total, s.cidx, kcap,
+                           npix, s.cvec);
+        hipLaunchKernelGGL(advance_base_kernel<>,dim3(cdiv(B, 256)), dim3(256), 0, stream, s.base, s.scan.total, B);
         IMCUI_CHECK_LAUNCH(h);
     }
     // ---- cut + emit
-    hipLaunchKernelGGL(cand_cut_kernel<>,dim3(B), dim3(1024), 0, stream, s.cscore, s.base, kcap, max_keypoints, s.kslot, s.nkept, st);
-    hipLaunchKernelGGL(r2_emit_kernel, dim3(cdiv(kout, 256), B), dim3(256), 0, stream, s.cscore, s.clev, s.cidx, s.cvec, s.kslot, s.nkept, kcap, kout, lv, H, W,
-                       keypoints, scores, descriptors, num_keypoints);
+    cand_cut(stream, s.cscore, s.base, kcap, max_keypoints, s.cut, st, B);
+    ranked_rows(stream, s.cscore, kcap, s.cut, kout, num_keypoints, R2Row{s.clev, s.cidx, s.cvec, kcap, kout, lv, H, W, keypoints, scores, descriptors}, B);
     IMCUI_CHECK_LAUNCH(h);
     return IMCUI_OK;
 }

@@ -1,9 +1,12 @@
 // List-building blocks shared by the extractors and matchers: ordered candidate compaction over a score map, an exclusive scan, the
 // order-preserving float key, the radix select of the k-th largest key, the rank of a flagged thread inside its workgroup, the loop
-// that keeps the keys >= the k-th in list order, and the candidate list of the multi-scale extractors (zero, advance, cut, rank).
-// Device code only.  The RULES stay with their owners (sp_topk_kernel, dk_select_kernel, ak_select_kernel, xf_rank_kernel, al_cut_kernel,
-// dd_cut_kernel, r2_emit_kernel, d2_emit_kernel, ...): which candidates a network keeps, in which order and how ties fall differs per
-// network, and none of that is decided here; R2D2 and D2-Net share one rule (a stable argsort of (score, list index)) and hence one cut.
+// that keeps the keys >= the k-th in list order, and the candidate list of the multi-scale extractors (zero, advance, cut, rank, the
+// ranked rows).  Below the kernels, the host side of the same blocks: cand_chunks, the scratch they index (CandScan, ScoreIndexList,
+// CutList, each with its carve) and their launches (cand_count_scan, cand_compact, cand_list, cand_cut, ranked_rows).
+// The RULES stay with their owners (sp_topk_kernel, dk_select_kernel, ak_select_kernel, xf_rank_kernel, al_cut_kernel, dd_cut_kernel,
+// the Row functors of ranked_rows_kernel, ...): which candidates a network keeps, in which order and how ties fall differs per network,
+// and none of that is decided here; R2D2, D2-Net, LANet and DarkFeat share one rule (a stable argsort of (score, list index)) and hence
+// one cut and one rank.
 #pragma once
 #include "common.h"
 
@@ -285,6 +288,91 @@ __device__ __forceinline__ int kept_rank_ascending(const float* __restrict__ cs,
         }
     }
     return rank;
+}
+
+// The ranked rows of a cut list.  Grid (cdiv(kout, 256), B), 256 threads: one workgroup = 256 kept candidates of image b; n =
+// min(nkept[b], kout) rows leave, nkpts[b] = n (when asked for).  The rank needs every thread of the workgroup (it has barriers), so
+// a workgroup leaves only as a whole.  Every thread calls both members of Row, which shares the rows out (a thread or a wave each):
+//   void clear(int b, int lo, int hi) const   -- output rows [lo, hi) of this workgroup lie past the count
+//   void emit(int b, int i0, int m, const int* ks, const int* rank, const float* cs) const
+//        -- kept candidate i0 + j (j < m) sits in slot ks[i0 + j] with score cs[slot] and goes to output row rank[j] (LDS)
+template <class Row>
+__global__ __launch_bounds__(256) void ranked_rows_kernel(const float* __restrict__ cscore, const int* __restrict__ kslot, const int* __restrict__ nkept, int cap,
+                                                          int kout, int* __restrict__ nkpts, Row row) {
+    __shared__ int rank_s[256];
+    const int b = blockIdx.y, i0 = blockIdx.x * 256;
+    const float* cs = cscore + (long)b * cap;
+    const int* ks = kslot + (long)b * cap;
+    const int n = min(nkept[b], kout);
+    if (nkpts && blockIdx.x == 0 && threadIdx.x == 0) nkpts[b] = n;
+    row.clear(b, max(i0, n), min(i0 + 256, kout));
+    if (i0 >= n) return;  // (uniform)
+    rank_s[threadIdx.x] = kept_rank_ascending(cs, ks, n, i0 + threadIdx.x);
+    __syncthreads();
+    row.emit(b, i0, min(256, n - i0), ks, rank_s, cs);
+}
+
+// ------------------------------------------------------------------ host side: the scratch of the blocks above and their launches
+// One place that sizes, carves and passes what the kernels index with, so that the chunk count, the row stride and the capacity cannot
+// differ between a launch and its scratch.  The caller checks the launches (IMCUI_CHECK_LAUNCH), where the handle is.
+static inline int cand_chunks(long domain) { return (int)((domain + SEL_CHUNK - 1) / SEL_CHUNK); }
+
+// per-chunk counts, their exclusive scan and the per-image total, sized for the largest domain the owner scans
+struct CandScan {
+    int *blkcnt, *blkoff, *total;
+    void carve(WsAlloc& a, int B, size_t domain_max) {
+        const size_t n = (size_t)B * cand_chunks((long)domain_max);
+        blkcnt = a.get<int>(n);
+        blkoff = a.get<int>(n);
+        total = a.get<int>(B);
+    }
+};
+
+template <class Pred>
+static void cand_count_scan(hipStream_t stream, const float* map, int domain, int B, Pred pred, const CandScan& s) {
+    const int nchunk = cand_chunks(domain);
+    hipLaunchKernelGGL(cand_count_kernel<Pred>, dim3(nchunk, B), dim3(256), 0, stream, map, domain, pred, s.blkcnt, nchunk);
+    hipLaunchKernelGGL(exclusive_scan_kernel<int>, dim3(B), dim3(1024), 0, stream, s.blkcnt, s.blkoff, s.total, (const int*)nullptr, nchunk, (long)nchunk);
+}
+template <class Pred, class Emit>
+static void cand_compact(hipStream_t stream, const float* map, int domain, int B, Pred pred, const CandScan& s, int cap, Emit emit) {
+    const int nchunk = cand_chunks(domain);
+    hipLaunchKernelGGL((cand_compact_kernel<Pred, Emit>), dim3(nchunk, B), dim3(256), 0, stream, map, domain, pred, s.blkoff, nchunk, cap, emit);
+}
+template <class Pred, class Emit>
+static void cand_list(hipStream_t stream, const float* map, int domain, int B, Pred pred, const CandScan& s, int cap, Emit emit) {
+    cand_count_scan(stream, map, domain, B, pred, s);
+    cand_compact(stream, map, domain, B, pred, s, cap, emit);
+}
+
+// the list EmitScoreIndex fills, [B][cap] each
+struct ScoreIndexList {
+    float* cscore;
+    int* cidx;
+    int cap;
+    void carve(WsAlloc& a, int B, int cap_) {
+        cap = cap_;
+        cscore = a.get<float>((size_t)B * cap);
+        cidx = a.get<int>((size_t)B * cap);
+    }
+    EmitScoreIndex emit() const { return EmitScoreIndex{cscore, cidx, cap}; }
+};
+
+// what cand_cut_kernel leaves: kslot [B][cap], nkept [B]
+struct CutList {
+    int *kslot, *nkept;
+    void carve(WsAlloc& a, int B, int cap) {
+        kslot = a.get<int>((size_t)B * cap);
+        nkept = a.get<int>(B);
+    }
+};
+template <class = void>  // (as the kernel: only the translation units that call it carry a copy)
+static void cand_cut(hipStream_t stream, const float* cscore, const int* ntotal, int cap, int limit, const CutList& cut, int* status, int B) {
+    hipLaunchKernelGGL(cand_cut_kernel<>, dim3(B), dim3(1024), 0, stream, cscore, ntotal, cap, limit, cut.kslot, cut.nkept, status);
+}
+template <class Row>
+static void ranked_rows(hipStream_t stream, const float* cscore, int cap, const CutList& cut, int kout, int* nkpts, Row row, int B) {
+    hipLaunchKernelGGL(ranked_rows_kernel<Row>, dim3(cdiv(kout, 256), B), dim3(256), 0, stream, cscore, cut.kslot, cut.nkept, cap, kout, nkpts, row);
 }
 
 }  // namespace

@@ -70,14 +70,16 @@ __global__ __launch_bounds__(1024) void sel_keep_kernel(const unsigned long long
     if (threadIdx.x == 0) count[b] = run;
 }
 
-// thread i0 + tid ranks kept candidate i0 + tid, as r2_emit_kernel / d2_emit_kernel do
-__global__ __launch_bounds__(256) void sel_kept_rank_kernel(const float* __restrict__ cscore, const int* __restrict__ kslot, const int* __restrict__ nkept, int kcap,
-                                                            int* __restrict__ rank) {
-    const int b = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
-    const int n = min(nkept[b], kcap);
-    const int rk = kept_rank_ascending(cscore + (long)b * kcap, kslot + (long)b * kcap, n, i);
-    if (i < n) rank[(long)b * kcap + i] = rk;
-}
+// CUT's rows of ranked_rows_kernel: entry i of the output holds the rank of kept candidate i; entries past the count keep what the
+// caller put there
+struct SelRankRow {
+    int* rank;  // [B][kcap]
+    int kcap;
+    __device__ void clear(int, int, int) const {}
+    __device__ void emit(int b, int i0, int m, const int*, const int* rank_s, const float*) const {
+        if ((int)threadIdx.x < m) rank[(long)b * kcap + i0 + threadIdx.x] = rank_s[threadIdx.x];
+    }
+};
 
 extern "C" size_t imcui_hip_select_desc_bytes(void) { return sizeof(imcui_hip_select_desc); }
 
@@ -127,15 +129,10 @@ extern "C" int imcui_hip_select_probe(imcui_hip_t* h, const imcui_hip_select_des
     SelRows r;
     for (int b = 0; b < IMCUI_SELECT_MAXB; ++b) r.n[b] = b < B ? d->n_row[b] : 0, r.k[b] = b < B ? d->k_row[b] : 1;
     switch (d->op) {
-        case SEL_COMPACT: {
-            const int npix = d->n, nchunk = cdiv(npix, SEL_CHUNK);
-            const SelAboveThr pred{d->thr, 0.0f};
-            hipLaunchKernelGGL(cand_count_kernel<SelAboveThr>, dim3(nchunk, B), dim3(256), 0, stream, d->score, npix, pred, d->out_aux, nchunk);
-            hipLaunchKernelGGL(exclusive_scan_kernel<int>, dim3(B), dim3(1024), 0, stream, d->out_aux, d->out_i32, d->out_count, (const int*)nullptr, nchunk, (long)nchunk);
-            hipLaunchKernelGGL((cand_compact_kernel<SelAboveThr, EmitScoreIndex>), dim3(nchunk, B), dim3(256), 0, stream, d->score, npix, pred, d->out_i32, nchunk, d->cap,
-                               EmitScoreIndex{d->out_score, d->out_idx, cap});
+        case SEL_COMPACT:  // (the list's rows are `capacity` apart; positions past d->cap are counted only)
+            cand_list(stream, d->score, d->n, B, SelAboveThr{d->thr, 0.0f}, CandScan{d->out_aux, d->out_i32, d->out_count}, d->cap,
+                      EmitScoreIndex{d->out_score, d->out_idx, cap});
             break;
-        }
         case SEL_SCAN:
             hipLaunchKernelGGL(exclusive_scan_kernel<int>, dim3(B), dim3(1024), 0, stream, d->in_i32, d->out_i32, d->out_count, d->n_dev, d->n, (long)cap);
             break;
@@ -163,8 +160,9 @@ extern "C" int imcui_hip_select_probe(imcui_hip_t* h, const imcui_hip_select_des
             hipLaunchKernelGGL(zero_i32_kernel<>, dim3(1), dim3(64), 0, stream, d->status, 1);
             for (int l = 0; l < d->nlev; ++l)
                 hipLaunchKernelGGL(advance_base_kernel<>, dim3(cdiv(B, 256)), dim3(256), 0, stream, base, d->in_i32 + (long)l * B, B);
-            hipLaunchKernelGGL(cand_cut_kernel<>, dim3(B), dim3(1024), 0, stream, d->score, base, cap, d->limit, d->out_idx, d->out_count, d->status);
-            hipLaunchKernelGGL(sel_kept_rank_kernel, dim3(cdiv(cap, 256), B), dim3(256), 0, stream, d->score, d->out_idx, d->out_count, cap, d->out_i32);
+            const CutList cut{d->out_idx, d->out_count};
+            cand_cut(stream, d->score, base, cap, d->limit, cut, d->status, B);
+            ranked_rows(stream, d->score, cap, cut, cap, (int*)nullptr, SelRankRow{d->out_i32, cap}, B);
             break;
         }
     }

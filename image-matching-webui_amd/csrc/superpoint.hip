@@ -367,15 +367,10 @@ __global__ __launch_bounds__(1024) void sp_topk_kernel(const unsigned long long*
 // The selection stage as `forward` launches it, on the post-NMS map: status memset, count / scan / compact into 64-bit keys, top-k.
 // The one launcher of both imcui_hip_superpoint_forward and the test entry imcui_hip_superpoint_select_probe.
 static int sp_select_launch(imcui_hip_t* h, const float* nms, int B, int H, int W, float keypoint_threshold, int remove_borders, int max_keypoints, int kcap,
-                            int cand_cap, int* blkcnt, int* blkoff, int* ncand, unsigned long long* cand, float* keypoints, float* scores, int* num_keypoints,
-                            int* st, hipStream_t stream) {
-    const int nchunk = cdiv(H * W, SEL_CHUNK);
+                            int cand_cap, const CandScan& scan, unsigned long long* cand, float* keypoints, float* scores, int* num_keypoints, int* st,
+                            hipStream_t stream) {
     hipMemsetAsync(st, 0, sizeof(int), stream);
-    const SpIsCand is_cand{H, W, keypoint_threshold, remove_borders};
-    hipLaunchKernelGGL(cand_count_kernel<SpIsCand>, dim3(nchunk, B), dim3(256), 0, stream, nms, H * W, is_cand, blkcnt, nchunk);
-    hipLaunchKernelGGL(exclusive_scan_kernel<int>, dim3(B), dim3(1024), 0, stream, blkcnt, blkoff, ncand, (const int*)nullptr, nchunk, (long)nchunk);
-    hipLaunchKernelGGL((cand_compact_kernel<SpIsCand, SpEmitKey>), dim3(nchunk, B), dim3(256), 0, stream, nms, H * W, is_cand, blkoff, nchunk, cand_cap,
-                       SpEmitKey{cand, cand_cap});
+    cand_list(stream, nms, H * W, B, SpIsCand{H, W, keypoint_threshold, remove_borders}, scan, cand_cap, SpEmitKey{cand, cand_cap});
     {
         int np2 = 1;
         const int kmax = max_keypoints < 0 ? 1 : (max_keypoints < TOPK_MAX ? max_keypoints : TOPK_MAX);
@@ -383,7 +378,7 @@ static int sp_select_launch(imcui_hip_t* h, const float* nms, int B, int H, int 
         const size_t smem = (size_t)np2 * sizeof(unsigned long long);
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(sp_topk_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                   (int)(TOPK_MAX * sizeof(unsigned long long)));
-        hipLaunchKernelGGL(sp_topk_kernel, dim3(B), dim3(1024), smem, stream, cand, cand_cap, ncand, max_keypoints, kcap, W,
+        hipLaunchKernelGGL(sp_topk_kernel, dim3(B), dim3(1024), smem, stream, cand, cand_cap, scan.total, max_keypoints, kcap, W,
                            keypoints, scores, num_keypoints, st);
     }
     IMCUI_CHECK_LAUNCH(h);
@@ -466,7 +461,8 @@ __global__ __launch_bounds__(256) void sp_sample_kernel(const float* __restrict_
 // ------------------------------------------------------------------ forward
 struct SpWs {
     float *a1a, *p1, *a2a, *p2, *a3a, *p3, *a4a, *feat, *head, *logits, *dense, *nms, *ddesc;
-    int *blkcnt, *blkoff, *ncand, *status;
+    CandScan scan;
+    int* status;
     unsigned long long* cand;
     size_t total;
     bool ok;
@@ -490,10 +486,7 @@ static SpWs sp_carve(void* ws, size_t ws_bytes, int B, int H, int W, int cand_ca
     s.dense = a.get<float>(hw);
     s.nms = a.get<float>(hw);
     s.ddesc = a.get<float>(c * 256);
-    const int nchunk = cdiv(H * W, SEL_CHUNK);
-    s.blkcnt = a.get<int>((size_t)B * nchunk);
-    s.blkoff = a.get<int>((size_t)B * nchunk);
-    s.ncand = a.get<int>(B);
+    s.scan.carve(a, B, (size_t)H * W);
     s.status = a.get<int>(1);
     s.cand = a.get<unsigned long long>((size_t)B * cand_cap);
     s.total = a.off;
@@ -598,7 +591,7 @@ extern "C" int imcui_hip_superpoint_forward(imcui_hip_t* h, const float* packed,
     IMCUI_CHECK_LAUNCH(h);
     // a4: NMS ; a5: select
     IMCUI_RUN(nms_launch(h, dense, s.nms, B, H, W, nms_radius, stream));
-    IMCUI_RUN(sp_select_launch(h, s.nms, B, H, W, keypoint_threshold, remove_borders, max_keypoints, kcap, cand_cap, s.blkcnt, s.blkoff, s.ncand, s.cand, keypoints,
+    IMCUI_RUN(sp_select_launch(h, s.nms, B, H, W, keypoint_threshold, remove_borders, max_keypoints, kcap, cand_cap, s.scan, s.cand, keypoints,
                                scores, num_keypoints, status ? status : s.status, stream));
     // a6: descriptor head + sampling
     IMCUI_RUN(conv(LDA, s.feat, s.head, Hc, Wc, 0));
@@ -631,7 +624,7 @@ extern "C" int imcui_hip_simple_nms(imcui_hip_t* h, const float* scores, float* 
 
 // test entry: the selection stage alone, through the launcher `forward` calls, on a post-NMS map given by the caller
 struct SpSelWs {
-    int *blkcnt, *blkoff, *ncand;
+    CandScan scan;
     unsigned long long* cand;
     size_t total;
     bool ok;
@@ -639,10 +632,7 @@ struct SpSelWs {
 static SpSelWs sp_select_carve(void* ws, size_t ws_bytes, int B, int H, int W, int cand_cap) {
     WsAlloc a(ws, ws_bytes);
     SpSelWs s;
-    const int nchunk = cdiv(H * W, SEL_CHUNK);
-    s.blkcnt = a.get<int>((size_t)B * nchunk);
-    s.blkoff = a.get<int>((size_t)B * nchunk);
-    s.ncand = a.get<int>(B);
+    s.scan.carve(a, B, (size_t)H * W);
     s.cand = a.get<unsigned long long>((size_t)B * cand_cap);
     s.total = a.off;
     s.ok = a.ok;
@@ -663,6 +653,6 @@ extern "C" int imcui_hip_superpoint_select_probe(imcui_hip_t* h, const float* nm
     if (!nms || !keypoints || !scores || !num_keypoints || !status) return imcui_set_err(h, IMCUI_ERR_ARG, "superpoint select probe: null argument");
     SpSelWs s = sp_select_carve(ws, ws_bytes, B, H, W, cand_cap);
     if (!ws || !s.ok) return imcui_set_err(h, IMCUI_ERR_WS, "superpoint select probe: workspace too small (%zu < %zu)", ws_bytes, s.total);
-    return sp_select_launch(h, nms, B, H, W, keypoint_threshold, remove_borders, max_keypoints, kcap, cand_cap, s.blkcnt, s.blkoff, s.ncand, s.cand, keypoints,
+    return sp_select_launch(h, nms, B, H, W, keypoint_threshold, remove_borders, max_keypoints, kcap, cand_cap, s.scan, s.cand, keypoints,
                             scores, num_keypoints, status, (hipStream_t)stream_);
 }

@@ -586,9 +586,11 @@ __global__ __launch_bounds__(256) void xf_probe_kernel(const float* __restrict__
 
 // ------------------------------------------------------------------ workspace
 struct XfWs {
-    float *gray, *norm, *s1, *s2, *s3, *q0, *q1, *q2, *e0, *e1, *e2, *e3, *x4a, *x4b, *x5a, *x5b, *x5c, *logits, *k1h, *rel, *m1, *cscore, *cfinal;
+    float *gray, *norm, *s1, *s2, *s3, *q0, *q1, *q2, *e0, *e1, *e2, *e3, *x4a, *x4b, *x5a, *x5b, *x5c, *logits, *k1h, *rel, *m1, *cfinal;
     double* part;
-    int *blkcnt, *blkoff, *ncand, *npos, *cidx, *crank, *status;
+    CandScan scan;
+    ScoreIndexList cand;
+    int *npos, *crank, *status;
     size_t total;
     bool ok;
 };
@@ -619,13 +621,9 @@ static XfWs xf_carve(void* ws, size_t bytes, int B, int Hr, int Wr) {
     s.k1h = a.get<float>(P);
     s.rel = a.get<float>(P / 64);
     s.m1 = a.get<float>(P / 64 * 64);
-    const int nchunk = cdiv(Hr * Wr, SEL_CHUNK);
-    s.blkcnt = a.get<int>((size_t)B * nchunk);
-    s.blkoff = a.get<int>((size_t)B * nchunk);
-    s.ncand = a.get<int>(B);
+    s.scan.carve(a, B, (size_t)Hr * Wr);
     s.npos = a.get<int>(B);
-    s.cscore = a.get<float>(P);  // a constant map is one plateau: every pixel can be a candidate
-    s.cidx = a.get<int>(P);
+    s.cand.carve(a, B, Hr * Wr);  // a constant map is one plateau: every pixel can be a candidate
     s.cfinal = a.get<float>(P);
     s.crank = a.get<int>(P);
     s.status = a.get<int>(1);
@@ -740,19 +738,15 @@ extern "C" int imcui_hip_xfeat_forward(imcui_hip_t* h, const float* packed, cons
     int* st = status ? status : s.status;
     hipMemsetAsync(st, 0, sizeof(int), stream);
     hipMemsetAsync(s.npos, 0, sizeof(int) * B, stream);
-    const int npix = Hr * Wr, nchunk = cdiv(npix, SEL_CHUNK), ccap = npix;
-    const XfKeep keep{Hr, Wr, threshold};
-    hipLaunchKernelGGL(cand_count_kernel<XfKeep>, dim3(nchunk, B), dim3(256), 0, stream, k1h, npix, keep, s.blkcnt, nchunk);
-    hipLaunchKernelGGL(exclusive_scan_kernel<int>, dim3(B), dim3(1024), 0, stream, s.blkcnt, s.blkoff, s.ncand, (const int*)nullptr, nchunk, (long)nchunk);
-    hipLaunchKernelGGL((cand_compact_kernel<XfKeep, EmitScoreIndex>), dim3(nchunk, B), dim3(256), 0, stream, k1h, npix, keep, s.blkoff, nchunk, ccap,
-                       EmitScoreIndex{s.cscore, s.cidx, ccap});
+    const int ccap = s.cand.cap, *cidx = s.cand.cidx, *ncand = s.scan.total;
+    cand_list(stream, k1h, Hr * Wr, B, XfKeep{Hr, Wr, threshold}, s.scan, ccap, s.cand.emit());
     const dim3 cgrid(cdiv(ccap, 256), B);
-    hipLaunchKernelGGL(xf_score_kernel, cgrid, dim3(256), 0, stream, k1h, rel, s.cidx, s.ncand, ccap, Hr, Wr, s.cfinal, s.npos);
-    hipLaunchKernelGGL(xf_rank_kernel, cgrid, dim3(256), 0, stream, s.cfinal, s.cidx, s.ncand, s.npos, ccap, top_k, kcap, Wr,
+    hipLaunchKernelGGL(xf_score_kernel, cgrid, dim3(256), 0, stream, k1h, rel, cidx, ncand, ccap, Hr, Wr, s.cfinal, s.npos);
+    hipLaunchKernelGGL(xf_rank_kernel, cgrid, dim3(256), 0, stream, s.cfinal, cidx, ncand, s.npos, ccap, top_k, kcap, Wr,
                        (float)((double)W / (double)Wr), (float)((double)H / (double)Hr), keypoints, scores, s.crank);
-    hipLaunchKernelGGL(xf_finish_kernel, dim3(cdiv(kcap, 4), B), dim3(256), 0, stream, s.ncand, s.npos, ccap, top_k, kcap, keypoints, scores, descriptors,
+    hipLaunchKernelGGL(xf_finish_kernel, dim3(cdiv(kcap, 4), B), dim3(256), 0, stream, ncand, s.npos, ccap, top_k, kcap, keypoints, scores, descriptors,
                        num_keypoints, st);
-    hipLaunchKernelGGL(xf_desc_kernel, dim3(min(cdiv(ccap, 4), 1024), B), dim3(256), 0, stream, m1, s.cidx, s.crank, s.ncand, ccap, kcap, Hr, Wr, descriptors);
+    hipLaunchKernelGGL(xf_desc_kernel, dim3(min(cdiv(ccap, 4), 1024), B), dim3(256), 0, stream, m1, cidx, s.crank, ncand, ccap, kcap, Hr, Wr, descriptors);
     IMCUI_CHECK_LAUNCH(h);
     return IMCUI_OK;
 }

@@ -42,10 +42,14 @@ class Handle:
         """`fn(h, *args)` for an ABI function of this handle; a non-zero status raises, naming the C symbol."""
         self.check(fn(self.h, *args), fn.__name__)
 
-    def launch(self, fn, *args):
-        """The one path of every stream-ordered ABI call: `fn(h, *args, stream)` on this handle's device and its current stream."""
+    def launch(self, fn, *args, check: bool = True) -> int:
+        """The one path of every stream-ordered ABI call: `fn(h, *args, stream)` on this handle's device and its current stream.  A
+        non-zero status raises, naming the C symbol; with check=False it is returned instead (the probes' refusal tests)."""
         with torch.cuda.device(self.device_index):
-            self.call(fn, *args, _stream_ptr())
+            rc = fn(self.h, *args, _stream_ptr())
+        if check:
+            self.check(rc, fn.__name__)
+        return rc
 
 
 def get_handle(device: torch.device) -> Handle:
@@ -64,6 +68,29 @@ def _stream_ptr() -> C.c_void_p:
 
 def _ptr(t: torch.Tensor | None) -> C.c_void_p:
     return C.c_void_p(0 if t is None else t.data_ptr())
+
+
+def _fill_desc(d, fields: dict, who: str):
+    """The descriptor `d` with `fields` set: a device tensor becomes its pointer, None a null pointer, a host tensor is refused."""
+    for k, v in fields.items():
+        if isinstance(v, torch.Tensor):
+            if v.device.type != "cuda":
+                raise ImcuiHipError(f"{who}: field {k} must be a device tensor")
+            v = v.data_ptr()
+        elif v is None:
+            v = 0
+        setattr(d, k, v)
+    return d
+
+
+def _route_table(device: torch.device, fn_name: str) -> dict:
+    """{route: value} of a per-route table of the device's handle (launch counts, feature masks), zero entries left out."""
+    hd = get_handle(device)
+    fn = getattr(hd.lib, fn_name)
+    n = fn(hd.h, None, 0)
+    buf = (C.c_int * n)()
+    fn(hd.h, buf, n)
+    return {r: c for r, c in enumerate(buf) if c}
 
 
 def _as_f32_host(t) -> np.ndarray:
@@ -249,14 +276,8 @@ class SuperPointHIP:
         args = (_ptr(nms), B, H, W, float(keypoint_threshold), int(remove_borders), int(max_keypoints), int(kcap), cand_cap,
                 _ptr(out["keypoints"]), _ptr(out["scores"]), _ptr(out["num_keypoints"]), _ptr(out["status"]))  # fmt: skip
         with self._ws.use(max(256, lib.imcui_hip_superpoint_select_workspace_bytes(B, H, W, cand_cap)), nms.device) as ws:
-            if check:
-                hd.launch(lib.imcui_hip_superpoint_select_probe, *args, _ptr(ws), ws.numel())
-            else:
-                with torch.cuda.device(hd.device_index):
-                    rc = lib.imcui_hip_superpoint_select_probe(hd.h, *args, _ptr(ws), ws.numel(), _stream_ptr())
-                if rc != 0:
-                    return rc
-        return out
+            rc = hd.launch(lib.imcui_hip_superpoint_select_probe, *args, _ptr(ws), ws.numel(), check=check)
+        return out if rc == 0 else rc
 
 
 # ------------------------------------------------------------------ DISK
@@ -347,14 +368,8 @@ class DiskHIP:
         args = (_ptr(heat), B, H, W, int(window), float(threshold), maxk, int(kcap), ccap,
                 _ptr(out["keypoints"]), _ptr(out["scores"]), _ptr(out["num_keypoints"]), _ptr(out["status"]))  # fmt: skip
         with self._ws.use(max(256, lib.imcui_hip_disk_select_workspace_bytes(B, H, W, ccap)), heat.device) as ws:
-            if check:
-                hd.launch(lib.imcui_hip_disk_select_probe, *args, _ptr(ws), ws.numel())
-            else:
-                with torch.cuda.device(hd.device_index):
-                    rc = lib.imcui_hip_disk_select_probe(hd.h, *args, _ptr(ws), ws.numel(), _stream_ptr())
-                if rc != 0:
-                    return rc
-        return out
+            rc = hd.launch(lib.imcui_hip_disk_select_probe, *args, _ptr(ws), ws.numel(), check=check)
+        return out if rc == 0 else rc
 
 
 # ------------------------------------------------------------------ XFeat
@@ -3377,43 +3392,22 @@ def gemm_probe(device: torch.device, check: bool = True, **fields) -> int:
     may be a GEMM_EPI name).  Returns the route of the launch (GEMM_ROUTE_KINDS); with check=False a refused call returns its
     negative status instead of raising."""
     hd = get_handle(device)
-    d = GemmDesc()
-    for k, v in {**GemmDesc.DEFAULTS, **fields}.items():
-        if k == "epi" and isinstance(v, str):
-            v = GEMM_EPI[v]
-        if isinstance(v, torch.Tensor):
-            if v.device.type != "cuda":
-                raise ImcuiHipError(f"gemm_probe: field {k} must be a device tensor")
-            v = v.data_ptr()
-        elif v is None:
-            v = 0
-        setattr(d, k, v)
-    if check:
-        hd.launch(hd.lib.imcui_hip_gemm_probe_f32, C.byref(d))
-    else:
-        with torch.cuda.device(hd.device_index):
-            rc = hd.lib.imcui_hip_gemm_probe_f32(hd.h, C.byref(d), _stream_ptr())
-        if rc != 0:
-            return rc
-    return int(hd.lib.imcui_hip_gemm_last_route(hd.h))
+    fields = {**GemmDesc.DEFAULTS, **fields}
+    if isinstance(fields.get("epi"), str):
+        fields["epi"] = GEMM_EPI[fields["epi"]]
+    d = _fill_desc(GemmDesc(), fields, "gemm_probe")
+    rc = hd.launch(hd.lib.imcui_hip_gemm_probe_f32, C.byref(d), check=check)
+    return rc if rc != 0 else int(hd.lib.imcui_hip_gemm_last_route(hd.h))
 
 
 def gemm_route_counts(device: torch.device) -> dict:
     """{route: launches} of every GEMM launch on the device's handle since gemm_route_reset."""
-    hd = get_handle(device)
-    n = hd.lib.imcui_hip_gemm_route_counts(hd.h, None, 0)
-    buf = (C.c_int * n)()
-    hd.lib.imcui_hip_gemm_route_counts(hd.h, buf, n)
-    return {r: c for r, c in enumerate(buf) if c}
+    return _route_table(device, "imcui_hip_gemm_route_counts")
 
 
 def gemm_route_features(device: torch.device) -> dict:
     """{route: OR of the GEMM_FEATURES bits its launches ran with} since gemm_route_reset (routes with no feature are absent)."""
-    hd = get_handle(device)
-    n = hd.lib.imcui_hip_gemm_route_features(hd.h, None, 0)
-    buf = (C.c_int * n)()
-    hd.lib.imcui_hip_gemm_route_features(hd.h, buf, n)
-    return {r: c for r, c in enumerate(buf) if c}
+    return _route_table(device, "imcui_hip_gemm_route_features")
 
 
 def gemm_feature_names(mask: int) -> list:
@@ -3454,27 +3448,13 @@ def attention_probe(device: torch.device, check: bool = True, **fields) -> int:
     V6_bytes / part_bytes default to the sizes of the tensors given as V6 / part).  Returns the route of the launch (ATTN_ROUTE_KINDS);
     with check=False a refused call returns its negative status instead of raising."""
     hd = get_handle(device)
-    d = AttnDesc()
     fields = {**AttnDesc.DEFAULTS, **fields}
     for k in ("V6", "part"):
         if isinstance(fields.get(k), torch.Tensor):
             fields.setdefault(k + "_bytes", fields[k].numel() * fields[k].element_size())
-    for k, v in fields.items():
-        if isinstance(v, torch.Tensor):
-            if v.device.type != "cuda":
-                raise ImcuiHipError(f"attention_probe: field {k} must be a device tensor")
-            v = v.data_ptr()
-        elif v is None:
-            v = 0
-        setattr(d, k, v)
-    if check:
-        hd.launch(hd.lib.imcui_hip_attention_probe_f32, C.byref(d))
-    else:
-        with torch.cuda.device(hd.device_index):
-            rc = hd.lib.imcui_hip_attention_probe_f32(hd.h, C.byref(d), _stream_ptr())
-        if rc != 0:
-            return rc
-    return int(hd.lib.imcui_hip_attn_last_route(hd.h))
+    d = _fill_desc(AttnDesc(), fields, "attention_probe")
+    rc = hd.launch(hd.lib.imcui_hip_attention_probe_f32, C.byref(d), check=check)
+    return rc if rc != 0 else int(hd.lib.imcui_hip_attn_last_route(hd.h))
 
 
 def attention_part_floats(device: torch.device, S: int, heads: int, rows: int) -> int:
@@ -3483,11 +3463,7 @@ def attention_part_floats(device: torch.device, S: int, heads: int, rows: int) -
 
 def attn_route_counts(device: torch.device) -> dict:
     """{route: launches} of every attention launch on the device's handle since attn_route_reset."""
-    hd = get_handle(device)
-    n = hd.lib.imcui_hip_attn_route_counts(hd.h, None, 0)
-    buf = (C.c_int * n)()
-    hd.lib.imcui_hip_attn_route_counts(hd.h, buf, n)
-    return {r: c for r, c in enumerate(buf) if c}
+    return _route_table(device, "imcui_hip_attn_route_counts")
 
 
 def attn_route_reset(device: torch.device) -> None:
@@ -3544,32 +3520,14 @@ def ffn_probe(device: torch.device, check: bool = True, **fields) -> int:
     pointer).  Returns the route of the launch (ffn_route); with check=False a refused call returns its negative status instead of
     raising."""
     hd = get_handle(device)
-    d = FfnDesc()
-    for k, v in fields.items():
-        if isinstance(v, torch.Tensor):
-            if v.device.type != "cuda":
-                raise ImcuiHipError(f"ffn_probe: field {k} must be a device tensor")
-            v = v.data_ptr()
-        elif v is None:
-            v = 0
-        setattr(d, k, v)
-    if check:
-        hd.launch(hd.lib.imcui_hip_ffn_probe_f32, C.byref(d))
-    else:
-        with torch.cuda.device(hd.device_index):
-            rc = hd.lib.imcui_hip_ffn_probe_f32(hd.h, C.byref(d), _stream_ptr())
-        if rc != 0:
-            return rc
-    return int(hd.lib.imcui_hip_ffn_last_route(hd.h))
+    d = _fill_desc(FfnDesc(), fields, "ffn_probe")
+    rc = hd.launch(hd.lib.imcui_hip_ffn_probe_f32, C.byref(d), check=check)
+    return rc if rc != 0 else int(hd.lib.imcui_hip_ffn_last_route(hd.h))
 
 
 def ffn_route_counts(device: torch.device) -> dict:
     """{route: launches} of every fused-FFN launch on the device's handle since ffn_route_reset."""
-    hd = get_handle(device)
-    n = hd.lib.imcui_hip_ffn_route_counts(hd.h, None, 0)
-    buf = (C.c_int * n)()
-    hd.lib.imcui_hip_ffn_route_counts(hd.h, buf, n)
-    return {r: c for r, c in enumerate(buf) if c}
+    return _route_table(device, "imcui_hip_ffn_route_counts")
 
 
 def ffn_route_reset(device: torch.device) -> None:
@@ -3657,44 +3615,21 @@ def conv_probe(device: torch.device, check: bool = True, **fields) -> int:
     pointers, `entry` may be a CONV_ENTRIES name).  Returns the route of the launch (CONV_ROUTE_KINDS); with check=False a refused call
     returns its negative status instead of raising."""
     hd = get_handle(device)
-    d = ConvDesc()
-    for k, v in fields.items():
-        if k == "entry" and isinstance(v, str):
-            v = CONV_ENTRIES[v]
-        if isinstance(v, torch.Tensor):
-            if v.device.type != "cuda":
-                raise ImcuiHipError(f"conv_probe: field {k} must be a device tensor")
-            v = v.data_ptr()
-        elif v is None:
-            v = 0
-        setattr(d, k, v)
-    if check:
-        hd.launch(hd.lib.imcui_hip_conv_probe_f32, C.byref(d))
-    else:
-        with torch.cuda.device(hd.device_index):
-            rc = hd.lib.imcui_hip_conv_probe_f32(hd.h, C.byref(d), _stream_ptr())
-        if rc != 0:
-            return rc
-    return int(hd.lib.imcui_hip_conv_last_route(hd.h))
-
-
-def _conv_route_table(device: torch.device, fn_name: str) -> dict:
-    hd = get_handle(device)
-    fn = getattr(hd.lib, fn_name)
-    n = fn(hd.h, None, 0)
-    buf = (C.c_int * n)()
-    fn(hd.h, buf, n)
-    return {r: c for r, c in enumerate(buf) if c}
+    if isinstance(fields.get("entry"), str):
+        fields["entry"] = CONV_ENTRIES[fields["entry"]]
+    d = _fill_desc(ConvDesc(), fields, "conv_probe")
+    rc = hd.launch(hd.lib.imcui_hip_conv_probe_f32, C.byref(d), check=check)
+    return rc if rc != 0 else int(hd.lib.imcui_hip_conv_last_route(hd.h))
 
 
 def conv_route_counts(device: torch.device) -> dict:
     """{route: launches} of every launch of csrc/conv.hip on the device's handle since conv_route_reset."""
-    return _conv_route_table(device, "imcui_hip_conv_route_counts")
+    return _route_table(device, "imcui_hip_conv_route_counts")
 
 
 def conv_route_features(device: torch.device) -> dict:
     """{route: OR of the CONV_FEATURES bits its launches ran with} since conv_route_reset (routes with no feature are absent)."""
-    return _conv_route_table(device, "imcui_hip_conv_route_features")
+    return _route_table(device, "imcui_hip_conv_route_features")
 
 
 def conv_route_reset(device: torch.device) -> None:
@@ -3787,11 +3722,7 @@ def select_probe(device: torch.device, check: bool = True, **fields) -> int:
         if isinstance(v, torch.Tensor) and v.device.type != "cuda":
             raise ImcuiHipError(f"select_probe: field {k} must be a device tensor")
     d = select_desc(**fields)
-    if check:
-        hd.launch(hd.lib.imcui_hip_select_probe, C.byref(d))
-        return 0
-    with torch.cuda.device(hd.device_index):
-        return int(hd.lib.imcui_hip_select_probe(hd.h, C.byref(d), _stream_ptr()))
+    return int(hd.launch(hd.lib.imcui_hip_select_probe, C.byref(d), check=check))
 
 
 def simple_nms(scores: torch.Tensor, radius: int) -> torch.Tensor:

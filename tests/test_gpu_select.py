@@ -413,13 +413,20 @@ CUT_CASES = [
     dict(id="more_than_kcap", kcap=800, levels=[[500, 200], [400, 300]], limit=300, wrong=("ties_low",)),
     dict(id="more_than_kcap_no_limit", kcap=300, levels=[[200, 100], [101, 50]], limit=0),
     dict(id="zero_total", kcap=64, levels=[[0, 2], [0, 3]], limit=10),
+    # the ranked rows (ranked_rows_kernel, workgroups of 256 kept candidates)
+    dict(id="kept_256", kcap=1024, levels=[[200, 100], [56, 50]], limit=0, wrong=("ties_reversed",)),
+    dict(id="kept_257_one_row_in_the_second_workgroup", kcap=1024, levels=[[200, 100], [57, 50]], limit=0, wrong=("ties_reversed",)),
+    dict(id="one_image_keeps_nothing", kcap=1024, levels=[[300, 0], [100, 0]], limit=0, wrong=("ties_reversed",)),
+    dict(id="all_equal_across_256", kcap=1024, levels=[[400, 300], [200, 250]], limit=300, equal=True, wrong=("ties_low", "ties_reversed")),
 ]
 
 
 def cut_inputs(c):
-    """-> (scores f32 [2][kcap] from a few values (negative, -0.0, +0.0, positive), level counts int32 [nlev][2])"""
+    """-> (scores f32 [2][kcap] from a few values (negative, -0.0, +0.0, positive; `equal`: image 0 holds one value), level counts int32 [nlev][2])"""
     rng = _rng("cut" + c["id"])
     s = rng.choice(_f32([-1.0, -0.0, 0.0, 0.25, 0.5, 1.0]), (2, c["kcap"])).astype(np.float32)
+    if c.get("equal"):
+        s[0] = 0.5
     return s, np.array(c["levels"], np.int32)
 
 
