@@ -1414,6 +1414,258 @@ class DarkFeatHIP:
         return out
 
 
+# ------------------------------------------------------------------ SFD2
+SFD2_DIM = 128
+SFD2_MIN_SIDE = 16
+SFD2_TRUNK = ("conv1a", "conv1b", "conv2a", "conv2b", "conv3a", "conv3b")
+SFD2_SELECT_DEFAULTS = {"min_keypoints": 128, "remove_borders": 4}  # backend-only conf keys (upstream's text is not at hand)
+SFD2_KINDS = ("stem", "conv3x3", "conv1x1", "grouped3x3", "heads")
+
+
+def sfd2_config(sd: dict) -> dict:
+    """What an SFD2 (ResNet4x) state dict decides, read from its shapes: trunk widths, bottleneck count, channels per group, hidden width
+    of the heads, kernel size of convPb / convDb, BatchNorm and bias.  Nothing is guessed: a missing key or an unexpected shape raises."""
+
+    def shape(name):
+        if name not in sd:
+            raise ImcuiHipError(f"SFD2 state dict: '{name}' is missing")
+        s = tuple(sd[name].shape)
+        if len(s) != 4 or s[2] != s[3]:
+            raise ImcuiHipError(f"SFD2 state dict: '{name}' has shape {s}, expected a square convolution kernel [cout, cin, k, k]")
+        return s
+
+    c1, c2, c3 = (shape(f"conv{i}b.0.weight")[0] for i in (1, 2, 3))
+    nb = 0
+    while f"conv4.{nb}.conv1.weight" in sd:
+        nb += 1
+    cg = shape("conv4.0.conv2.weight")[1] if nb else 8  # (no bottleneck: no grouped layer is launched, the value is read by nobody)
+    ch = shape("convPa.0.weight")[0]
+    if shape("convDa.0.weight")[0] != ch:
+        raise ImcuiHipError(f"SFD2: convPa is {ch} wide and convDa {shape('convDa.0.weight')[0]}: the two hidden layers run as one launch and need one width")
+    pb, db = shape("convPb.weight"), shape("convDb.weight")
+    if pb[0] != 16 or db[0] != SFD2_DIM:
+        raise ImcuiHipError(f"SFD2: convPb has {pb[0]} outputs (16: a 4 x 4 depth-to-space) and convDb {db[0]} ({SFD2_DIM})")
+    for name, s in (("convPb", pb), ("convDb", db)):
+        if s[2] not in (1, 3):
+            raise ImcuiHipError(f"SFD2: {name}.weight has shape {s}: the kernel must be 1x1 or 3x3")
+    cfg = {"widths": (c1, c2, c3), "blocks": nb, "group_channels": cg, "hidden": ch, "k": (pb[2], db[2]), "bn": int("conv1a.1.weight" in sd),
+           "bias": int("conv1a.0.bias" in sd), "block_bias": int("conv4.0.conv1.bias" in sd)}  # fmt: skip
+    if load_library().imcui_hip_sfd2_packed_floats(sfd2_cfg_array(cfg)) == 0:
+        raise ImcuiHipError(f"SFD2: the library refuses the configuration {cfg} (c1 = 64, widths multiples of 32 up to 512, up to 8 bottlenecks, "
+                            "4 / 8 / 16 channels per group)")  # fmt: skip
+    return cfg
+
+
+def sfd2_cfg_array(cfg: dict):
+    """The 12 ints of include/imcui_hip.h's `cfg`."""
+    return (C.c_int * 12)(*cfg["widths"], cfg["blocks"], cfg["group_channels"], cfg["hidden"], *cfg["k"], cfg["bn"], cfg["bias"], cfg["block_bias"], 0)
+
+
+def sfd2_layers(cfg: dict) -> list[dict]:
+    """The launch list as the library's ONE table states it (csrc/sfd2.hip, SFD2_LAYERS): name, kind, cin, cout, stride, block (0 none,
+    1 / 2 / 3 = first / middle / last launch of a bottleneck)."""
+    lib, ca = load_library(), sfd2_cfg_array(cfg)
+    out = []
+    for i in range(lib.imcui_hip_sfd2_num_layers(ca)):
+        v = (C.c_int * 5)()
+        name = lib.imcui_hip_sfd2_layer(ca, i, v).decode()
+        out.append({"name": name, "kind": SFD2_KINDS[v[0]], "cin": v[1], "cout": v[2], "stride": v[3], "block": v[4]})
+    return out
+
+
+def sfd2_tensor_names(cfg: dict) -> list[str]:
+    lib, ca = load_library(), sfd2_cfg_array(cfg)
+    return [lib.imcui_hip_sfd2_tensor_name(ca, i).decode() for i in range(lib.imcui_hip_sfd2_num_tensors(ca))]
+
+
+def sfd2_tensor_shapes(cfg: dict) -> dict:
+    shapes = {}
+
+    def conv(stem, bn, cout, cin, k, bias):
+        shapes[f"{stem}.weight"] = (cout, cin, k, k)
+        if bias:
+            shapes[f"{stem}.bias"] = (cout,)
+        if cfg["bn"]:
+            for key in _BN_KEYS:
+                shapes[f"{bn}.{key}"] = (cout,)
+
+    c3, ch, cg = cfg["widths"][2], cfg["hidden"], cfg["group_channels"]
+    for L in sfd2_layers(cfg):
+        if L["kind"] == "heads":
+            conv("convPa.0", "convPa.1", ch, c3, 3, cfg["bias"])
+            conv("convDa.0", "convDa.1", ch, c3, 3, cfg["bias"])
+        elif L["block"]:
+            stem = L["name"]  # conv4.{i}.conv{j}
+            conv(stem, stem.replace(".conv", ".bn"), L["cout"], cg if L["kind"] == "grouped3x3" else L["cin"], 1 if L["kind"] == "conv1x1" else 3, cfg["block_bias"])
+        else:
+            stem = L["name"]  # conv1a.0
+            conv(stem, stem[:-1] + "1", L["cout"], L["cin"], 3, cfg["bias"])
+    shapes["convPb.weight"], shapes["convPb.bias"] = (16, ch, cfg["k"][0], cfg["k"][0]), (16,)
+    shapes["convDb.weight"], shapes["convDb.bias"] = (SFD2_DIM, ch, cfg["k"][1], cfg["k"][1]), (SFD2_DIM,)
+    return shapes
+
+
+def pack_sfd2(state_dict: dict):
+    """SFD2 state dict under upstream's keys (the plugin's SFD2_KEYS table admits them) -> (packed float32 buffer (host), cfg).  BatchNorm
+    (eval) is folded by the packer.  Strict: `num_batches_tracked` counters are ignored, a convPb / convDb bias the checkpoint does not
+    carry is zero, every other key is consumed exactly once and every shape checked; an unknown or missing key raises."""
+    lib = load_library()
+    sd = {k: t for k, t in state_dict.items() if not k.endswith("num_batches_tracked")}
+    cfg = sfd2_config(sd)
+    sd.setdefault("convPb.bias", torch.zeros(16))
+    sd.setdefault("convDb.bias", torch.zeros(SFD2_DIM))
+    ca = sfd2_cfg_array(cfg)
+    return _pack_named("SFD2", "the ResNet4x", sfd2_tensor_names(cfg), sfd2_tensor_shapes(cfg), sd, lib.imcui_hip_sfd2_packed_floats(ca), lib.imcui_hip_sfd2_pack_weights, ca), cfg
+
+
+def sfd2_pack_group(w: torch.Tensor) -> torch.Tensor:
+    """Grouped 3x3 weights [C, CG, 3, 3] (OIHW per group) -> the packed order [group][tap][ci][co] of csrc/sfd2.hip."""
+    Cc, cg = w.shape[:2]
+    return w.reshape(Cc // cg, cg, cg, 9).permute(0, 3, 2, 1).contiguous()
+
+
+def sfd2_map_sizes(H: int, W: int) -> tuple:
+    """(h2, w2, Hc, Wc): a stride-2 layer leaves (n - 1) // 2 + 1 rows / columns; the score map is (4 Hc, 4 Wc)."""
+    h2, w2 = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    return h2, w2, (h2 - 1) // 2 + 1, (w2 - 1) // 2 + 1
+
+
+def sfd2_select_conf(conf: dict) -> dict:
+    """conf_th, max_keypoints and the backend-only keys min_keypoints / remove_borders of a conf; refusals by name."""
+    if conf.get("multiscale"):
+        raise ValueError("SFD2: multiscale is not served by the HIP backend")
+    d = {"conf_th": float(conf.get("conf_th", 0.001)), "max_keypoints": int(conf.get("max_keypoints") or 0),
+         **{k: int(conf.get(k, v)) for k, v in SFD2_SELECT_DEFAULTS.items()}}  # fmt: skip
+    if d["max_keypoints"] < 0:
+        raise ValueError(f"SFD2: max_keypoints={d['max_keypoints']} is negative; 0 keeps every key-point")
+    if d["min_keypoints"] < 0 or d["remove_borders"] < 0 or not d["conf_th"] >= 0:
+        raise ValueError(f"SFD2: min_keypoints={d['min_keypoints']} (>= 0), remove_borders={d['remove_borders']} (>= 0), conf_th={d['conf_th']} (>= 0)")
+    return d
+
+
+def sfd2_check_args(image_shape) -> None:
+    """Refusals raised before anything is launched."""
+    if len(image_shape) != 4 or image_shape[1] != 3:
+        raise ValueError(f"SFD2 expects an RGB image [B,3,H,W], got shape {tuple(image_shape)}")
+    if image_shape[2] < SFD2_MIN_SIDE or image_shape[3] < SFD2_MIN_SIDE:
+        raise ValueError(f"SFD2 needs images of at least {SFD2_MIN_SIDE} x {SFD2_MIN_SIDE}, got {tuple(image_shape[2:])}")
+
+
+class Sfd2HIP:
+    def __init__(self, cfg: dict):
+        self.cfg = cfg
+        self._ca = sfd2_cfg_array(cfg)
+        self._ws = _Workspace()
+
+    def forward(self, packed: torch.Tensor, image: torch.Tensor, conf: dict, want_maps: bool = False, layer: int = -1):
+        """image [B,3,H,W] float32 RGB in [0,1] on the GPU -> fixed-stride outputs, no host synchronisation: keypoints [B,K,2] (x, y in
+        pixels, integer-valued), scores [B,K], descriptors [B,K,128], num_keypoints [B] int32, status [1] int32 (always 0), rows in
+        descending score order (equal scores by ascending pixel index), rows past the count zero.  K = min(max_keypoints or all, score-map
+        pixels).  want_maps adds score [B,4Hc,4Wc] and desc_map [B,Hc,Wc,128] (normalised); `layer` adds layer_out, the NHWC output of
+        that launch of `sfd2_layers`."""
+        sel = sfd2_select_conf(conf)
+        sfd2_check_args(tuple(image.shape))
+        hd = get_handle(image.device)
+        _same_device(packed, image)
+        lib = hd.lib
+        image = image.contiguous().float()
+        B, Cc, H, W = image.shape
+        dev = image.device
+        _, _, Hc, Wc = sfd2_map_sizes(H, W)
+        np_ = 16 * Hc * Wc
+        kout = max(1, min(sel["max_keypoints"], np_) if sel["max_keypoints"] > 0 else np_)
+        kpts, scores, desc, nk, status, out = _sparse_outputs(B, kout, SFD2_DIM, dev)
+        f32 = dict(dtype=torch.float32, device=dev)
+        maps = {}
+        if want_maps:
+            maps = dict(score=torch.empty((B, 4 * Hc, 4 * Wc), **f32), desc_map=torch.empty((B, Hc, Wc, SFD2_DIM), **f32))
+        if layer >= 0:
+            hh, ww, sizes = H, W, []
+            for L in sfd2_layers(self.cfg):
+                if L["stride"] == 2:
+                    hh, ww = (hh - 1) // 2 + 1, (ww - 1) // 2 + 1
+                sizes.append((B, hh, ww, L["cout"]))
+            maps["layer_out"] = torch.empty(sizes[layer], **f32)
+        with self._ws.use(lib.imcui_hip_sfd2_workspace_bytes(self._ca, B, H, W), dev) as ws:
+            hd.launch(
+                lib.imcui_hip_sfd2_forward, self._ca, _ptr(packed), _ptr(image), B, Cc, H, W, sel["conf_th"], sel["remove_borders"], sel["min_keypoints"],
+                sel["max_keypoints"], kout, _ptr(kpts), _ptr(scores), _ptr(desc), _ptr(nk), _ptr(status), _ptr(maps.get("score")), _ptr(maps.get("desc_map")),
+                int(layer), _ptr(maps.get("layer_out")), _ptr(ws), ws.numel(),
+            )  # fmt: skip
+        out.update(maps)
+        return out
+
+    def gconv_probe(self, x: torch.Tensor, w: torch.Tensor, shift: torch.Tensor, relu: bool) -> torch.Tensor:
+        """Test entry: the grouped 3x3 convolution of x [B,H,W,C] (NHWC) with OIHW group weights w [C,CG,3,3] and shift [C]."""
+        hd = get_handle(x.device)
+        x, shift = x.contiguous().float(), shift.contiguous().float()
+        wp = sfd2_pack_group(w.float()).to(x.device)
+        B, H, W, Cc = x.shape
+        out = torch.empty_like(x)
+        hd.launch(hd.lib.imcui_hip_sfd2_gconv_probe, _ptr(x), _ptr(wp), _ptr(shift), B, H, W, Cc, int(w.shape[1]), int(bool(relu)), _ptr(out))
+        return out
+
+    def layers_probe(self, packed: torch.Tensor, x: torch.Tensor, first: int, last: int) -> torch.Tensor:
+        """Test entry: launches [first, last] of the forward's own list on x: the planar image [B,3,H,W] when first == 0, else an NHWC map
+        [B,H,W,cin] -> the last launch's NHWC map."""
+        hd = get_handle(x.device)
+        x = x.contiguous().float()
+        B, H, W = (x.shape[0], x.shape[2], x.shape[3]) if first == 0 else tuple(x.shape[:3])
+        hh, ww = H, W
+        layers = sfd2_layers(self.cfg)
+        for L in layers[first : last + 1]:
+            if L["stride"] == 2:
+                hh, ww = (hh - 1) // 2 + 1, (ww - 1) // 2 + 1
+        out = torch.empty((B, hh, ww, layers[last]["cout"]), dtype=torch.float32, device=x.device)
+        with self._ws.use(hd.lib.imcui_hip_sfd2_layers_workspace_bytes(self._ca, first, last, B, H, W), x.device) as ws:
+            hd.launch(hd.lib.imcui_hip_sfd2_layers_probe, self._ca, _ptr(packed), _ptr(x), first, last, B, H, W, _ptr(out), _ptr(ws), ws.numel())
+        return out
+
+    @staticmethod
+    def score_probe(logits: torch.Tensor) -> torch.Tensor:
+        """Test entry: logits [B,Hc,Wc,16] -> score [B,4Hc,4Wc] (sigmoid, depth-to-space with channel 4 dy + dx)."""
+        hd = get_handle(logits.device)
+        logits = logits.contiguous().float()
+        B, Hc, Wc, _ = logits.shape
+        out = torch.empty((B, 4 * Hc, 4 * Wc), dtype=torch.float32, device=logits.device)
+        hd.launch(hd.lib.imcui_hip_sfd2_score_probe, _ptr(logits), B, Hc, Wc, _ptr(out))
+        return out
+
+    def select_probe(self, score: torch.Tensor, image_size: tuple, conf: dict | None = None) -> dict:
+        """Test entry: NMS, fallback, cut and ranked rows on a score map [B,Hs,Ws] of images of image_size = (H, W)."""
+        sel = sfd2_select_conf(dict(conf or {}))
+        hd = get_handle(score.device)
+        score = score.contiguous().float()
+        B, Hs, Ws = score.shape
+        H, W = image_size
+        dev = score.device
+        kout = max(1, min(sel["max_keypoints"], Hs * Ws) if sel["max_keypoints"] > 0 else Hs * Ws)
+        kpts, scores, _, nk, status, out = _sparse_outputs(B, kout, 1, dev)
+        out.pop("descriptors")
+        out["num_candidates"] = torch.empty((B,), dtype=torch.int32, device=dev)
+        out["threshold"] = torch.empty((B,), dtype=torch.float32, device=dev)
+        out["nms"] = torch.empty((B, Hs, Ws), dtype=torch.float32, device=dev)
+        with self._ws.use(hd.lib.imcui_hip_sfd2_select_workspace_bytes(B, Hs, Ws), dev) as ws:
+            hd.launch(hd.lib.imcui_hip_sfd2_select_probe, _ptr(score), B, Hs, Ws, int(H), int(W), sel["conf_th"], sel["remove_borders"], sel["min_keypoints"],
+                      sel["max_keypoints"], kout, _ptr(kpts), _ptr(scores), _ptr(nk), _ptr(out["num_candidates"]), _ptr(out["threshold"]), _ptr(status),
+                      _ptr(out["nms"]), _ptr(ws), ws.numel())  # fmt: skip
+        return out
+
+    @staticmethod
+    def describe_probe(dmap: torch.Tensor, keypoints: torch.Tensor, nkpts: torch.Tensor, normalise: bool = True):
+        """Test entry: descriptors at keypoints [B,K,2] (x, y in image pixels; nkpts [B] valid rows) of a map dmap [B,h4,w4,128]
+        -> (descriptors [B,K,128], the map the sampler read: normalised over channels when `normalise`)."""
+        hd = get_handle(dmap.device)
+        dmap, keypoints = dmap.contiguous().float(), keypoints.contiguous().float()
+        nkpts = nkpts.to(dmap.device, torch.int32).contiguous()
+        B, h4, w4, _ = dmap.shape
+        K = keypoints.shape[1]
+        out = torch.empty((B, K, SFD2_DIM), dtype=torch.float32, device=dmap.device)
+        dn = torch.empty_like(dmap) if normalise else None
+        hd.launch(hd.lib.imcui_hip_sfd2_describe_probe, _ptr(dmap), B, h4, w4, int(bool(normalise)), _ptr(dn), _ptr(keypoints), _ptr(nkpts), K, _ptr(out))
+        return out, (dn if normalise else dmap)
+
+
 # ------------------------------------------------------------------ NetVLAD
 # (cin, cout, index in torchvision's vgg16().features): VGG-16 to conv5_3, csrc/netvlad.hip
 NETVLAD_LAYERS = ((3, 64, 0), (64, 64, 2), (64, 128, 5), (128, 128, 7), (128, 256, 10), (256, 256, 12), (256, 256, 14), (256, 512, 17), (512, 512, 19),

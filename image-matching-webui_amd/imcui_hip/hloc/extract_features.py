@@ -78,6 +78,14 @@ confs = {
         "model": {"name": "darkfeat", "max_keypoints": 5000, "reliability_threshold": 0.7, "repetability_threshold": 0.7},
         "preprocessing": {"grayscale": False, "force_resize": True, "resize_max": 1600, "width": 640, "height": 480, "dfactor": 8},
     },
+    # imcui/hloc/configs/extractors.py:349-365: SFD2 (the `sfd2` plugin), RGB.  `width` / `height` are read by the UI's `extract` (:130-132)
+    # only; this driver follows `ImageDataset.__getitem__` (:83-88), where `force_resize` scales the longer side to `resize_max`
+    "sfd2": {
+        "output": "feats-sfd2-n4096-r1600",
+        "model": {"name": "sfd2", "max_keypoints": 4096},
+        "preprocessing": {"grayscale": False, "force_resize": True, "resize_max": 1600, "width": 640, "height": 480, "conf_th": 0.001, "multiscale": False,
+                          "scales": [1.0]},
+    },
 }
 
 

@@ -130,6 +130,23 @@ SIGNATURES = {
     "imcui_hip_darkfeat_detect_probe": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 3 + [C.c_float] * 2 + [C.c_int] * 5 + [C.c_void_p] * 6
                                         + [C.c_void_p, C.c_size_t, C.c_void_p]),
     "imcui_hip_darkfeat_describe_probe": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 3 + [C.c_void_p] * 2 + [C.c_int] + [C.c_void_p] * 2),
+    "imcui_hip_sfd2_num_layers": (C.c_int, [C.c_void_p]),
+    "imcui_hip_sfd2_layer": (C.c_char_p, [C.c_void_p, C.c_int, C.c_void_p]),
+    "imcui_hip_sfd2_num_tensors": (C.c_int, [C.c_void_p]),
+    "imcui_hip_sfd2_tensor_name": (C.c_char_p, [C.c_void_p, C.c_int]),
+    "imcui_hip_sfd2_packed_floats": (C.c_size_t, [C.c_void_p]),
+    "imcui_hip_sfd2_pack_weights": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p]),
+    "imcui_hip_sfd2_workspace_bytes": (C.c_size_t, [C.c_void_p] + [C.c_int] * 3),
+    "imcui_hip_sfd2_forward": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_float] + [C.c_int] * 4 + [C.c_void_p] * 7 + [C.c_int] + [C.c_void_p]
+                               + [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "imcui_hip_sfd2_gconv_probe": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 6 + [C.c_void_p] * 2),
+    "imcui_hip_sfd2_layers_workspace_bytes": (C.c_size_t, [C.c_void_p] + [C.c_int] * 5),
+    "imcui_hip_sfd2_layers_probe": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 5 + [C.c_void_p] + [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "imcui_hip_sfd2_score_probe": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 3 + [C.c_void_p] * 2),
+    "imcui_hip_sfd2_select_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
+    "imcui_hip_sfd2_select_probe": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 5 + [C.c_float] + [C.c_int] * 4 + [C.c_void_p] * 7
+                                    + [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "imcui_hip_sfd2_describe_probe": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 4 + [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 2),
     "imcui_hip_dedode_packed_floats": (C.c_size_t, [C.c_void_p]),
     "imcui_hip_dedode_num_tensors": (C.c_int, [C.c_void_p]),
     "imcui_hip_dedode_tensor_name": (C.c_char_p, [C.c_void_p, C.c_int]),

@@ -1120,3 +1120,98 @@ def darkfeat_synth_state(seed: int = 0, bias: bool = False, peak_gain: float = 1
     sd["clf.weight"] = w
     sd["clf.bias"] = torch.tensor([0.0, (lo + hi) / 2])
     return sd
+
+
+# ------------------------------------------------------------------ SFD2
+def _sfd2_simple_nms(s: torch.Tensor, r: int) -> torch.Tensor:
+    """SuperPoint's simple_nms on [B,H,W]."""
+    import torch.nn.functional as F
+
+    def mp(x):
+        return F.max_pool2d(x, 2 * r + 1, 1, r)
+
+    zeros = torch.zeros_like(s)
+    mask = s == mp(s)
+    for _ in range(2):
+        supp = mp(mask.float()) > 0
+        ss = torch.where(supp, zeros, s)
+        mask = mask | ((ss == mp(ss)) & ~supp)
+    return torch.where(mask, s, zeros)
+
+
+def sfd2_synth_state(seed: int = 0, widths=(64, 128, 256), blocks: int = 3, groups: int = 32, hidden: int = 256, k_pb: int = 3, k_db: int = 1,
+                     bn: bool = True, bias: bool = True, share: float = 0.5) -> dict:
+    """Seeded SFD2 (ResNet4x) weights under the recalled key names: `conv1a.0.weight` / `.0.bias` / `.1.{weight, bias, running_mean,
+    running_var, num_batches_tracked}` .. `conv3b`, `conv4.{i}.conv{1,2,3}.weight` + `bn{1,2,3}.*` (conv2 grouped: [C, C / groups, 3, 3]),
+    `convPa` / `convDa` like the trunk, `convPb.*` (16 outputs), `convDb.*` (128).  Convolutions are He-initialised, BatchNorm statistics
+    are drawn near the identity.  A plain draw leaves every score near sigmoid(0) with a spread nobody chose, so convPb is calibrated on a
+    seeded 64 x 64 uniform image (drawn from the same generator, evaluated here with torch's own operations): its logits get a standard
+    deviation of 2 and its bias is bisected so that `share` of the radius-4 NMS maxima inside the 4-pixel border band lie above 0.5 on
+    that image.  At the sizes the tests use (32x48, 50x70, 96x128 and 40x56, seed 0) 32 %, 38 %, 53 % and 42 % of those maxima (19, 53,
+    198 and 31 of them) lie above 0.5; tests/test_sfd2_cpu.py asserts 30 % .. 70 %.  Every maximum is far above the default conf_th of
+    0.001."""
+    import torch.nn.functional as F
+
+    g = torch.Generator().manual_seed(seed)
+    sd = {}
+    c1, c2, c3 = widths
+
+    def rn(*shape, scale=1.0):
+        return torch.randn(*shape, generator=g) * scale
+
+    def conv(stem, bnstem, cout, cin, k, with_bias, gain=1.0):
+        sd[f"{stem}.weight"] = rn(cout, cin, k, k, scale=math.sqrt(2.0) / math.sqrt(cin * k * k))
+        if with_bias:
+            sd[f"{stem}.bias"] = 0.1 * rn(cout)
+        if bn:
+            sd[f"{bnstem}.weight"] = gain * (1.0 + 0.1 * rn(cout))
+            sd[f"{bnstem}.bias"] = 0.1 * rn(cout)
+            sd[f"{bnstem}.running_mean"] = 0.1 * rn(cout)
+            sd[f"{bnstem}.running_var"] = 0.75 + 0.5 * torch.rand(cout, generator=g)
+            sd[f"{bnstem}.num_batches_tracked"] = torch.tensor(1000, dtype=torch.long)
+
+    chain = (("conv1a", 3, c1), ("conv1b", c1, c1), ("conv2a", c1, c2), ("conv2b", c2, c2), ("conv3a", c2, c3), ("conv3b", c3, c3))
+    for name, cin, cout in chain:
+        conv(f"{name}.0", f"{name}.1", cout, cin, 3, bias)
+    for i in range(blocks):
+        conv(f"conv4.{i}.conv1", f"conv4.{i}.bn1", c3, c3, 1, False)
+        conv(f"conv4.{i}.conv2", f"conv4.{i}.bn2", c3, c3 // groups, 3, False)
+        conv(f"conv4.{i}.conv3", f"conv4.{i}.bn3", c3, c3, 1, False, gain=0.5)
+    conv("convPa.0", "convPa.1", hidden, c3, 3, bias)
+    conv("convDa.0", "convDa.1", hidden, c3, 3, bias)
+    sd["convDb.weight"] = rn(128, hidden, k_db, k_db, scale=1.0 / math.sqrt(hidden * k_db * k_db))
+    sd["convDb.bias"] = 0.1 * rn(128)
+    wpb = rn(16, hidden, k_pb, k_pb, scale=1.0 / math.sqrt(hidden * k_pb * k_pb))
+
+    # ---- the calibration image through the network
+    def layer(x, stem, bnstem, stride=1, ngroups=1, pad=1):
+        x = F.conv2d(x, sd[f"{stem}.weight"], sd.get(f"{stem}.bias"), stride=stride, padding=pad, groups=ngroups)
+        if bn:
+            x = F.batch_norm(x, sd[f"{bnstem}.running_mean"], sd[f"{bnstem}.running_var"], sd[f"{bnstem}.weight"], sd[f"{bnstem}.bias"], False, 0.0, 1e-5)
+        return x
+
+    img = torch.rand(1, 3, 64, 64, generator=g)
+    x = (img - torch.tensor([0.485, 0.456, 0.406]).view(1, 3, 1, 1)) / torch.tensor([0.229, 0.224, 0.225]).view(1, 3, 1, 1)
+    for name, _, _ in chain:
+        x = F.relu(layer(x, f"{name}.0", f"{name}.1", stride=2 if name in ("conv1b", "conv2b") else 1))
+    for i in range(blocks):
+        y = F.relu(layer(x, f"conv4.{i}.conv1", f"conv4.{i}.bn1", pad=0))
+        y = F.relu(layer(y, f"conv4.{i}.conv2", f"conv4.{i}.bn2", ngroups=groups))
+        x = F.relu(layer(y, f"conv4.{i}.conv3", f"conv4.{i}.bn3", pad=0) + x)
+    hid = F.relu(layer(x, "convPa.0", "convPa.1"))
+    logit = F.conv2d(hid, wpb, padding=k_pb // 2)
+    wpb = wpb * (2.0 / logit.std())
+    logit = F.conv2d(hid, wpb, padding=k_pb // 2)
+
+    def share_above(b0):
+        s = F.pixel_shuffle(torch.sigmoid(logit + b0), 4)[:, 0]
+        nms = _sfd2_simple_nms(s, 4)[0, 4:-4, 4:-4]
+        return (nms[nms > 0] > 0.5).float().mean().item()
+
+    lo, hi = -30.0, 30.0
+    for _ in range(40):
+        mid = (lo + hi) / 2
+        lo, hi = (mid, hi) if share_above(mid) < share else (lo, mid)
+    sd["convPb.weight"] = wpb
+    sd["convPb.bias"] = torch.full((16,), (lo + hi) / 2)
+    return sd

@@ -416,6 +416,65 @@ int imcui_hip_darkfeat_detect_probe(imcui_hip_t* h, const float* score, int B, i
 int imcui_hip_darkfeat_describe_probe(imcui_hip_t* h, const float* dmap, int B, int h4, int w4, const float* keypoints, const int* nkpts, int K,
                                       float* descriptors, void* stream);
 
+/* ---- SFD2 (zoo entry sfd2+mnn: `feature: sfd2` + NN-mutual; imcui/hloc/extractors/sfd2.py) ------------------------------- */
+/* pram.nets.sfd2.load_sfd2(weight_path) (replaces sfd2.py:31) is not part of the reference checkout (third_party is empty): the ResNet4x
+ * network is restated from its description (tests/sfd2_reference.py) and parity with upstream's code is NOT pinned (INTEGRATION.md,
+ * "SFD2: what is pinned").  cfg [host, 12 ints], read from the checkpoint's shapes by the binding: c1 (64), c2, c3 (trunk widths,
+ * multiples of 32 up to 512), bottlenecks of conv4 (0..8), channels per group of their 3x3 (4 / 8 / 16), hidden width of either head,
+ * kernel size of convPb and of convDb (1 or 3), BatchNorm behind the convolutions (0 / 1), bias on the trunk / head convolutions,
+ * bias on the bottleneck convolutions, 0.  The backbone is ONE table in csrc/sfd2.hip (SFD2_LAYERS), readable through
+ * imcui_hip_sfd2_layer: launch name, and out5 = kind (0 layer 0 on the VALU, 1 3x3 implicit GEMM, 2 1x1 GEMM, 3 grouped 3x3, 4 the two
+ * heads' hidden layers as one launch), cin, cout, stride, place in a bottleneck (0 none, 1 first, 2 middle, 3 last: + identity).
+ * Tensors in imcui_hip_sfd2_tensor_name order, upstream's state-dict keys: `conv1a.0.weight` .. (`.0.bias`, `.1.{weight, bias,
+ * running_mean, running_var}`), `conv4.{i}.conv{1,2,3}.weight` / `conv4.{i}.bn{1,2,3}.*`, `convPa.0` / `convPa.1`, `convDa.0` /
+ * `convDa.1`, `convPb.{weight, bias}`, `convDb.{weight, bias}`. */
+int imcui_hip_sfd2_num_layers(const int* cfg);
+const char* imcui_hip_sfd2_layer(const int* cfg, int i, int* out5);
+int imcui_hip_sfd2_num_tensors(const int* cfg);
+const char* imcui_hip_sfd2_tensor_name(const int* cfg, int i);
+size_t imcui_hip_sfd2_packed_floats(const int* cfg);
+/* BatchNorm (eval, eps 1e-5) is folded in float32; tvf.Normalize's mean / std (sfd2.py:24-26) go into the packed header. */
+int imcui_hip_sfd2_pack_weights(const int* cfg, const float* const* tensors, float* packed);
+/* Scratch of imcui_hip_sfd2_forward: B images of H x W (H, W >= 16). */
+size_t imcui_hip_sfd2_workspace_bytes(const int* cfg, int B, int H, int W);
+/* sfd2.py:35-44 `_forward`: `self.norm_rgb(data["image"])` (:37) and `self.net.extract_local_global(data, config=self.conf)` (:36).
+ * image [dev, B,C,H,W] RGB in [0, 1] with C == 3 (anything else is refused), H, W >= 16.  (x - mean_c) / std_c where layer 0 reads the
+ * image; trunk to 1/4 resolution (Hc = ceil(ceil(H / 2) / 2)); score = sigmoid(convPb(relu(convPa(x)))) through a 4 x 4 depth-to-space
+ * (channel 4 dy + dx) -> [4 Hc, 4 Wc]; descriptors = F.normalize(convDb(relu(convDa(x)))) at 1/4 resolution.  Selection: simple_nms radius
+ * 4; score > conf_th (strict) and not within remove_borders pixels of the IMAGE's border (the map may exceed the image by up to 3 rows /
+ * columns: nothing outside the image is kept); an image with fewer than min_keypoints such candidates is selected again with threshold 0
+ * (decided on the device); the max_keypoints highest scores stay (0: all; negative: refused).  Output in DESCENDING score order, equal
+ * scores by ascending pixel index (torch.topk leaves that open).  descriptor = sample_descriptors with s = 4 (grid_sample bilinear,
+ * align_corners=True, zero padding) / max(norm, 1e-12).  kout >= min(max_keypoints or all, 16 Hc Wc).  Outputs, first num_keypoints[b]
+ * rows valid, the rest zero:
+ *   keypoints [dev, B,kout,2] (x, y), integer-valued;  scores [dev, B,kout];  descriptors [dev, B,kout,128];  num_keypoints [dev, B] int32
+ *   status [dev, 1] int32 optional: always 0 (the candidate list holds every score-map pixel, so it cannot overflow)
+ *   optional debug outputs: dbg_score [B,4 Hc,4 Wc], dbg_desc [B,Hc,Wc,128] (normalised), dbg_map: the NHWC output of launch dbg_layer
+ * No host synchronisation; a row's bits do not depend on the batch. */
+int imcui_hip_sfd2_forward(imcui_hip_t* h, const int* cfg, const float* packed, const float* image, int B, int C, int H, int W, float conf_th,
+                           int remove_borders, int min_keypoints, int max_keypoints, int kout, float* keypoints, float* scores, float* descriptors,
+                           int* num_keypoints, int* status, float* dbg_score, float* dbg_desc, int dbg_layer, float* dbg_map, void* ws, size_t ws_bytes,
+                           void* stream);
+/* Test entries.  gconv_probe: the grouped 3x3 convolution (F.conv2d(groups=C / cg), pad 1) of x [dev, B,H,W,C] with weights in the packed
+ * order [group][tap][ci][co] and shift [C] as the start of every sum, optional ReLU.  layers_probe: launches [first, last] of the
+ * forward's own list on the planar image (first == 0) or an NHWC map [dev, B,H,W,cin] -> the last launch's NHWC map; ws:
+ * imcui_hip_sfd2_layers_workspace_bytes.  score_probe: logits [dev, B,Hc,Wc,16] -> score [dev, B,4 Hc,4 Wc].  select_probe: the selection on
+ * a given score map [dev, B,Hs,Ws] of H x W images (H <= Hs, W <= Ws); num_candidates [dev, B], eff [dev, B] (the per-image threshold)
+ * and nms_map optional; ws: imcui_hip_sfd2_select_workspace_bytes.  describe_probe: descriptors at keypoints [dev, B,K,2] (nkpts [dev, B]
+ * valid rows) of a map dmap [dev, B,h4,w4,128], normalised into dmap_out first when `normalise`. */
+int imcui_hip_sfd2_gconv_probe(imcui_hip_t* h, const float* x, const float* w_packed, const float* shift, int B, int H, int W, int C, int cg, int relu,
+                               float* out, void* stream);
+size_t imcui_hip_sfd2_layers_workspace_bytes(const int* cfg, int first, int last, int B, int H, int W);
+int imcui_hip_sfd2_layers_probe(imcui_hip_t* h, const int* cfg, const float* packed, const float* in, int first, int last, int B, int H, int W, float* out,
+                                void* ws, size_t ws_bytes, void* stream);
+int imcui_hip_sfd2_score_probe(imcui_hip_t* h, const float* logits, int B, int Hc, int Wc, float* score, void* stream);
+size_t imcui_hip_sfd2_select_workspace_bytes(int B, int Hs, int Ws);
+int imcui_hip_sfd2_select_probe(imcui_hip_t* h, const float* score, int B, int Hs, int Ws, int H, int W, float conf_th, int remove_borders, int min_keypoints,
+                                int max_keypoints, int kout, float* keypoints, float* scores, int* num_keypoints, int* num_candidates, float* eff, int* status,
+                                float* nms_map, void* ws, size_t ws_bytes, void* stream);
+int imcui_hip_sfd2_describe_probe(imcui_hip_t* h, const float* dmap, int B, int h4, int w4, int normalise, float* dmap_out, const float* keypoints,
+                                  const int* nkpts, int K, float* descriptors, void* stream);
+
 /* ---- DeDoDe (zoo entry dedode: `feature: dedode` + Dual-Softmax; imcui/hloc/extractors/dedode.py) ----------------------- */
 /* dedode_detector_L (vgg19_bn encoder) and dedode_descriptor_B (vgg11_bn encoder) of Parskatt/DeDoDe, each with a decoder of four
  * ConvRefiners (scales 8, 4, 2, 1).  The refiners' shapes are READ from the checkpoint by the binding and handed over as
