@@ -25,6 +25,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 
+#include "imcui_hip.h"
 #include "simred.h"
 
 #define SR_PLD 132      // floats per parked COLUMN of 128 rows (+ 4: the 16-byte reads of four adjacent columns x four row groups hit 64 different banks)

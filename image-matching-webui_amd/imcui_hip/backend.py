@@ -9,12 +9,14 @@ from __future__ import annotations
 
 import contextlib
 import ctypes as C
+import keyword
 import math
 import threading
 
 import numpy as np
 import torch
 
+from . import header
 from .lib_loader import ImcuiHipError, load_library
 
 SP_ORDER = ["conv1a", "conv1b", "conv2a", "conv2b", "conv3a", "conv3b", "conv4a", "conv4b", "convPa", "convPb", "convDa", "convDb"]
@@ -68,6 +70,18 @@ def _stream_ptr() -> C.c_void_p:
 
 def _ptr(t: torch.Tensor | None) -> C.c_void_p:
     return C.c_void_p(0 if t is None else t.data_ptr())
+
+
+PY_FIELD_NAMES = {"in": "inp"}  # descriptor fields of the header whose names are Python keywords -> their spelling here
+
+
+def _desc_fields(struct: str) -> list:
+    """`_fields_` of the ctypes class of a descriptor struct of include/imcui_hip.h, in the header's order and types."""
+    fields = [(PY_FIELD_NAMES.get(name, name), t) for name, t in header.read().structs[struct]]
+    for name, _ in fields:
+        if keyword.iskeyword(name):
+            raise ImcuiHipError(f"{struct}.{name} is a Python keyword: give it a spelling in PY_FIELD_NAMES")
+    return fields
 
 
 def _fill_desc(d, fields: dict, who: str):
@@ -3591,21 +3605,9 @@ def gemm_route_name(route: int) -> str:
 
 
 class GemmDesc(C.Structure):
-    """ctypes mirror of imcui_hip_gemm_desc (include/imcui_hip.h); the CPU suite compares its size with the library's."""
+    """imcui_hip_gemm_desc, laid out from include/imcui_hip.h."""
 
-    _fields_ = [("epi", C.c_int), ("A", C.c_void_p), ("lda", C.c_long), ("A2", C.c_void_p), ("lda2", C.c_long), ("K1", C.c_int),
-                ("W", C.c_void_p), ("ldw", C.c_long), ("Wh", C.c_void_p), ("Wl", C.c_void_p), ("wscale", C.c_void_p), ("bias", C.c_void_p),
-                ("C", C.c_void_p), ("ldc", C.c_long), ("M", C.c_int), ("N", C.c_int), ("K", C.c_int), ("alpha", C.c_float),
-                ("cnt", C.c_void_p), ("active", C.c_void_p), ("rows_per_seq", C.c_int), ("wsel", C.c_void_p), ("wsel_off", C.c_int),
-                ("w_stride", C.c_long), ("b_stride", C.c_long), ("batch", C.c_int), ("a_bs", C.c_long), ("a2_bs", C.c_long),
-                ("w_bs", C.c_long), ("c_bs", C.c_long), ("mcnt", C.c_void_p), ("ncnt", C.c_void_p), ("cnt_stride", C.c_int),
-                ("Q", C.c_void_p), ("Kt", C.c_void_p), ("V", C.c_void_p), ("v_transposed", C.c_int), ("split_out", C.c_int),
-                ("plane_halves", C.c_size_t), ("conv_k", C.c_int), ("conv_stride", C.c_int), ("conv_pad", C.c_int), ("conv_hin", C.c_int),
-                ("conv_win", C.c_int), ("conv_hout", C.c_int), ("conv_wout", C.c_int), ("conv_cin", C.c_int), ("resid", C.c_void_p),
-                ("ldr", C.c_long), ("rup_h", C.c_int), ("rup_w", C.c_int), ("rup_align", C.c_int), ("act", C.c_int), ("single", C.c_int),
-                ("rope_cos", C.c_void_p), ("rope_sin", C.c_void_p), ("heads", C.c_int), ("role0", C.c_int), ("rope_seq_row0", C.c_void_p),
-                ("ln_stats", C.c_void_p), ("ln_rowsum", C.c_void_p), ("ln_stride", C.c_long),
-                ("conv_dil", C.c_int)]  # fmt: skip
+    _fields_ = _desc_fields("imcui_hip_gemm_desc")
     DEFAULTS = {"batch": 1, "cnt_stride": 1, "conv_stride": 1, "rup_align": 1, "heads": 4, "alpha": 1.0}
 
 
@@ -3686,12 +3688,9 @@ def attn_route_name(route: int) -> str:
 
 
 class AttnDesc(C.Structure):
-    """ctypes mirror of imcui_hip_attn_desc (include/imcui_hip.h); the CPU suite compares its size with the library's."""
+    """imcui_hip_attn_desc, laid out from include/imcui_hip.h."""
 
-    _fields_ = [("Q", C.c_void_p), ("K", C.c_void_p), ("V", C.c_void_p), ("O", C.c_void_p), ("cnt", C.c_void_p), ("active", C.c_void_p),
-                ("nseq", C.c_int), ("heads", C.c_int), ("rows_per_seq", C.c_int), ("cross", C.c_int), ("log2_domain", C.c_int),
-                ("single", C.c_int), ("variant", C.c_int), ("V6", C.c_void_p), ("V6_bytes", C.c_size_t), ("v6_ready", C.c_int),
-                ("part", C.c_void_p), ("part_bytes", C.c_size_t)]  # fmt: skip
+    _fields_ = _desc_fields("imcui_hip_attn_desc")
     DEFAULTS = {"heads": 4, "variant": -1}
 
 
@@ -3740,11 +3739,9 @@ def ffn_route_name(route: int) -> str:
 
 
 class FfnDesc(C.Structure):
-    """ctypes mirror of imcui_hip_ffn_desc (include/imcui_hip.h); the CPU suite compares its size with the library's."""
+    """imcui_hip_ffn_desc, laid out from include/imcui_hip.h."""
 
-    _fields_ = [("x", C.c_void_p), ("ctx", C.c_void_p), ("out", C.c_void_p), ("w1h", C.c_void_p), ("w1l", C.c_void_p), ("w2h", C.c_void_p),
-                ("w2l", C.c_void_p), ("s1", C.c_void_p), ("s2", C.c_void_p), ("b1", C.c_void_p), ("gamma", C.c_void_p), ("beta", C.c_void_p),
-                ("b2", C.c_void_p), ("act", C.c_int), ("M", C.c_int), ("cnt", C.c_void_p), ("active", C.c_void_p), ("rows_per_seq", C.c_int)]  # fmt: skip
+    _fields_ = _desc_fields("imcui_hip_ffn_desc")
 
 
 class FfnWeights:
@@ -3809,13 +3806,9 @@ def conv_feature_names(mask: int) -> list:
 
 
 class ConvDesc(C.Structure):
-    """ctypes mirror of imcui_hip_conv_desc (include/imcui_hip.h); the CPU suite compares its size with the library's."""
+    """imcui_hip_conv_desc, laid out from include/imcui_hip.h."""
 
-    _fields_ = [("entry", C.c_int), ("inp", C.c_void_p), ("wp", C.c_void_p), ("wh", C.c_void_p), ("wl", C.c_void_p), ("wscale", C.c_void_p),
-                ("bias", C.c_void_p), ("out", C.c_void_p), ("B", C.c_int), ("H", C.c_int), ("W", C.c_int), ("Cin", C.c_int), ("Cout", C.c_int),
-                ("relu", C.c_int), ("pool", C.c_int), ("resid", C.c_void_p), ("resid2", C.c_void_p), ("cin_stride", C.c_int),
-                ("cout_live", C.c_int), ("single", C.c_int), ("head", C.c_int), ("head_w", C.c_void_p), ("head_b", C.c_void_p),
-                ("head_pts", C.c_void_p), ("head_conf", C.c_void_p), ("head_raw", C.c_void_p), ("w1a", C.c_void_p), ("b1a", C.c_void_p)]  # fmt: skip
+    _fields_ = _desc_fields("imcui_hip_conv_desc")
 
 
 class ConvWeights:
@@ -3933,18 +3926,14 @@ def attention_mx_f32(q, k, v, cnt, cross=False):
 
 # ------------------------------------------------------------------ the list-building blocks of csrc/select.h, entered directly
 SELECT_OPS = {"compact": 0, "scan": 1, "order_key": 2, "kth32": 3, "kth64": 4, "rank4": 5, "rank16": 6, "keep": 7, "cut": 8}
-SELECT_MAXB = 8  # IMCUI_SELECT_MAXB
+SELECT_MAXB = header.read().defines["IMCUI_SELECT_MAXB"]
 SELECT_RULES = {1: "op", 2: "B", 3: "n / capacity", 4: "k", 5: "cap / limit", 6: "null pointer", 7: "nlev"}  # imcui_hip_select_desc_check
 
 
 class SelectDesc(C.Structure):
-    """ctypes mirror of imcui_hip_select_desc (include/imcui_hip.h); the CPU suite compares its size with the library's."""
+    """imcui_hip_select_desc, laid out from include/imcui_hip.h."""
 
-    _fields_ = [("op", C.c_int), ("B", C.c_int), ("n", C.c_int), ("capacity", C.c_int), ("cap", C.c_int), ("limit", C.c_int), ("filter", C.c_int),
-                ("nlev", C.c_int), ("n_row", C.c_int * SELECT_MAXB), ("k_row", C.c_int * SELECT_MAXB), ("kth", C.c_ulonglong), ("score", C.c_void_p),
-                ("thr", C.c_void_p), ("key64", C.c_void_p), ("in_i32", C.c_void_p), ("n_dev", C.c_void_p), ("out_score", C.c_void_p),
-                ("out_idx", C.c_void_p), ("out_count", C.c_void_p), ("out_i32", C.c_void_p), ("out_aux", C.c_void_p), ("out_key32", C.c_void_p),
-                ("out_key64", C.c_void_p), ("status", C.c_void_p)]  # fmt: skip
+    _fields_ = _desc_fields("imcui_hip_select_desc")
 
 
 def select_desc(**fields) -> SelectDesc:

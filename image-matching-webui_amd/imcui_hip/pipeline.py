@@ -7,6 +7,9 @@ runs batch 1 (imcui/hloc/match_features.py:172-174).
 """
 from __future__ import annotations
 
+import contextlib
+import gc
+
 import torch
 
 from . import backend
@@ -77,6 +80,23 @@ class SuperPointSuperGluePipeline(torch.nn.Module):
         }  # fmt: skip
 
 
+@contextlib.contextmanager
+def _capture(graph: torch.cuda.CUDAGraph, **kwargs):
+    """`torch.cuda.graph(graph, **kwargs)` with Python's cyclic collector kept out of the capture.  A collection that starts inside a
+    capture runs the destructors of whatever dead cycles there are on the capturing thread; a dropped plugin with `hip_graph` is such a
+    cycle (plugin -> _graphs -> GraphedCall -> fn -> plugin), and destroying its `torch.cuda.CUDAGraph` synchronises the device, which a
+    capture forbids: the process aborts.  torch no longer collects before a capture by default, so: collect now, none until it ends."""
+    enabled = gc.isenabled()
+    gc.disable()
+    try:
+        gc.collect()
+        with torch.cuda.graph(graph, **kwargs):
+            yield
+    finally:
+        if enabled:
+            gc.enable()
+
+
 class GraphedPipeline:
     """One forward of a pipeline captured in a HIP graph and replayed (fixed image shapes and batch size).
 
@@ -99,7 +119,7 @@ class GraphedPipeline:
             torch.cuda.current_stream(image0.device).wait_stream(side)
             torch.cuda.synchronize(image0.device)
             self.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph):
+            with _capture(self.graph):
                 self.out = pipe(self.image0, self.image1)
 
     @torch.no_grad()
@@ -133,7 +153,7 @@ class GraphedCall:
             torch.cuda.current_stream(dev).wait_stream(self.stream)
             torch.cuda.synchronize(dev)
             self.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph, stream=self.stream):
+            with _capture(self.graph, stream=self.stream):
                 self.out = fn(*self.static_in)
 
     @torch.no_grad()

@@ -22,6 +22,9 @@ def test_every_header_symbol_is_exported_and_bound(lib):
     for name in sorted(declared):
         assert hasattr(lib, name), f"{name} declared in include/imcui_hip.h but not exported"
         assert name in SIGNATURES, f"{name} has no ctypes signature"
+    for name, (restype, argtypes) in SIGNATURES.items():  # what the loader set on the library's function objects is exactly the table
+        fn = getattr(lib, name)
+        assert fn.restype is restype and list(fn.argtypes) == list(argtypes), name
     assert lib.imcui_hip_version() >= 100
 
 
