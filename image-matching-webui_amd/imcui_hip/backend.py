@@ -490,6 +490,201 @@ class XFeatHIP:
         return near, bil, cub
 
 
+# ------------------------------------------------------------------ LiftFeat
+LIFTFEAT_GROUPS = ("skip1", "block1", "block2", "block3", "block4", "block5", "block_fusion", "keypoint_head", "normal_head", "feature_boost")
+LIFTFEAT_ALIGN_CORNERS, LIFTFEAT_SLOPE = 1, 0.1  # the up-sampling stages of the normal head (tests/liftfeat_reference.py, TABLE)
+
+
+def liftfeat_config(sd: dict) -> dict:
+    """Widths, depth and optional parts of the lifting network from the checkpoint's shapes and keys; a key group the layout does not
+    know and a trunk tensor whose width differs from XFeat's are refused by name."""
+    for k in sd:
+        if k.split(".")[0] not in LIFTFEAT_GROUPS:
+            raise ImcuiHipError(f"LiftFeat state dict: '{k}' belongs to no known key group ({', '.join(LIFTFEAT_GROUPS)})")
+    trunk = xfeat_tensor_shapes()
+    for k, v in sd.items():
+        if k in trunk and tuple(v.shape) != trunk[k]:
+            raise ImcuiHipError(f"LiftFeat state dict: '{k}' has shape {tuple(v.shape)}, XFeat's trunk has {trunk[k]}")
+    fb = "feature_boost"
+
+    def out_width(key):
+        if f"{key}.weight" not in sd:
+            raise ImcuiHipError(f"LiftFeat state dict: '{key}.weight' is missing")
+        return int(sd[f"{key}.weight"].shape[0])
+
+    layers = sorted({int(k.split(".")[2]) for k in sd if k.startswith(f"{fb}.layers.")})
+    if not layers or layers != list(range(len(layers))):
+        raise ImcuiHipError(f"LiftFeat state dict: '{fb}.layers' must be numbered 0 .. n - 1, got {layers}")
+    kenc = any(k.startswith(f"{fb}.kenc.") for k in sd)
+    cfg = {"kenc": int(kenc), "ffn": out_width(f"{fb}.layers.0.ffn.0"), "denc": out_width(f"{fb}.denc.0"), "nenc1": out_width(f"{fb}.nenc.0"),
+           "nenc2": out_width(f"{fb}.nenc.2"), "kenc1": out_width(f"{fb}.kenc.0") if kenc else 0, "kenc2": out_width(f"{fb}.kenc.2") if kenc else 0,
+           "n_layers": len(layers)}  # fmt: skip
+    if load_library().imcui_hip_liftfeat_packed_floats(liftfeat_cfg_array(cfg)) == 0:
+        raise ImcuiHipError(f"LiftFeat: configuration {cfg} is not supported (hidden widths: multiples of 32 up to 128, second hidden width 32 or 64, "
+                            "1 .. 8 layers)")  # fmt: skip
+    return cfg
+
+
+def liftfeat_cfg_array(cfg: dict):
+    return (C.c_int * 8)(cfg["kenc"], cfg["ffn"], cfg["denc"], cfg["nenc1"], cfg["nenc2"], cfg["kenc1"], cfg["kenc2"], cfg["n_layers"])
+
+
+def liftfeat_tensor_names(cfg: dict) -> list[str]:
+    lib, ca = load_library(), liftfeat_cfg_array(cfg)
+    return [lib.imcui_hip_liftfeat_tensor_name(ca, i).decode() for i in range(lib.imcui_hip_liftfeat_num_tensors(ca))]
+
+
+def liftfeat_tensor_shapes(cfg: dict) -> dict:
+    shapes = {k: v for k, v in xfeat_tensor_shapes().items() if not k.startswith("heatmap_head.")}
+    for s, c in enumerate((64, 32, 16)):
+        shapes[f"normal_head.{s}.conv.weight"] = (c // 2, c, 3, 3)
+        for k in ("conv.bias", "bn.weight", "bn.bias", "bn.running_mean", "bn.running_var"):
+            shapes[f"normal_head.{s}.{k}"] = (c // 2,)
+    shapes["normal_head.3.weight"], shapes["normal_head.3.bias"] = (3, 8, 1, 1), (3,)
+
+    def lin(stem, cin, cout):
+        shapes[f"{stem}.weight"], shapes[f"{stem}.bias"] = (cout, cin), (cout,)
+
+    fb = "feature_boost"
+    encoders = {"denc": (64, cfg["denc"], 64), "nenc": (192, cfg["nenc1"], cfg["nenc2"], 64)}
+    if cfg["kenc"]:
+        encoders["kenc"] = (65, cfg["kenc1"], cfg["kenc2"], 64)
+    for name, w in encoders.items():
+        for i in range(len(w) - 1):
+            lin(f"{fb}.{name}.{2 * i}", w[i], w[i + 1])
+    for i in range(cfg["n_layers"]):
+        p = f"{fb}.layers.{i}"
+        for n in ("q", "k", "v", "proj"):
+            lin(f"{p}.attn.{n}", 64, 64)
+        lin(f"{p}.ffn.0", 64, cfg["ffn"])
+        lin(f"{p}.ffn.2", cfg["ffn"], 64)
+        for n in ("norm1", "norm2"):
+            shapes[f"{p}.{n}.weight"], shapes[f"{p}.{n}.bias"] = (64,), (64,)
+    lin(f"{fb}.final_proj", 64, 64)
+    return shapes
+
+
+def pack_liftfeat(state_dict: dict):
+    """LiftFeat state dict -> (packed float32 buffer (host), cfg).  `num_batches_tracked` counters are dropped; every other key is consumed
+    exactly once and every shape checked."""
+    lib = load_library()
+    sd = {k: v for k, v in state_dict.items() if not k.endswith("num_batches_tracked")}
+    cfg = liftfeat_config(sd)
+    ca = liftfeat_cfg_array(cfg)
+    return _pack_named("LiftFeat", "the restated", liftfeat_tensor_names(cfg), liftfeat_tensor_shapes(cfg), sd, lib.imcui_hip_liftfeat_packed_floats(ca),
+                       lib.imcui_hip_liftfeat_pack_weights, ca), cfg  # fmt: skip
+
+
+def liftfeat_check_args(image_shape) -> None:
+    """Refused before anything is launched: the reference's wrapper runs `squeeze().transpose(1, 2, 0)` (liftfeat.py:35-36), which fails on
+    a gray image."""
+    if len(image_shape) != 4 or image_shape[1] != 3:
+        raise ValueError(f"LiftFeat expects an RGB image [B,3,H,W] (the wrapper's transpose(1, 2, 0) needs three channels), got shape {tuple(image_shape)}")
+
+
+def liftfeat_pad(v: int) -> int:
+    return (v + 31) // 32 * 32
+
+
+class LiftFeatHIP:
+    def __init__(self, cfg: dict):
+        self.cfg = cfg
+        self._ca = liftfeat_cfg_array(cfg)
+        self._ws = _Workspace()
+
+    def forward(self, packed: torch.Tensor, image: torch.Tensor, conf: dict, want_dense: bool = False, kcap: int | None = None):
+        """image [B,3,H,W] float32 in [0,1] on the GPU -> fixed-stride outputs, no host synchronisation: keypoints [B,K,2], scores [B,K],
+        descriptors [B,K,64], num_keypoints [B] int32, status [1] int32 (bit 1: `kcap` too small); with `want_dense` also kpt_heat
+        [B,Hp,Wp], normals [B,Hp/8,Wp/8,192], boosted [B,Hp/8,Wp/8,64].  Order per image: row-major when the count is at most
+        `max_keypoints`, else ascending score (the last `max_keypoints`; 0 keeps all, -k drops the k lowest)."""
+        liftfeat_check_args(tuple(image.shape))
+        hd = get_handle(image.device)
+        _same_device(packed, image)
+        lib = hd.lib
+        image = image.contiguous().float()
+        B, Cc, H, W = image.shape
+        k = int(conf["max_keypoints"])
+        bound = lib.imcui_hip_liftfeat_max_keypoints_bound(H, W)
+        if kcap is None:
+            kcap = bound if k <= 0 else max(1, min(k, bound))
+        dev = image.device
+        Hp, Wp = liftfeat_pad(H), liftfeat_pad(W)
+        kpts, scores, desc, nk, status, out = _sparse_outputs(B, kcap, 64, dev)
+        heat = torch.empty((B, Hp, Wp), dtype=torch.float32, device=dev) if want_dense else None
+        nrm = torch.empty((B, Hp // 8, Wp // 8, 192), dtype=torch.float32, device=dev) if want_dense else None
+        boost = torch.empty((B, Hp // 8, Wp // 8, 64), dtype=torch.float32, device=dev) if want_dense else None
+        with self._ws.use(lib.imcui_hip_liftfeat_workspace_bytes(B, H, W), dev) as ws:
+            hd.launch(
+                lib.imcui_hip_liftfeat_forward, self._ca, _ptr(packed), _ptr(image), B, Cc, H, W, float(conf["keypoint_threshold"]), k, kcap,
+                _ptr(kpts), _ptr(scores), _ptr(desc), _ptr(nk), _ptr(status), _ptr(heat), _ptr(nrm), _ptr(boost), _ptr(ws), ws.numel(),
+            )  # fmt: skip
+        if want_dense:
+            out.update(kpt_heat=heat, normals=nrm, boosted=boost)
+        return out
+
+    # ---- test entries
+    def input_probe(self, image: torch.Tensor):
+        """image [B,3,H,W] -> gray [B,Hp,Wp] (zero in the pad), norm [B,2] = (invstd, -mean * invstd) over the padded image."""
+        hd = get_handle(image.device)
+        image = image.contiguous().float()
+        B, _, H, W = image.shape
+        Hp, Wp = liftfeat_pad(H), liftfeat_pad(W)
+        gray = torch.empty((B, Hp, Wp), dtype=torch.float32, device=image.device)
+        norm = torch.empty((B, 2), dtype=torch.float32, device=image.device)
+        with self._ws.use(B * ((Hp * Wp + 4095) // 4096) * 16, image.device) as ws:
+            hd.launch(hd.lib.imcui_hip_liftfeat_input_probe, _ptr(image), B, H, W, _ptr(gray), _ptr(norm), _ptr(ws), ws.numel())
+        return gray, norm
+
+    def upconv_probe(self, packed: torch.Tensor, x: torch.Tensor, stage: int, fused: bool = False, align_corners: bool = True,
+                     slope: float = LIFTFEAT_SLOPE):
+        """Up-conv stage 0 / 1 / 2 on x [B,h,w,cin] (NHWC) -> [B,2h,2w,cin/2]; `fused` (stage 2) -> the unfolded unit normals
+        [B,2h/8,2w/8,192]."""
+        hd = get_handle(x.device)
+        x = x.contiguous().float()
+        B, h, w, cin = x.shape
+        if cin != (64, 32, 16)[stage]:
+            raise ValueError(f"stage {stage} takes {(64, 32, 16)[stage]} channels, got {cin}")
+        shape = (B, 2 * h // 8, 2 * w // 8, 192) if fused else (B, 2 * h, 2 * w, cin // 2)
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+        hd.launch(hd.lib.imcui_hip_liftfeat_upconv_probe, self._ca, _ptr(packed), _ptr(x), stage, int(fused), B, h, w, int(align_corners), float(slope), _ptr(out))
+        return out
+
+    def booster_probe(self, packed: torch.Tensor, d: torch.Tensor, k: torch.Tensor, n: torch.Tensor):
+        """d [B,N,64], k [B,N,65], n [B,N,192] -> (out [B,N,64] unit rows, x_enc [B,N,64] the encoders' sum)."""
+        hd = get_handle(d.device)
+        d, k, n = d.contiguous().float(), k.contiguous().float(), n.contiguous().float()
+        B, N, _ = d.shape
+        out, xe = torch.empty_like(d), torch.empty_like(d)
+        with self._ws.use(hd.lib.imcui_hip_liftfeat_tokens_workspace_bytes(B, N), d.device) as ws:
+            hd.launch(hd.lib.imcui_hip_liftfeat_booster_probe, self._ca, _ptr(packed), _ptr(d), _ptr(k), _ptr(n), B, N, _ptr(out), _ptr(xe), _ptr(ws), ws.numel())
+        return out, xe
+
+    def aft_probe(self, packed: torch.Tensor, x: torch.Tensor, layer: int):
+        """AFT layer `layer` on x [B,N,64] -> (out [B,N,64], kv [B,64])."""
+        hd = get_handle(x.device)
+        x = x.contiguous().float()
+        B, N, _ = x.shape
+        out = torch.empty_like(x)
+        kv = torch.empty((B, 64), dtype=torch.float32, device=x.device)
+        with self._ws.use(hd.lib.imcui_hip_liftfeat_tokens_workspace_bytes(B, N), x.device) as ws:
+            hd.launch(hd.lib.imcui_hip_liftfeat_aft_probe, self._ca, _ptr(packed), _ptr(x), int(layer), B, N, _ptr(out), _ptr(kv), _ptr(ws), ws.numel())
+        return out, kv
+
+    def select_probe(self, heat: torch.Tensor, boosted: torch.Tensor, H: int, W: int, threshold: float, max_keypoints: int, kcap: int | None = None):
+        """The selection on heat [B,Hp,Wp] and boosted [B,Hp/8,Wp/8,64] for images of H x W -> the outputs of `forward`."""
+        hd = get_handle(heat.device)
+        heat, boosted = heat.contiguous().float(), boosted.contiguous().float()
+        B, Hp, Wp = heat.shape
+        if kcap is None:
+            bound = ((Hp + 2) // 3) * ((Wp + 2) // 3)
+            kcap = bound if max_keypoints <= 0 else max(1, min(max_keypoints, bound))
+        kpts, scores, desc, nk, status, out = _sparse_outputs(B, kcap, 64, heat.device)
+        with self._ws.use(hd.lib.imcui_hip_liftfeat_select_workspace_bytes(B, Hp, Wp), heat.device) as ws:
+            hd.launch(hd.lib.imcui_hip_liftfeat_select_probe, _ptr(heat), _ptr(boosted), B, int(H), int(W), Hp, Wp, float(threshold), int(max_keypoints), kcap,
+                      _ptr(kpts), _ptr(scores), _ptr(desc), _ptr(nk), _ptr(status), _ptr(ws), ws.numel())  # fmt: skip
+        return out
+
+
 # ------------------------------------------------------------------ ALIKED
 ALIKED_MODELS = ("aliked-n16", "aliked-n16rot")  # (c1,c2,c3,c4,dim,K,M) = (16,32,64,128,128,3,16): what csrc/aliked.hip is built for
 

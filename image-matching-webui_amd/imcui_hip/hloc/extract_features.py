@@ -86,6 +86,12 @@ confs = {
         "preprocessing": {"grayscale": False, "force_resize": True, "resize_max": 1600, "width": 640, "height": 480, "conf_th": 0.001, "multiscale": False,
                           "scales": [1.0]},
     },
+    # imcui/hloc/configs/extractors.py:198-208: LiftFeat (the `liftfeat` plugin), RGB
+    "liftfeat": {
+        "output": "feats-liftfeat-n5000-r1600",
+        "model": {"name": "liftfeat", "max_keypoints": 5000},
+        "preprocessing": {"grayscale": False, "resize_max": 1600},
+    },
 }
 
 

@@ -1215,3 +1215,55 @@ def sfd2_synth_state(seed: int = 0, widths=(64, 128, 256), blocks: int = 3, grou
     sd["convPb.weight"] = wpb
     sd["convPb.bias"] = torch.full((16,), (lo + hi) / 2)
     return sd
+
+
+def liftfeat_synth_state(seed: int = 0, kenc: bool = True, ffn: int = 128, n_layers: int = 3, logit_gain: float = 0.7, dustbin_bias: float = 0.5,
+                         key_gain: float = 0.5) -> dict:
+    """Seeded LiftFeat weights under the key names of tests/liftfeat_reference.py's table: XFeat's trunk (`xfeat_state_dict` without
+    `heatmap_head.*` and `fine_matcher.*`, counters included), `normal_head.{0,1,2}.{conv,bn}.*` + `normal_head.3.*`, and
+    `feature_boost.{denc,nenc,kenc}.{0,2,4}.*`, `.layers.{i}.{attn.{q,k,v,proj},norm1,ffn.{0,2},norm2}.*`, `.final_proj.*`.  Linears are
+    drawn at 1 / sqrt(fan-in), BatchNorm and LayerNorm near the identity.  The key-point head takes XFeat's `logit_gain` / `dustbin_bias`
+    (0.7: peaks on both sides of the 0.05 threshold, 24 key-points on the 32x48 image of the tests); the AFT key projections carry `key_gain`, so that the soft-max over the tokens is spread
+    (tests/test_liftfeat_cpu.py asserts the key-point counts at 96x128 and 32x48 and that no soft-max column puts more than 0.9 of its
+    weight on one token)."""
+    sd = {k: v for k, v in xfeat_state_dict(seed, logit_gain=logit_gain, dustbin_bias=dustbin_bias).items()
+          if not k.startswith(("heatmap_head.", "fine_matcher."))}  # fmt: skip
+    g = torch.Generator().manual_seed(seed + 7919)
+
+    def rn(*shape, scale=1.0):
+        return torch.randn(*shape, generator=g) * scale
+
+    def linear(stem, cin, cout, gain=1.0):
+        sd[f"{stem}.weight"] = rn(cout, cin, scale=gain / math.sqrt(cin))
+        sd[f"{stem}.bias"] = rn(cout, scale=0.05)
+
+    for s, c in enumerate((64, 32, 16)):
+        sd[f"normal_head.{s}.conv.weight"] = rn(c // 2, c, 3, 3, scale=math.sqrt(2.0 / (c * 9)))
+        sd[f"normal_head.{s}.conv.bias"] = rn(c // 2, scale=0.1)
+        sd[f"normal_head.{s}.bn.weight"] = 1.0 + 0.1 * rn(c // 2)
+        sd[f"normal_head.{s}.bn.bias"] = 0.1 * rn(c // 2)
+        sd[f"normal_head.{s}.bn.running_mean"] = 0.1 * rn(c // 2)
+        sd[f"normal_head.{s}.bn.running_var"] = 0.75 + 0.5 * torch.rand(c // 2, generator=g)
+        sd[f"normal_head.{s}.bn.num_batches_tracked"] = torch.tensor(1000, dtype=torch.long)
+    sd["normal_head.3.weight"] = rn(3, 8, 1, 1, scale=1.0 / math.sqrt(8))
+    sd["normal_head.3.bias"] = rn(3, scale=0.1)
+    fb = "feature_boost"
+    encoders = {"denc": (64, 64, 64), "nenc": (192, 128, 64, 64)}
+    if kenc:
+        encoders["kenc"] = (65, 128, 64, 64)
+    for name, widths in encoders.items():
+        for i in range(len(widths) - 1):
+            linear(f"{fb}.{name}.{2 * i}", widths[i], widths[i + 1])
+    for i in range(n_layers):
+        p = f"{fb}.layers.{i}"
+        linear(f"{p}.attn.q", 64, 64)
+        linear(f"{p}.attn.k", 64, 64, gain=key_gain)
+        linear(f"{p}.attn.v", 64, 64)
+        linear(f"{p}.attn.proj", 64, 64)
+        linear(f"{p}.ffn.0", 64, ffn)
+        linear(f"{p}.ffn.2", ffn, 64)
+        for n in ("norm1", "norm2"):
+            sd[f"{p}.{n}.weight"] = 1.0 + 0.1 * rn(64)
+            sd[f"{p}.{n}.bias"] = 0.1 * rn(64)
+    linear(f"{fb}.final_proj", 64, 64)
+    return sd

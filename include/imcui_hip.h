@@ -698,6 +698,55 @@ int imcui_hip_xfeat_forward(imcui_hip_t* h, const float* packed, const float* im
 int imcui_hip_xfeat_sample_probe(imcui_hip_t* h, const float* kpt_heat, const float* reliability, const float* feats, int H, int W, const int* xy, int n,
                                  float* nearest, float* bilinear, float* bicubic, void* stream);
 
+/* ---- LiftFeat (zoo entry liftfeat(sparse) = `feature: liftfeat` + NN-mutual; imcui/hloc/extractors/liftfeat.py) ------------ */
+/* `models.liftfeat_wrapper.LiftFeat` (liftfeat.py:9, :27-31) is not part of the reference checkout (third_party is empty): the network is
+ * restated from its description (tests/liftfeat_reference.py) and parity with upstream's code is NOT pinned ("LiftFeat:
+ * what is pinned").  cfg [8] int32, read from the checkpoint's shapes and keys: {kenc present, FFN hidden width, denc hidden, nenc hidden
+ * 1, nenc hidden 2, kenc hidden 1, kenc hidden 2, AFT layers}; first hidden widths and the FFN: multiples of 32 up to 128, second hidden
+ * widths 32 or 64, 1 .. 8 layers; an unsupported cfg gives 0 / NULL / IMCUI_ERR_ARG.  Weight packing runs on the HOST (replaces the
+ * checkpoint load of liftfeat.py:27): tensor i is the state-dict entry named imcui_hip_liftfeat_tensor_name(cfg, i): XFeat's trunk
+ * without heatmap_head.*, normal_head.{0,1,2}.{conv,bn}.* and normal_head.3.*, feature_boost.*.  BatchNorm is folded in float32. */
+size_t imcui_hip_liftfeat_packed_floats(const int* cfg);
+int imcui_hip_liftfeat_num_tensors(const int* cfg);
+const char* imcui_hip_liftfeat_tensor_name(const int* cfg, int i);
+int imcui_hip_liftfeat_pack_weights(const int* cfg, const float* const* tensors, float* packed);
+/* Scratch of imcui_hip_liftfeat_forward for B images of H x W (independent of the threshold, max_keypoints and kcap). */
+size_t imcui_hip_liftfeat_workspace_bytes(int B, int H, int W);
+/* Bound on the key-points of an image whose scores do not tie exactly (5x5 NMS over the padded map); a plateau can exceed it. */
+int imcui_hip_liftfeat_max_keypoints_bound(int H, int W);
+/* liftfeat.py:34-53 `_forward`: `self.net.extract(image)` (:37) and the wrapper's cut (:42-46).
+ * image [dev, B,3,H,W] in [0,1] (the `* 255` of :35 and extract's `/ 255` are applied as two float32 roundings): zero-padded at the bottom
+ * and right to Hp x Wp = multiples of 32, channel mean, InstanceNorm over the padded image, XFeat's trunk, the normal head, the lifting
+ * network over all (Hp/8)(Wp/8) cells, then 5x5 NMS over the padded map (`==` max and > threshold), x < W and y < H, score = nearest
+ * sample of the heat map, bicubic descriptors of the boosted map.  Order (:42-46): count <= max_keypoints: row-major; otherwise ascending
+ * score (equal scores by row-major index: stable), the last max_keypoints entries (0: all; -k: all but the k lowest).
+ * Outputs, fixed stride `kcap` per image, first num_keypoints[b] entries valid, the rest zero:
+ *   keypoints [dev, B,kcap,2] (x, y);  scores [dev, B,kcap];  descriptors [dev, B,kcap,64] unit rows;  num_keypoints [dev, B] int32
+ *   status [dev, 1] int32 optional: 0 = fine, bit 1 = more key-points than kcap
+ *   kpt_heat [dev, B,Hp,Wp], normals [dev, B,Hp/8,Wp/8,192] (channel c * 64 + dy * 8 + dx), boosted [dev, B,Hp/8,Wp/8,64] optional
+ * Zero key-points is a valid result.  No host synchronisation. */
+int imcui_hip_liftfeat_forward(imcui_hip_t* h, const int* cfg, const float* packed, const float* image, int B, int C, int H, int W, float threshold,
+                               int max_keypoints, int kcap, float* keypoints, float* scores, float* descriptors, int* num_keypoints, int* status,
+                               float* kpt_heat, float* normals, float* boosted, void* ws, size_t ws_bytes, void* stream);
+/* Test entries (device pointers), each a stage of liftfeat.py:37 alone.  input_probe: image [B,3,H,W] -> gray [B,Hp,Wp], norm [B,2] =
+ * (invstd, -mean * invstd); ws: B * cdiv(Hp Wp, 4096) * 16 bytes.  upconv_probe: up-conv stage 0 / 1 / 2 on x [B,hh,ww,cin] (NHWC) -> out
+ * [B,2hh,2ww,cin/2], or with fused = 1 (stage 2, 2hh and 2ww multiples of 8) the unfolded unit normals [B,2hh/8,2ww/8,192].  booster_probe:
+ * d [B,N,64], k [B,N,65], n [B,N,192] -> out [B,N,64] (unit rows), x_enc optional [B,N,64] = the encoders' sum.  aft_probe: AFT layer
+ * `layer` on x [B,N,64] -> out, kv optional [B,64]; both with ws of imcui_hip_liftfeat_tokens_workspace_bytes.  select_probe: the selection
+ * on heat [B,Hp,Wp] and boosted [B,Hp/8,Wp/8,64] (Hp, Wp multiples of 8), outputs as imcui_hip_liftfeat_forward. */
+int imcui_hip_liftfeat_input_probe(imcui_hip_t* h, const float* image, int B, int H, int W, float* gray, float* norm, void* ws, size_t ws_bytes, void* stream);
+int imcui_hip_liftfeat_upconv_probe(imcui_hip_t* h, const int* cfg, const float* packed, const float* x, int stage, int fused, int B, int hh, int ww,
+                                    int align_corners, float slope, float* out, void* stream);
+size_t imcui_hip_liftfeat_tokens_workspace_bytes(int B, int N);
+int imcui_hip_liftfeat_booster_probe(imcui_hip_t* h, const int* cfg, const float* packed, const float* d, const float* k, const float* n, int B, int N,
+                                     float* out, float* x_enc, void* ws, size_t ws_bytes, void* stream);
+int imcui_hip_liftfeat_aft_probe(imcui_hip_t* h, const int* cfg, const float* packed, const float* x, int layer, int B, int N, float* out, float* kv, void* ws,
+                                 size_t ws_bytes, void* stream);
+size_t imcui_hip_liftfeat_select_workspace_bytes(int B, int Hp, int Wp);
+int imcui_hip_liftfeat_select_probe(imcui_hip_t* h, const float* heat, const float* boosted, int B, int H, int W, int Hp, int Wp, float threshold,
+                                    int max_keypoints, int kcap, float* keypoints, float* scores, float* descriptors, int* num_keypoints, int* status, void* ws,
+                                    size_t ws_bytes, void* stream);
+
 /* ---- LightGlue --------------------------------------------- */
 /* Host-side packing of the upstream state dict (9 layers, dim 256, 4 heads).  `tensors` holds the
  * host pointers of imcui_hip_lightglue_num_tensors() tensors; tensor i is the upstream state-dict
