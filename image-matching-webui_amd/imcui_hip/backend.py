@@ -3336,6 +3336,149 @@ def conv_gemm_f32(x_nhwc, w_oihw, bias, resid=None, stride=1, act=0):
     return out
 
 
+# ------------------------------------------------------------------ LISRD
+LISRD_DESC, LISRD_META, LISRD_CLUSTERS, LISRD_TILE, LISRD_HIDDEN = 128, 128, 8, 3, 256
+LISRD_DM = LISRD_CLUSTERS * LISRD_META
+LISRD_MIN_SIDE = 8 * LISRD_TILE
+LISRD_KINDS = ("stem", "conv3x3", "heads", "conv1x1")
+
+
+def lisrd_layers() -> list[dict]:
+    """The launch list as the library's ONE table states it (csrc/lisrd.hip, LISRD_LAYERS)."""
+    lib = load_library()
+    out = []
+    for i in range(lib.imcui_hip_lisrd_num_layers()):
+        v = (C.c_int * 5)()
+        name = lib.imcui_hip_lisrd_layer(i, v).decode()
+        out.append({"name": name, "kind": LISRD_KINDS[v[0]], "cin": v[1], "cout": v[2], "pool": v[3], "in_off": v[4]})
+    return out
+
+
+def lisrd_tensor_names() -> list[str]:
+    lib = load_library()
+    return [lib.imcui_hip_lisrd_tensor_name(i).decode() for i in range(lib.imcui_hip_lisrd_num_tensors())]
+
+
+def lisrd_tensor_shapes() -> dict:
+    """Shape of every tensor the packer takes, as the library states it (imcui_hip_lisrd_tensor_shape)."""
+    lib = load_library()
+    shapes = {}
+    for i, name in enumerate(lisrd_tensor_names()):
+        d = (C.c_int * 4)()
+        shapes[name] = tuple(d[: lib.imcui_hip_lisrd_tensor_shape(i, d)])
+    return shapes
+
+
+def lisrd_variances() -> tuple:
+    """The four variances in the order the wrapper's dictionaries iterate in, as the library states them."""
+    lib = load_library()
+    return tuple(lib.imcui_hip_lisrd_variance(v).decode() for v in range(4))
+
+
+def pack_lisrd(state_dict: dict) -> torch.Tensor:
+    """LISRD state dict (the keys of tests/lisrd_reference.py, which restate upstream's attribute names) -> packed float32 buffer (host).
+    The BatchNorms (eval) become the affine y = x a + b behind the ReLU.  Strict: `num_batches_tracked` counters are ignored, every other
+    key is consumed exactly once and every shape checked, so a checkpoint of another configuration than LISRD_CONFIG is refused by name."""
+    lib = load_library()
+    sd = {k: t for k, t in state_dict.items() if not k.endswith("num_batches_tracked")}
+    return _pack_named("LISRD", "the LISRD_CONFIG", lisrd_tensor_names(), lisrd_tensor_shapes(), sd, lib.imcui_hip_lisrd_packed_floats(), lib.imcui_hip_lisrd_pack_weights)
+
+
+def lisrd_check_args(image_shape) -> None:
+    """Refusals raised before anything is launched."""
+    if len(image_shape) != 4 or image_shape[1] != 3:
+        raise ValueError(f"LISRD expects a 3-channel image [B,3,H,W], got shape {tuple(image_shape)}")
+    if image_shape[2] < LISRD_MIN_SIDE or image_shape[3] < LISRD_MIN_SIDE:
+        raise ValueError(f"LISRD needs images of at least {LISRD_MIN_SIDE} x {LISRD_MIN_SIDE} (a region of the 1/8-resolution map without cells), got {tuple(image_shape[2:])}")
+
+
+class LisrdHIP:
+    def __init__(self):
+        self._ws = _Workspace()
+
+    def describe(self, packed: torch.Tensor, image: torch.Tensor, keypoints: torch.Tensor, counts: torch.Tensor) -> dict:
+        """image [B,3,H,W] in [0,1] on the GPU, keypoints [B,K,2] (x, y) in pixels, counts [B] int32 -> desc [B,K,4,128], meta [B,K,4,1024]
+        (unit vectors, rows past the count zero), status [1] int32.  Never synchronises."""
+        lisrd_check_args(tuple(image.shape))
+        hd = get_handle(image.device)
+        _same_device(packed, image)
+        image, keypoints = image.contiguous().float(), keypoints.contiguous().float()
+        counts = counts.to(image.device, torch.int32).contiguous()
+        B, Cc, H, W = image.shape
+        K = keypoints.shape[1]
+        if tuple(keypoints.shape) != (B, K, 2) or counts.numel() != B or K < 1:
+            raise ImcuiHipError(f"LISRD: keypoints {tuple(keypoints.shape)} / counts {tuple(counts.shape)} do not belong to {B} images")
+        dev = image.device
+        out = {"desc": torch.empty((B, K, 4, LISRD_DESC), dtype=torch.float32, device=dev), "meta": torch.empty((B, K, 4, LISRD_DM), dtype=torch.float32, device=dev),
+               "status": torch.empty((1,), dtype=torch.int32, device=dev)}  # fmt: skip
+        with self._ws.use(hd.lib.imcui_hip_lisrd_describe_workspace_bytes(B, H, W), dev) as ws:
+            hd.launch(hd.lib.imcui_hip_lisrd_describe, _ptr(packed), _ptr(image), B, Cc, H, W, _ptr(keypoints), _ptr(counts), K, _ptr(out["desc"]), _ptr(out["meta"]),
+                      _ptr(out["status"]), _ptr(ws), ws.numel())  # fmt: skip
+        return out
+
+    def dense(self, packed: torch.Tensor, image: torch.Tensor) -> dict:
+        """Test entry: descriptors [4][B,Hc,Wc,128] and raw meta maps [4][B,Hc,Wc,128] (NHWC, un-normalised), meta_descriptors [B,4,3,3,1024]."""
+        lisrd_check_args(tuple(image.shape))
+        hd = get_handle(image.device)
+        image = image.contiguous().float()
+        B, Cc, H, W = image.shape
+        dense = torch.empty((8, B, H // 8, W // 8, 128), dtype=torch.float32, device=image.device)
+        vlad = torch.empty((B, 4, LISRD_TILE, LISRD_TILE, LISRD_DM), dtype=torch.float32, device=image.device)
+        with self._ws.use(hd.lib.imcui_hip_lisrd_describe_workspace_bytes(B, H, W), image.device) as ws:
+            hd.launch(hd.lib.imcui_hip_lisrd_dense, _ptr(packed), _ptr(image), B, Cc, H, W, _ptr(dense), _ptr(vlad), _ptr(ws), ws.numel())
+        return {"descriptors": dense[:4], "meta_maps": dense[4:], "meta_descriptors": vlad}
+
+    def layers_probe(self, packed: torch.Tensor, x: torch.Tensor, first: int, last: int) -> torch.Tensor:
+        """Test entry: entries [first, last] of `lisrd_layers` through the forward's own launch list on x: the planar image [B,3,H,W] when
+        first == 0, else an NHWC map -> the last entry's NHWC map."""
+        hd = get_handle(x.device)
+        x = x.contiguous().float()
+        B, H, W = (x.shape[0], x.shape[2], x.shape[3]) if first == 0 else tuple(x.shape[:3])
+        hh, ww = H, W
+        layers = lisrd_layers()
+        for L in layers[first : last + 1]:
+            if L["pool"]:
+                hh, ww = hh // 2, ww // 2
+        out = torch.empty((B, hh, ww, layers[last]["cout"]), dtype=torch.float32, device=x.device)
+        with self._ws.use(max(256, hd.lib.imcui_hip_lisrd_layers_workspace_bytes(first, last, B, H, W)), x.device) as ws:
+            hd.launch(hd.lib.imcui_hip_lisrd_layers_probe, _ptr(packed), _ptr(x), first, last, B, H, W, _ptr(out), _ptr(ws), ws.numel())
+        return out
+
+    @staticmethod
+    def affine_probe(x: torch.Tensor, a: torch.Tensor, b: torch.Tensor, pool: bool) -> torch.Tensor:
+        """Test entry: y = x a + b on x [B,H,W,C] (NHWC), through AvgPool2d(2, 2) when `pool`."""
+        hd = get_handle(x.device)
+        x, a, b = x.contiguous().float(), a.contiguous().float(), b.contiguous().float()
+        B, H, W, Cc = x.shape
+        out = torch.empty((B, H // 2, W // 2, Cc) if pool else (B, H, W, Cc), dtype=torch.float32, device=x.device)
+        hd.launch(hd.lib.imcui_hip_lisrd_affine_probe, _ptr(x), _ptr(a), _ptr(b), B, H, W, Cc, int(bool(pool)), _ptr(out))
+        return out
+
+    def vlad_probe(self, packed: torch.Tensor, v: int, fmap: torch.Tensor) -> torch.Tensor:
+        """Test entry: regional NetVLAD with variance v's weights on fmap [B,hc,wc,128] -> [B,3,3,1024]."""
+        hd = get_handle(fmap.device)
+        fmap = fmap.contiguous().float()
+        B, hc, wc, _ = fmap.shape
+        out = torch.empty((B, LISRD_TILE, LISRD_TILE, LISRD_DM), dtype=torch.float32, device=fmap.device)
+        with self._ws.use(max(256, hd.lib.imcui_hip_lisrd_vlad_workspace_bytes(B, hc, wc)), fmap.device) as ws:
+            hd.launch(hd.lib.imcui_hip_lisrd_vlad_probe, _ptr(packed), int(v), _ptr(fmap), B, hc, wc, _ptr(out), _ptr(ws), ws.numel())
+        return out
+
+    @staticmethod
+    def sample_probe(dmaps: torch.Tensor, vlad: torch.Tensor, image_size: tuple, keypoints: torch.Tensor, counts: torch.Tensor) -> dict:
+        """Test entry: the sparse sampling of dmaps [4,B,hc,wc,128] and vlad [B,4,3,3,1024] at keypoints [B,K,2] (x, y) of H x W images."""
+        hd = get_handle(dmaps.device)
+        dmaps, vlad, keypoints = dmaps.contiguous().float(), vlad.contiguous().float(), keypoints.contiguous().float()
+        counts = counts.to(dmaps.device, torch.int32).contiguous()
+        _, B, hc, wc, _ = dmaps.shape
+        K = keypoints.shape[1]
+        out = {"desc": torch.empty((B, K, 4, LISRD_DESC), dtype=torch.float32, device=dmaps.device),
+               "meta": torch.empty((B, K, 4, LISRD_DM), dtype=torch.float32, device=dmaps.device)}  # fmt: skip
+        hd.launch(hd.lib.imcui_hip_lisrd_sample_probe, _ptr(dmaps), _ptr(vlad), B, hc, wc, int(image_size[0]), int(image_size[1]), _ptr(keypoints), _ptr(counts), K,
+                  _ptr(out["desc"]), _ptr(out["meta"]))  # fmt: skip
+        return out
+
+
 # ------------------------------------------------------------------ mutual NN
 _nn_ws = _Workspace()
 
@@ -3377,6 +3520,39 @@ def mutual_nn_dn(desc0_dn: torch.Tensor, desc1_dm: torch.Tensor, ratio_threshold
         hd.launch(lib.imcui_hip_mutual_nn_dn, _ptr(desc0_dn), _ptr(desc1_dm), B, N, M, D, float(ratio_threshold or 0.0), float(distance_threshold or 0.0),
                   int(bool(do_mutual_check)), _ptr(m0), _ptr(s0), _ptr(ws), ws.numel())  # fmt: skip
     return m0, s0
+
+
+def lisrd_match(desc0: torch.Tensor, meta0: torch.Tensor, desc1: torch.Tensor, meta1: torch.Tensor, cnt0: torch.Tensor | None = None,
+                cnt1: torch.Tensor | None = None, want_nn: bool = False) -> dict:
+    """LISRD's meta-weighted mutual nearest neighbours and the confidence of the matched pairs (imcui_hip_lisrd_match): desc0 [B,N,4,128],
+    meta0 [B,N,4,Dm], desc1 [B,M,4,128], meta1 [B,M,4,Dm]; cnt0 / cnt1 [B] int32 on the device = live key-points per image (None: all).
+    Returns matches0 [B,N] int32 (-1 = none), best0 [B,N] (row-best similarity), mconf [B,N] (0 where unmatched) and, with want_nn, the
+    row / column arg-maxima nn12 [B,N] / nn21 [B,M] and the column-best similarity best1 [B,M].  Never synchronises."""
+    dev = desc0.device
+    hd = get_handle(dev)
+    lib = hd.lib
+    desc0, meta0, desc1, meta1 = (t.contiguous().float() for t in (desc0, meta0, desc1, meta1))
+    if desc0.dim() != 4 or meta0.dim() != 4 or desc1.dim() != 4 or meta1.dim() != 4:
+        raise ImcuiHipError("lisrd_match: descriptors are [B,K,4,128] and meta descriptors [B,K,4,Dm]")
+    B, N, V, D = desc0.shape
+    M, Dm = desc1.shape[1], meta0.shape[3]
+    if (V, D) != (4, 128) or tuple(desc1.shape) != (B, M, 4, 128) or tuple(meta0.shape) != (B, N, 4, Dm) or tuple(meta1.shape) != (B, M, 4, Dm):
+        raise ImcuiHipError(f"lisrd_match: shapes {tuple(desc0.shape)}, {tuple(meta0.shape)}, {tuple(desc1.shape)}, {tuple(meta1.shape)} do not belong together")
+    if min(B, N, M) < 1 or Dm % 128 or not 128 <= Dm <= 1024:
+        raise ImcuiHipError(f"lisrd_match: B={B}, N={N}, M={M} must be positive and the meta width {Dm} a multiple of 128 up to 1024")
+    for c in (cnt0, cnt1):
+        if c is not None and (c.dtype != torch.int32 or c.device != dev or c.numel() != B or not c.is_contiguous()):
+            raise ImcuiHipError("lisrd_match: counts are contiguous int32 [B] tensors on the descriptors' device")
+    out = {"matches0": torch.empty((B, N), dtype=torch.int32, device=dev), "best0": torch.empty((B, N), dtype=torch.float32, device=dev),
+           "mconf": torch.empty((B, N), dtype=torch.float32, device=dev)}  # fmt: skip
+    if want_nn:
+        out["nn12"] = torch.empty((B, N), dtype=torch.int32, device=dev)
+        out["nn21"] = torch.empty((B, M), dtype=torch.int32, device=dev)
+        out["best1"] = torch.empty((B, M), dtype=torch.float32, device=dev)
+    with _nn_ws.use(lib.imcui_hip_lisrd_match_workspace_bytes(B, N, M, Dm), dev) as ws:
+        hd.launch(lib.imcui_hip_lisrd_match, _ptr(desc0), _ptr(meta0), _ptr(cnt0), _ptr(desc1), _ptr(meta1), _ptr(cnt1), B, N, M, Dm, _ptr(out["matches0"]),
+                  _ptr(out["best0"]), _ptr(out["mconf"]), _ptr(out.get("nn12")), _ptr(out.get("nn21")), _ptr(out.get("best1")), _ptr(ws), ws.numel())  # fmt: skip
+    return out
 
 
 def nn_argmax(queries: torch.Tensor, db: torch.Tensor, return_best: bool = False, split: bool = False):

@@ -31,7 +31,7 @@ def unwrap_checkpoint(obj):
     for _ in range(2):  # a container in a container is the deepest the upstream projects go
         if not isinstance(obj, dict):
             break
-        inner = next((obj[k] for k in ("state_dict", "model") if isinstance(obj.get(k), dict)), None)
+        inner = next((obj[k] for k in ("state_dict", "model", "model_state_dict") if isinstance(obj.get(k), dict)), None)  # (the last: LISRD's checkpoints)
         if inner is None or any(torch.is_tensor(v) for v in obj.values()):
             break  # tensors at this level: this IS the state dict (a parameter may be called "model...." but is not a dict)
         obj = inner

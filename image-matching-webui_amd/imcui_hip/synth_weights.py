@@ -1267,3 +1267,56 @@ def liftfeat_synth_state(seed: int = 0, kenc: bool = True, ffn: int = 128, n_lay
             sd[f"{p}.{n}.bias"] = 0.1 * rn(64)
     linear(f"{fb}.final_proj", 64, 64)
     return sd
+
+
+LISRD_BACKBONE = (("1_1", 3, 64, False), ("1_2", 64, 64, True), ("2_1", 64, 64, False), ("2_2", 64, 64, True), ("3_1", 64, 128, False), ("3_2", 128, 128, True),
+                  ("4_1", 128, 256, False), ("4_2", 256, 256, False))  # fmt: skip
+
+
+def lisrd_synth_state(seed: int = 0) -> dict:
+    """Seeded LISRD weights (LISRD_CONFIG of the wrapper: desc_size 128, tile 3, n_clusters 8, meta_desc_dim 128) under the recalled key
+    names: `_backbone._conv{a}_{b}.*` / `_backbone._bn{a}_{b}.*`, per variance `conv_{v}_1` / `bn_{v}_1` / `conv_{v}_2` (descriptor head),
+    `conv_meta_{v}_1` / `bn_meta_{v}_1` / `conv_meta_{v}_2` (meta head), `vlad_{v}.conv.weight` [8,128,1,1] and `vlad_{v}.centroids` [8,128].
+    Convolutions are He-initialised.  Every block is conv -> ReLU -> BatchNorm, so a plain draw of the statistics would let the scale of
+    the activations drift from layer to layer: each BatchNorm is calibrated on a seeded 64 x 64 uniform image (drawn from the same
+    generator, evaluated here with torch's own operations) -- running_mean / running_var are the measured per-channel statistics of the
+    ReLU output times a factor drawn in 0.8 .. 1.25, weight 1 +- 0.1, bias 0.1 N(0, 1) -- so every layer's output has about zero mean and
+    unit variance and no channel dies.  NetVLAD's assignment layer is drawn N(0, 1) / sqrt(128) and scaled so that its logits have a
+    standard deviation of 2 on the calibration image's unit vectors: the median top assignment lies near 0.6, well away from 1 / 8
+    (tests/test_lisrd_cpu.py asserts 0.3 .. 0.9)."""
+    import torch.nn.functional as F
+
+    from .backend import lisrd_variances  # (the library's own statement of the four names and their order)
+
+    g = torch.Generator().manual_seed(seed)
+    sd = {}
+
+    def rn(*shape, scale=1.0):
+        return torch.randn(*shape, generator=g) * scale
+
+    def block(x, conv, bn, cin, cout):
+        sd[f"{conv}.weight"] = rn(cout, cin, 3, 3, scale=math.sqrt(2.0) / math.sqrt(cin * 9))
+        sd[f"{conv}.bias"] = 0.1 * rn(cout)
+        y = F.relu(F.conv2d(x, sd[f"{conv}.weight"], sd[f"{conv}.bias"], padding=1))
+        sd[f"{bn}.weight"] = 1.0 + 0.1 * rn(cout)
+        sd[f"{bn}.bias"] = 0.1 * rn(cout)
+        sd[f"{bn}.running_mean"] = y.mean((0, 2, 3)) + 0.05 * rn(cout)
+        sd[f"{bn}.running_var"] = (y.var((0, 2, 3)) + 1e-3) * (0.8 + 0.45 * torch.rand(cout, generator=g))
+        sd[f"{bn}.num_batches_tracked"] = torch.tensor(1000, dtype=torch.long)
+        return F.batch_norm(y, sd[f"{bn}.running_mean"], sd[f"{bn}.running_var"], sd[f"{bn}.weight"], sd[f"{bn}.bias"], False, 0.0, 1e-5)
+
+    x = torch.rand(1, 3, 64, 64, generator=g)
+    for tag, cin, cout, pool in LISRD_BACKBONE:
+        x = block(x, f"_backbone._conv{tag}", f"_backbone._bn{tag}", cin, cout)
+        if pool:
+            x = F.avg_pool2d(x, 2, 2)
+    for v in lisrd_variances():
+        for pre in ("", "_meta"):
+            hid = block(x, f"conv{pre}_{v}_1", f"bn{pre}_{v}_1", 256, 256)
+            sd[f"conv{pre}_{v}_2.weight"] = rn(128, 256, 1, 1, scale=1.0 / math.sqrt(256))
+            sd[f"conv{pre}_{v}_2.bias"] = 0.1 * rn(128)
+        meta = F.normalize(F.conv2d(hid, sd[f"conv_meta_{v}_2.weight"], sd[f"conv_meta_{v}_2.bias"]), dim=1)
+        w = rn(8, 128, 1, 1, scale=1.0 / math.sqrt(128))
+        sd[f"vlad_{v}.conv.weight"] = w * (2.0 / F.conv2d(meta, w).std())
+        sd[f"vlad_{v}.centroids"] = rn(8, 128, scale=1.0 / math.sqrt(128))
+    return sd

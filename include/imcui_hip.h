@@ -1092,6 +1092,61 @@ int imcui_hip_simred_debug(imcui_hip_t* h, int mode, const float* A, const float
                            int nchunk, float* r0, float* r1, int* ri, float* c0, float* c1, int* ci, const float* rmax, const float* rsum, const float* cmax,
                            const float* csum, const float* l0, const float* l1, const unsigned char* flags, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- LISRD's matcher (zoo entries LISRD+SuperPoint / +ALIKED / +SIFT; imcui/hloc/matchers/lisrd.py) -- csrc/lisrd.hip ----
+ * imcui_hip_lisrd_match replaces `_lisrd_matcher` (lisrd.py:122-134) and `_compute_confidence` (lisrd.py:137-149) as `_forward` calls
+ * them (lisrd.py:279-290) on the sampled sets of `_extract_descriptors` (lisrd.py:90-119): desc0 [dev, B,N,4,128], meta0 [dev, B,N,4,Dm],
+ * desc1 [dev, B,M,4,128], meta1 [dev, B,M,4,Dm], one row per key-point and variance, Dm a multiple of 128 up to 1024; cnt0 / cnt1
+ * [dev, B] int32 live key-points per image or NULL (all N / M).  The similarity sum_v softmax_v(<meta0, meta1>) * <desc0, desc1> is
+ * reduced tile by tile on the matrix cores; neither [N,4,M] tensor nor the N x M matrix exists.  Among equal similarities the FIRST
+ * index wins (`torch.max` leaves it open).  Outputs: matches0 [dev, B,N] int32 = nn12[i] where nn21[nn12[i]] == i, else -1 (rows past
+ * cnt0: -1); best0 [dev, B,N] or NULL = the row-best similarity (0 for rows without a partner); mconf [dev, B,N] or NULL = the
+ * confidence of the matched pair (0 where unmatched); nn12 [dev, B,N] / nn21 [dev, B,M] or NULL = the row / column arg-maxima (-1
+ * past the counts) and best1 [dev, B,M] or NULL = the column-best similarity, for tests.  No host synchronisation; capturable. */
+size_t imcui_hip_lisrd_match_workspace_bytes(int B, int N, int M, int Dm);
+int imcui_hip_lisrd_match(imcui_hip_t* h, const float* desc0, const float* meta0, const int* cnt0, const float* desc1, const float* meta1, const int* cnt1, int B,
+                          int N, int M, int Dm, int* matches0, float* best0, float* mconf, int* nn12, int* nn21, float* best1, void* ws, size_t ws_bytes, void* stream);
+/* The network.  `lisrd.models` (lisrd.py:25-29) is not part of the reference checkout (third_party is empty): it is restated from its
+ * description (tests/lisrd_reference.py) and parity with upstream's code is NOT pinned ("LISRD: what is pinned").  One
+ * configuration is built: LISRD_CONFIG of lisrd.py:33-42 (desc_size 128, tile 3, n_clusters 8, meta_desc_dim 128, compute_meta_desc).
+ * Host-side packing (replaces `self.net.load(weight_file, Mode.EXPORT)`, lisrd.py:187-189): tensor i is the state-dict entry named
+ * imcui_hip_lisrd_tensor_name(i); imcui_hip_lisrd_tensor_shape(i, out4) returns its number of dimensions and writes them.  imcui_hip_lisrd_variance(v):
+ * the name of variance v < 4, in the order the wrapper's dictionaries iterate in.  imcui_hip_lisrd_layer: entry i of the ONE launch table
+ * (csrc/lisrd.hip, LISRD_LAYERS): its name, out5 = kind (0 first layer on the VALU, 1 3x3 on the implicit GEMM, 2 the eight hidden head
+ * layers as one launch, 3 a head's 1x1 layer), cin, cout, pool (AvgPool2d(2, 2) behind the block), first channel it reads of its input. */
+int imcui_hip_lisrd_num_layers(void);
+const char* imcui_hip_lisrd_layer(int i, int* out5);
+int imcui_hip_lisrd_num_tensors(void);
+const char* imcui_hip_lisrd_tensor_name(int i);
+int imcui_hip_lisrd_tensor_shape(int i, int* out4);
+const char* imcui_hip_lisrd_variance(int v);
+size_t imcui_hip_lisrd_packed_floats(void);
+int imcui_hip_lisrd_pack_weights(const float* const* tensors, float* packed);
+/* imcui_hip_lisrd_describe replaces, per image batch, `img * 255.0` (lisrd.py:209-210), `self.net._forward(...)` (lisrd.py:260-268), the
+ * (x, y) -> (row, col) flip (lisrd.py:256-257) and `_extract_descriptors` with `_keypoints_to_grid` (lisrd.py:77-119, called at
+ * lisrd.py:271-276): image [dev, B,3,H,W] in [0, 1] (H, W >= 24; all images of a call have one size), keypoints [dev, B,K,2] (x, y) in
+ * pixels, counts [dev, B] int32 -> desc [dev, B,K,4,128], meta [dev, B,K,4,1024], every vector v / max(|v|, 1e-12), rows past the count
+ * zero; status [dev, 1] int32 or NULL (always 0).  The dense maps stay in the workspace. */
+size_t imcui_hip_lisrd_describe_workspace_bytes(int B, int H, int W);
+int imcui_hip_lisrd_describe(imcui_hip_t* h, const float* packed, const float* image, int B, int C, int H, int W, const float* keypoints, const int* counts, int K,
+                             float* desc, float* meta, int* status, void* ws, size_t ws_bytes, void* stream);
+/* Test entries (device pointers).  dense: the eight dense maps [8][B,H/8,W/8,128] (descriptor maps of the four variances, then the raw
+ * meta maps) and the meta maps [B,4,3,3,1024] (either may be NULL); ws of imcui_hip_lisrd_describe_workspace_bytes.  layers_probe: entries
+ * [first, last] of the launch table through the forward's own launch list (entries 8 .. 16 one at a time; entries >= 9 read the
+ * 2048-channel hidden map).  affine_probe: the BatchNorm pass behind the ReLU alone, y = x a + b on x [B,H,W,C] (pool = 1: through the 2x2
+ * average pool, out [B,H/2,W/2,C]).  vlad_probe: regional NetVLAD with the weights of variance v on map [B,hc,wc,128] -> [B,3,3,1024].
+ * sample_probe: the sparse sampling on given maps dmaps [4][B,hc,wc,128] and vlad [B,4,3,3,1024]. */
+int imcui_hip_lisrd_dense(imcui_hip_t* h, const float* packed, const float* image, int B, int C, int H, int W, float* dense, float* vlad, void* ws, size_t ws_bytes,
+                          void* stream);
+size_t imcui_hip_lisrd_layers_workspace_bytes(int first, int last, int B, int H, int W);
+int imcui_hip_lisrd_layers_probe(imcui_hip_t* h, const float* packed, const float* in, int first, int last, int B, int H, int W, float* out, void* ws,
+                                 size_t ws_bytes, void* stream);
+int imcui_hip_lisrd_affine_probe(imcui_hip_t* h, const float* x, const float* a, const float* b, int B, int H, int W, int C, int pool, float* out, void* stream);
+size_t imcui_hip_lisrd_vlad_workspace_bytes(int B, int hc, int wc);
+int imcui_hip_lisrd_vlad_probe(imcui_hip_t* h, const float* packed, int v, const float* map, int B, int hc, int wc, float* out, void* ws, size_t ws_bytes,
+                               void* stream);
+int imcui_hip_lisrd_sample_probe(imcui_hip_t* h, const float* dmaps, const float* vlad, int B, int hc, int wc, int H, int W, const float* keypoints,
+                                 const int* counts, int K, float* desc, float* meta, void* stream);
+
 /* ---- dual-softmax matcher (imcui/hloc/matchers/dual_softmax.py; zoo entries disk+dualsoftmax, superpoint+dualsoftmax) */
 size_t imcui_hip_dual_softmax_workspace_bytes(int B, int C, int N, int M);
 /* desc0 [dev, B,C,N], desc1 [dev, B,C,M] channels-first as the plugin receives them (any C >= 1); the matcher
