@@ -2794,6 +2794,110 @@ class SuperGlueHIP:
         }  # fmt: skip
 
 
+# ------------------------------------------------------------------ IMP
+def imp_tensor_table() -> list[tuple[str, tuple]]:
+    """(state-dict name, shape) of every tensor of `imp_gml.920.pth`, from the one table in csrc/imp.hip."""
+    lib = load_library()
+    dims = (C.c_int * 3)()
+    out = []
+    for i in range(lib.imcui_hip_imp_num_tensors()):
+        nd = lib.imcui_hip_imp_tensor_shape(i, dims)
+        out.append((lib.imcui_hip_imp_tensor_name(i).decode(), tuple(dims[:nd])))
+    return out
+
+
+def pack_imp(state_dict: dict, conf: dict | None = None) -> torch.Tensor:
+    """pram.nets.gml.GML state dict -> packed float32 buffer (host).  Strict, like the reference's `load_state_dict(..., strict=True)`
+    (imcui/hloc/matchers/imp.py:41-44): a missing name, a shape that differs or an extra key is refused with a message that names it."""
+    conf = conf or {}
+    name = str(conf.get("model_name", ""))
+    if "adagml" in name.lower() or any(k.startswith(("pooling", "pool.", "ada")) for k in state_dict):
+        raise ImcuiHipError(f"IMP: the adaptive-pooling model (AdaGML, '{name or 'imp_adagml*'}') is not built; only GML (imp_gml*) runs here")
+    if conf.get("with_sinkhorn", True) is False:
+        raise ImcuiHipError("IMP: with_sinkhorn=False (the dual-softmax score) is not built; only the Sinkhorn assignment runs here")
+    if int(conf.get("n_layers", 9)) != 9:
+        raise ImcuiHipError(f"IMP: n_layers={conf['n_layers']} is not built; only the 9 x ['self', 'cross'] network runs here")
+    lib = load_library()
+    table = imp_tensor_table()
+    w = state_dict.get("input_proj.weight")
+    if w is not None and tuple(w.shape)[:2] != (256, 128):
+        raise ImcuiHipError(f"IMP: input_proj takes {tuple(w.shape)[1]}-wide descriptors; only the 128-wide (sfd2) model runs here")
+    bn = {n[: -len("running_var")] + "num_batches_tracked" for n, _ in table if n.endswith(".running_var")}  # BatchNorm's counter, not a weight
+    extra = sorted(set(state_dict) - {n for n, _ in table} - bn)
+    if extra:
+        raise ImcuiHipError(f"IMP: the state dict has {len(extra)} keys the network does not: {', '.join(extra[:8])}{' ...' if len(extra) > 8 else ''}")
+    arrs = []
+    for n, shp in table:
+        if n not in state_dict:
+            raise ImcuiHipError(f"IMP state dict lacks '{n}'")
+        if tuple(state_dict[n].shape) != shp:
+            raise ImcuiHipError(f"IMP: '{n}' has shape {tuple(state_dict[n].shape)}, the network needs {shp}")
+        arrs.append(_as_f32_host(state_dict[n]).reshape(-1) if not shp else _as_f32_host(state_dict[n]))
+    packed = np.zeros(lib.imcui_hip_imp_packed_floats(), dtype=np.float32)
+    tp = (C.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
+    rc = lib.imcui_hip_imp_pack_weights(tp, packed.ctypes.data)
+    if rc != 0:
+        raise ImcuiHipError(f"imcui_hip_imp_pack_weights failed ({rc})")
+    return torch.from_numpy(packed)
+
+
+class IMPHIP:
+    def __init__(self):
+        self._ws = _Workspace()
+
+    def forward(self, packed, kpts0, kpts1, scores0, scores1, desc0, desc1, n0, n1, size0, size1, sinkhorn_iterations,
+                match_threshold):  # fmt: skip
+        """kptsX [B,ncap,2], scoresX [B,ncap], descX [B,ncap,128] (row per point), nX [B] int32 on the GPU; sizeX = (W, H)."""
+        dev = kpts0.device
+        hd = get_handle(dev)
+        lib = hd.lib
+        B, ncap0 = kpts0.shape[0], kpts0.shape[1]
+        ncap1 = kpts1.shape[1]
+        ncap = max(ncap0, ncap1, 1)
+        kpts0, kpts1, desc0, desc1, scores0, scores1 = (_pad_rows(t, ncap, dev) for t in (kpts0, kpts1, desc0, desc1, scores0, scores1))
+        n0 = n0.to(device=dev, dtype=torch.int32).contiguous()
+        n1 = n1.to(device=dev, dtype=torch.int32).contiguous()
+        m0 = torch.empty((B, ncap), dtype=torch.int32, device=dev)
+        m1 = torch.empty((B, ncap), dtype=torch.int32, device=dev)
+        s0 = torch.empty((B, ncap), dtype=torch.float32, device=dev)
+        s1 = torch.empty((B, ncap), dtype=torch.float32, device=dev)
+        with self._ws.use(lib.imcui_hip_imp_workspace_bytes(B, ncap), dev) as ws:
+            hd.launch(
+                lib.imcui_hip_imp_forward, _ptr(packed), B, ncap, _ptr(kpts0), _ptr(kpts1), _ptr(scores0), _ptr(scores1), _ptr(desc0), _ptr(desc1),
+                _ptr(n0), _ptr(n1), float(size0[0]), float(size0[1]), float(size1[0]), float(size1[1]),
+                int(sinkhorn_iterations), float(match_threshold),
+                _ptr(m0), _ptr(m1), _ptr(s0), _ptr(s1), _ptr(ws), ws.numel(),
+            )  # fmt: skip
+        return {
+            "matches0": m0[:, :ncap0], "matches1": m1[:, :ncap1], "matching_scores0": s0[:, :ncap0],
+            "matching_scores1": s1[:, :ncap1],
+        }  # fmt: skip
+
+    def ot_probe(self, scores, n0, n1, bin_score, iterations, p=0.2) -> dict:
+        """The assignment stage alone (imcui_hip_imp_ot_probe): scores [B,ncap,ncap] float32 on the GPU, n0 / n1 [B] int32.
+        u / v [B,ncap+1]: entry n0[b] / n1[b] is the dust-bin's."""
+        dev = scores.device
+        hd = get_handle(dev)
+        lib = hd.lib
+        B, ncap = scores.shape[0], scores.shape[1]
+        assert scores.shape[2] == ncap and scores.dtype == torch.float32
+        scores = scores.contiguous()
+        n0 = n0.to(device=dev, dtype=torch.int32).contiguous()
+        n1 = n1.to(device=dev, dtype=torch.int32).contiguous()
+        m0 = torch.empty((B, ncap), dtype=torch.int32, device=dev)
+        m1 = torch.empty((B, ncap), dtype=torch.int32, device=dev)
+        s0 = torch.empty((B, ncap), dtype=torch.float32, device=dev)
+        s1 = torch.empty((B, ncap), dtype=torch.float32, device=dev)
+        u = torch.empty((B, ncap + 1), dtype=torch.float32, device=dev)
+        v = torch.empty((B, ncap + 1), dtype=torch.float32, device=dev)
+        with self._ws.use(lib.imcui_hip_imp_workspace_bytes(B, ncap), dev) as ws:
+            hd.launch(
+                lib.imcui_hip_imp_ot_probe, _ptr(scores), B, ncap, _ptr(n0), _ptr(n1), float(bin_score), int(iterations), float(p),
+                _ptr(m0), _ptr(m1), _ptr(s0), _ptr(s1), _ptr(u), _ptr(v), _ptr(ws), ws.numel(),
+            )  # fmt: skip
+        return {"matches0": m0, "matches1": m1, "matching_scores0": s0, "matching_scores1": s1, "u": u, "v": v}
+
+
 # ------------------------------------------------------------------ LoFTR
 def _fold_bn(w: torch.Tensor, sd: dict, bn: str | None, eps: float = 1e-5):
     """conv (no bias) followed by eval-mode BatchNorm -> (w', b')."""

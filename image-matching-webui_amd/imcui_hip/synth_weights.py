@@ -320,6 +320,37 @@ def superglue_state_dict(seed: int = 0, structured: bool = True) -> dict:
     return sd
 
 
+def imp_synth_state(seed: int = 0) -> dict:
+    """Random IMP weights in the state-dict layout of pram.nets.gml.GML (`imp_gml.920.pth` under its "model" key; names and shapes
+    are the table of csrc/imp.hip): SuperGlue's key-point encoder and 18 attentional layers, plus
+
+    input_proj.{weight[256,128,1],bias}       128-d descriptors -> the 256-d token states
+    final_proj.{0..8}.{weight[256,256,1],bias} one per layer pair (training supervises every pair; inference reads .8)
+    bin_score                                 scalar
+
+    Structured like `superglue_state_dict`: damped residual updates and `final_proj.8` near a scaled identity.  `input_proj` is an
+    isometry (orthonormal columns) plus small noise, so distinctive unit descriptors stay distinctive: their inner products, and with
+    them the score of a true correspondence (about 60 cos), survive the projection, and 20 probability-domain Sinkhorn rounds resolve
+    the true correspondences above the dust-bin score (tests/test_imp_cpu.py asserts the share).
+    """
+    sd = superglue_state_dict(seed, structured=True)
+    g = torch.Generator().manual_seed(seed + 7919)
+    fw, fb = sd.pop("final_proj.weight"), sd.pop("final_proj.bias")
+    for k in range(9):
+        if k == 8:
+            sd["final_proj.8.weight"], sd["final_proj.8.bias"] = fw, fb
+        else:  # read by no inference path; present because the checkpoint is loaded strictly
+            sd[f"final_proj.{k}.weight"] = (torch.rand(256, 256, 1, generator=g) * 2 - 1) * math.sqrt(3.0 / 256)
+            sd[f"final_proj.{k}.bias"] = (torch.rand(256, generator=g) * 2 - 1) * 0.1
+    q, _ = torch.linalg.qr(torch.randn(256, 128, generator=g, dtype=torch.float64))
+    sd["input_proj.weight"] = (q.float() + 0.01 * torch.randn(256, 128, generator=g))[:, :, None].contiguous()
+    sd["input_proj.bias"] = 0.01 * torch.randn(256, generator=g)
+    # true correspondences score about 80 after the 18 layers, the best outlier up to about 42 (512 .. 2100 points per image): between them,
+    # far enough above the outliers that an unmatched row keeps less than 1e-6 outside its dust-bin
+    sd["bin_score"] = torch.tensor(58.0)
+    return sd
+
+
 def eloftr_state_dict(seed: int = 0, gain: float = 1.0, shaped: bool = True) -> dict:
     """Random EfficientLoFTR weights in the layout of `transformers.EfficientLoFTRForKeypointMatching.state_dict()`
     (the maintained port of the upstream network the reference wrapper imports, imcui/hloc/matchers/eloftr.py:13-18):

@@ -11,6 +11,7 @@
  *   imcui_hip_loftr_forward       <- imcui/hloc/matchers/loftr.py:54            `self.net(data_)`
  *   imcui_hip_dual_softmax        <- imcui/hloc/matchers/dual_softmax.py:62-75  `dual_softmax_matcher(...)`
  *   imcui_hip_superglue_forward   <- imcui/hloc/matchers/superglue.py:42-43     `self.net(data)`
+ *   imcui_hip_imp_forward         <- imcui/hloc/matchers/imp.py:51              `self.net.produce_matches(data, p=0.2)`
  *   *_pack_weights                <- the `_init` weight loading (superpoint.py:48-53, lightglue.py:39-51)
  *
  * Conventions
@@ -816,6 +817,35 @@ int imcui_hip_superglue_forward(imcui_hip_t* h, const float* packed, int B, int 
                                 const float* descriptors1, const int* n0, const int* n1, float w0, float h0, float w1, float h1,
                                 int sinkhorn_iterations, double match_threshold, int* matches0, int* matches1,
                                 float* matching_scores0, float* matching_scores1, void* ws, size_t ws_bytes, void* stream);
+
+/* ---- IMP (`sfd2+imp`; imcui/hloc/matchers/imp.py:51 `self.net.produce_matches(data, p=0.2)`, pram.nets.gml.GML) ---------- */
+/* The state dict in ONE table (csrc/imp.hip): imcui_hip_imp_num_tensors() entries, entry i named imcui_hip_imp_tensor_name(i)
+ * with the shape imcui_hip_imp_tensor_shape(i, dims) (returns the number of dimensions, at most 3; 0 = scalar; -1 = bad index).
+ * imp.py:41-44 loads exactly these names strictly.  Packing (imp.py:40-44 `GML(conf)` + `load_state_dict`): `tensors` holds the
+ * host pointers in table order; eval-mode BatchNorm and attn.merge are folded into the neighbouring layers, heads are
+ * de-interleaved, of the nine final projections only final_proj.8 is packed (inference reads no other). */
+size_t imcui_hip_imp_packed_floats(void);
+int imcui_hip_imp_num_tensors(void);
+const char* imcui_hip_imp_tensor_name(int i);
+int imcui_hip_imp_tensor_shape(int i, int* dims);
+int imcui_hip_imp_pack_weights(const float* const* tensors, float* packed);
+size_t imcui_hip_imp_workspace_bytes(int B, int ncap);
+/* imp.py:51 for B pairs.  keypoints0/1 [dev, B,ncap,2] pixel (x,y); scores0/1 [dev, B,ncap]; descriptors0/1 [dev, B,ncap,128]
+ * (row per key-point: what imp.py:48-49 hands over); n0/n1 [dev, B] int32 valid counts (<= ncap <= 4096); (w0,h0)/(w1,h1): image
+ * sizes, used to normalise key-points only.  sinkhorn_iterations = conf (imp.py:19); match_threshold = the `p` of imp.py:51.
+ * Outputs [dev]: matches0/1 [B,ncap] int32 (-1 = unmatched), matching_scores0/1 [B,ncap] (probabilities); a pair with an empty
+ * side gets all -1 / 0, entries >= n are -1 / 0.  No host synchronisation; graph-capturable. */
+int imcui_hip_imp_forward(imcui_hip_t* h, const float* packed, int B, int ncap, const float* keypoints0, const float* keypoints1,
+                          const float* scores0, const float* scores1, const float* descriptors0, const float* descriptors1,
+                          const int* n0, const int* n1, float w0, float h0, float w1, float h1, int sinkhorn_iterations,
+                          double match_threshold, int* matches0, int* matches1, float* matching_scores0, float* matching_scores1,
+                          void* ws, size_t ws_bytes, void* stream);
+/* Test hook: the assignment stage of imp.py:51 alone (dust-bin soft-max, `iterations` probability-domain Sinkhorn rounds, mutual
+ * arg-max, strict threshold `p`) on given scores [dev, B,ncap,ncap] (pair b uses its top-left n0[b] x n1[b]).  u / v [dev, B,ncap+1]
+ * (may be NULL): the row / column scalings, entry n0[b] / n1[b] = the dust-bin's.  Workspace: imcui_hip_imp_workspace_bytes. */
+int imcui_hip_imp_ot_probe(imcui_hip_t* h, const float* scores, int B, int ncap, const int* n0, const int* n1, float bin_score,
+                           int iterations, double p, int* matches0, int* matches1, float* matching_scores0, float* matching_scores1,
+                           float* u, float* v, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- LoFTR (kornia.feature.LoFTR behind imcui/hloc/matchers/loftr.py:54) ---- */
 /* Host-side packing.  Every convolution / Linear is one layer W[N][K] (+ bias[N], may be NULL) in GEMM
