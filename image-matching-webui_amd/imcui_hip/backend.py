@@ -124,6 +124,16 @@ def _pad_rows(t: torch.Tensor, n: int, device: torch.device) -> torch.Tensor:
     return o
 
 
+def _pack_arrays(arrs: list, n_floats: int, pack_call, *lead) -> torch.Tensor:
+    """`pack_call(*lead, pointers to the float32 host arrays `arrs`, packed)` -> the float32 buffer (host) it filled."""
+    packed = np.zeros(n_floats, dtype=np.float32)
+    tp = (C.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
+    rc = pack_call(*lead, tp, packed.ctypes.data)
+    if rc != 0:
+        raise ImcuiHipError(f"{pack_call.__name__} failed ({rc})")
+    return torch.from_numpy(packed)
+
+
 def _pack_named(kind: str, layout_name: str, names: list, shapes: dict, state_dict: dict, n_floats: int, pack_call, *lead) -> torch.Tensor:
     """The strict packer of a network whose library entry takes its tensors by name order: `state_dict` (already without the keys the
     caller ignores) must hold exactly `names`, each with its shape in `shapes`; `pack_call(*lead, tensor pointers, packed)` fills the
@@ -138,12 +148,7 @@ def _pack_named(kind: str, layout_name: str, names: list, shapes: dict, state_di
         if a.shape != shapes[n]:
             raise ImcuiHipError(f"{kind} state dict: '{n}' has shape {a.shape}, expected {shapes[n]}")
         arrs.append(a)
-    packed = np.zeros(n_floats, dtype=np.float32)
-    tp = (C.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
-    rc = pack_call(*lead, tp, packed.ctypes.data)
-    if rc != 0:
-        raise ImcuiHipError(f"{pack_call.__name__} failed ({rc})")
-    return torch.from_numpy(packed)
+    return _pack_arrays(arrs, n_floats, pack_call, *lead)
 
 
 def _same_device(packed: torch.Tensor, image: torch.Tensor) -> None:
@@ -2753,12 +2758,37 @@ def pack_superglue(state_dict: dict) -> torch.Tensor:
         arrs.append(_as_f32_host(state_dict[n]).reshape(-1) if n == "bin_score" else _as_f32_host(state_dict[n]))
     if arrs[0].size != 32 * 3 or arrs[names.index("gnn.layers.17.mlp.3.weight")].size != 256 * 512:
         raise ImcuiHipError("only the 256-d / 4-head / 18-layer SuperGlue with the [32,64,128,256] key-point encoder is supported")
-    packed = np.zeros(lib.imcui_hip_superglue_packed_floats(), dtype=np.float32)
-    tp = (C.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
-    rc = lib.imcui_hip_superglue_pack_weights(tp, packed.ctypes.data)
-    if rc != 0:
-        raise ImcuiHipError(f"imcui_hip_superglue_pack_weights failed ({rc})")
-    return torch.from_numpy(packed)
+    return _pack_arrays(arrs, lib.imcui_hip_superglue_packed_floats(), lib.imcui_hip_superglue_pack_weights)
+
+
+def _glue_forward(wsp, ws_bytes_fn: str, forward_fn: str, packed, kpts0, kpts1, scores0, scores1, desc0, desc1, n0, n1, size0, size1,
+                  sinkhorn_iterations, match_threshold) -> dict:  # fmt: skip
+    """The forward of the matchers on the SuperGlue trunk (SuperGlueHIP, IMPHIP), which differ in the two library entries named here:
+    pads both sides to one ncap, runs in the workspace `wsp`, returns matches / scores cut back to each side's own length."""
+    dev = kpts0.device
+    hd = get_handle(dev)
+    lib = hd.lib
+    B, ncap0 = kpts0.shape[0], kpts0.shape[1]
+    ncap1 = kpts1.shape[1]
+    ncap = max(ncap0, ncap1, 1)
+    kpts0, kpts1, desc0, desc1, scores0, scores1 = (_pad_rows(t, ncap, dev) for t in (kpts0, kpts1, desc0, desc1, scores0, scores1))
+    n0 = n0.to(device=dev, dtype=torch.int32).contiguous()
+    n1 = n1.to(device=dev, dtype=torch.int32).contiguous()
+    m0 = torch.empty((B, ncap), dtype=torch.int32, device=dev)
+    m1 = torch.empty((B, ncap), dtype=torch.int32, device=dev)
+    s0 = torch.empty((B, ncap), dtype=torch.float32, device=dev)
+    s1 = torch.empty((B, ncap), dtype=torch.float32, device=dev)
+    with wsp.use(getattr(lib, ws_bytes_fn)(B, ncap), dev) as ws:
+        hd.launch(
+            getattr(lib, forward_fn), _ptr(packed), B, ncap, _ptr(kpts0), _ptr(kpts1), _ptr(scores0), _ptr(scores1), _ptr(desc0), _ptr(desc1),
+            _ptr(n0), _ptr(n1), float(size0[0]), float(size0[1]), float(size1[0]), float(size1[1]),
+            int(sinkhorn_iterations), float(match_threshold),
+            _ptr(m0), _ptr(m1), _ptr(s0), _ptr(s1), _ptr(ws), ws.numel(),
+        )  # fmt: skip
+    return {
+        "matches0": m0[:, :ncap0], "matches1": m1[:, :ncap1], "matching_scores0": s0[:, :ncap0],
+        "matching_scores1": s1[:, :ncap1],
+    }  # fmt: skip
 
 
 class SuperGlueHIP:
@@ -2768,35 +2798,13 @@ class SuperGlueHIP:
     def forward(self, packed, kpts0, kpts1, scores0, scores1, desc0, desc1, n0, n1, size0, size1, sinkhorn_iterations,
                 match_threshold):  # fmt: skip
         """kptsX [B,ncap,2], scoresX [B,ncap], descX [B,ncap,256] (row per point), nX [B] int32 on the GPU; sizeX = (W, H)."""
-        dev = kpts0.device
-        hd = get_handle(dev)
-        lib = hd.lib
-        B, ncap0 = kpts0.shape[0], kpts0.shape[1]
-        ncap1 = kpts1.shape[1]
-        ncap = max(ncap0, ncap1, 1)
-        kpts0, kpts1, desc0, desc1, scores0, scores1 = (_pad_rows(t, ncap, dev) for t in (kpts0, kpts1, desc0, desc1, scores0, scores1))
-        n0 = n0.to(device=dev, dtype=torch.int32).contiguous()
-        n1 = n1.to(device=dev, dtype=torch.int32).contiguous()
-        m0 = torch.empty((B, ncap), dtype=torch.int32, device=dev)
-        m1 = torch.empty((B, ncap), dtype=torch.int32, device=dev)
-        s0 = torch.empty((B, ncap), dtype=torch.float32, device=dev)
-        s1 = torch.empty((B, ncap), dtype=torch.float32, device=dev)
-        with self._ws.use(lib.imcui_hip_superglue_workspace_bytes(B, ncap), dev) as ws:
-            hd.launch(
-                lib.imcui_hip_superglue_forward, _ptr(packed), B, ncap, _ptr(kpts0), _ptr(kpts1), _ptr(scores0), _ptr(scores1), _ptr(desc0), _ptr(desc1),
-                _ptr(n0), _ptr(n1), float(size0[0]), float(size0[1]), float(size1[0]), float(size1[1]),
-                int(sinkhorn_iterations), float(match_threshold),
-                _ptr(m0), _ptr(m1), _ptr(s0), _ptr(s1), _ptr(ws), ws.numel(),
-            )  # fmt: skip
-        return {
-            "matches0": m0[:, :ncap0], "matches1": m1[:, :ncap1], "matching_scores0": s0[:, :ncap0],
-            "matching_scores1": s1[:, :ncap1],
-        }  # fmt: skip
+        return _glue_forward(self._ws, "imcui_hip_superglue_workspace_bytes", "imcui_hip_superglue_forward", packed, kpts0, kpts1, scores0, scores1,
+                             desc0, desc1, n0, n1, size0, size1, sinkhorn_iterations, match_threshold)  # fmt: skip
 
 
 # ------------------------------------------------------------------ IMP
 def imp_tensor_table() -> list[tuple[str, tuple]]:
-    """(state-dict name, shape) of every tensor of `imp_gml.920.pth`, from the one table in csrc/imp.hip."""
+    """(state-dict name, shape) of every tensor of `imp_gml.920.pth`, from the one table generator in csrc/glue_shared.h."""
     lib = load_library()
     dims = (C.c_int * 3)()
     out = []
@@ -2833,12 +2841,7 @@ def pack_imp(state_dict: dict, conf: dict | None = None) -> torch.Tensor:
         if tuple(state_dict[n].shape) != shp:
             raise ImcuiHipError(f"IMP: '{n}' has shape {tuple(state_dict[n].shape)}, the network needs {shp}")
         arrs.append(_as_f32_host(state_dict[n]).reshape(-1) if not shp else _as_f32_host(state_dict[n]))
-    packed = np.zeros(lib.imcui_hip_imp_packed_floats(), dtype=np.float32)
-    tp = (C.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
-    rc = lib.imcui_hip_imp_pack_weights(tp, packed.ctypes.data)
-    if rc != 0:
-        raise ImcuiHipError(f"imcui_hip_imp_pack_weights failed ({rc})")
-    return torch.from_numpy(packed)
+    return _pack_arrays(arrs, lib.imcui_hip_imp_packed_floats(), lib.imcui_hip_imp_pack_weights)
 
 
 class IMPHIP:
@@ -2848,30 +2851,8 @@ class IMPHIP:
     def forward(self, packed, kpts0, kpts1, scores0, scores1, desc0, desc1, n0, n1, size0, size1, sinkhorn_iterations,
                 match_threshold):  # fmt: skip
         """kptsX [B,ncap,2], scoresX [B,ncap], descX [B,ncap,128] (row per point), nX [B] int32 on the GPU; sizeX = (W, H)."""
-        dev = kpts0.device
-        hd = get_handle(dev)
-        lib = hd.lib
-        B, ncap0 = kpts0.shape[0], kpts0.shape[1]
-        ncap1 = kpts1.shape[1]
-        ncap = max(ncap0, ncap1, 1)
-        kpts0, kpts1, desc0, desc1, scores0, scores1 = (_pad_rows(t, ncap, dev) for t in (kpts0, kpts1, desc0, desc1, scores0, scores1))
-        n0 = n0.to(device=dev, dtype=torch.int32).contiguous()
-        n1 = n1.to(device=dev, dtype=torch.int32).contiguous()
-        m0 = torch.empty((B, ncap), dtype=torch.int32, device=dev)
-        m1 = torch.empty((B, ncap), dtype=torch.int32, device=dev)
-        s0 = torch.empty((B, ncap), dtype=torch.float32, device=dev)
-        s1 = torch.empty((B, ncap), dtype=torch.float32, device=dev)
-        with self._ws.use(lib.imcui_hip_imp_workspace_bytes(B, ncap), dev) as ws:
-            hd.launch(
-                lib.imcui_hip_imp_forward, _ptr(packed), B, ncap, _ptr(kpts0), _ptr(kpts1), _ptr(scores0), _ptr(scores1), _ptr(desc0), _ptr(desc1),
-                _ptr(n0), _ptr(n1), float(size0[0]), float(size0[1]), float(size1[0]), float(size1[1]),
-                int(sinkhorn_iterations), float(match_threshold),
-                _ptr(m0), _ptr(m1), _ptr(s0), _ptr(s1), _ptr(ws), ws.numel(),
-            )  # fmt: skip
-        return {
-            "matches0": m0[:, :ncap0], "matches1": m1[:, :ncap1], "matching_scores0": s0[:, :ncap0],
-            "matching_scores1": s1[:, :ncap1],
-        }  # fmt: skip
+        return _glue_forward(self._ws, "imcui_hip_imp_workspace_bytes", "imcui_hip_imp_forward", packed, kpts0, kpts1, scores0, scores1,
+                             desc0, desc1, n0, n1, size0, size1, sinkhorn_iterations, match_threshold)  # fmt: skip
 
     def ot_probe(self, scores, n0, n1, bin_score, iterations, p=0.2) -> dict:
         """The assignment stage alone (imcui_hip_imp_ot_probe): scores [B,ncap,ncap] float32 on the GPU, n0 / n1 [B] int32.

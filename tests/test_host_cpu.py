@@ -270,6 +270,21 @@ def test_superglue_packing_folds_bn_merge_and_heads(lib):
     assert (ms - ref["matching_scores0"]).abs().max().item() < 1e-4
 
 
+def test_superglue_and_imp_packed_buffers_are_pinned(lib):
+    """SuperGlue and IMP pack through one body (csrc/glue_shared.h); the buffers stay byte for byte what the two separate packers
+    wrote.  The digests were computed with the library of commit d64d14b (the last one with a packer per file), not with the code
+    under test."""
+    import hashlib
+
+    from imcui_hip import backend
+    from imcui_hip.synth_weights import imp_synth_state, superglue_state_dict
+
+    sg = backend.pack_superglue(superglue_state_dict(3)).numpy()
+    assert hashlib.sha256(sg.tobytes()).hexdigest() == "0d16437be4efb0c62602c8a8af8eaae3a3355dff6f4dcbe17c9cb04094c238a5"
+    imp = backend.pack_imp(imp_synth_state(0)).numpy()
+    assert hashlib.sha256(imp.tobytes()).hexdigest() == "53a7e3d4cb6befb04e69a7292454f4868f97c3a9002870ffd75c8a3b54c7721b"
+
+
 def test_eloftr_upstream_checkpoint_names_round_trip():
     """The zoo's `eloftr` entry downloads `eloftr_outdoor.ckpt` and loads `["state_dict"]` with the UPSTREAM module names
     (imcui/hloc/matchers/eloftr.py:56-61).  The plugin's name map must be a bijection onto the names the packer reads: port
