@@ -14,6 +14,7 @@ enum SimRedMode {
     SR_DSBEST = 2,  // conf = softmax_col(x) * softmax_row(x): per row best (value, first column), per column best value   (pass 2, LoFTR family)
     SR_LGBEST = 3,  // LightGlue's log assignment: per row best (value, first column), per column best (value, first row)   (pass 2)
     SR_NN1 = 4,     // SR_NN without the second best (find_nn without a ratio test): r1 / c1 are not written
+    SR_NND = 5,     // SR_NN of x = (2 A.B^T - rnorm[i]) - cnorm[j] = minus the squared distance of unnormalised descriptors (AdaLAM, adalam.hip)
 };
 
 #define SR_TILE 128  // rows per workgroup block and columns per tile
@@ -45,6 +46,8 @@ struct SimRedP {
     const float *rmax = nullptr, *rsum = nullptr, *cmax = nullptr, *csum = nullptr;
     const float *l0 = nullptr, *l1 = nullptr;  // SR_LGBEST: logsigmoid(z0) of row i of batch b at l0[b * l0_bs + i], logsigmoid(z1) likewise
     long l0_bs = 0, l1_bs = 0;
+    const float *rnorm = nullptr, *cnorm = nullptr;  // SR_NND: squared norm of row i of batch b at rnorm[b * rn_bs + i], of column j at cnorm[b * cn_bs + j]
+    long rn_bs = 0, cn_bs = 0;
     // SR_DSBEST: [batch][ceil(M / 128)][ceil(N / 128)] tile flags (0 = no entry of the tile can exceed the threshold: skipped), or nullptr
     const unsigned char* flags = nullptr;
     int dbg = 0;  // lab switch (IMCUI_SR_DBG, read once): bit 0 = skip the per-column part of the epilogue, bit 1 = skip the per-row part (both: WRONG results, timing only), bit 2 = the two column halves half a tile apart (results unchanged; slower: simred.hip), bit 3 = 32-row wave tiles at every width (results unchanged; A/B of the 64-row tiles of K <= 128)

@@ -92,7 +92,8 @@ void simred_pack(imcui_hip_s* h, const float* X, long ldr, long ldk, long xbs, i
 template <int KS, int WN, int MODE, bool F32>
 __global__ __launch_bounds__(512, 2) void simred_kernel(SimRedP p) {
     constexpr int NW = 8, NWM = NW / WN, RF = 4 / NWM, NF = 4 / WN, KT = KS / 2, PPW = 16 / NW;
-    constexpr bool ISNN = MODE == SR_NN || MODE == SR_NN1;  // SR_NN1: no second best (find_nn without a ratio test)
+    constexpr bool ISNN = MODE == SR_NN || MODE == SR_NN1 || MODE == SR_NND;  // SR_NN1: no second best (find_nn without a ratio test)
+    constexpr bool NN2 = MODE == SR_NN || MODE == SR_NND;                    // the modes that keep a second best
     constexpr bool PREMASK = ISNN || MODE == SR_LSE;       // columns past the matrix are set to -inf in the accumulators, before the epilogue
     static_assert(WN == 2 || WN == 4, "column groups of waves");
     static_assert(KT >= 2, "at least two stages per tile");
@@ -224,6 +225,7 @@ __global__ __launch_bounds__(512, 2) void simred_kernel(SimRedP p) {
             rc1[f] = (MODE == SR_DSBEST) ? __builtin_amdgcn_rcpf(p.rsum[ro]) : p.rsum[ro];
             if (MODE == SR_LGBEST) rc2[f] = p.l0[(size_t)b * p.l0_bs + rg];
         }
+        if constexpr (MODE == SR_NND) rc0[f] = p.rnorm[(size_t)b * p.rn_bs + min(rowg0 + 32 * f, Mb - 1)];
     }
 
     const int S = ntl * KT;
@@ -258,6 +260,12 @@ __global__ __launch_bounds__(512, 2) void simred_kernel(SimRedP p) {
                 ctab[jl] = p.cmax[co];
                 ctab[SR_TILE + jl] = (MODE == SR_DSBEST) ? __builtin_amdgcn_rcpf(p.csum[co]) : p.csum[co];
                 if (MODE == SR_LGBEST) ctab[2 * SR_TILE + jl] = p.l1[(size_t)b * p.l1_bs + j];
+            }
+        }
+        if constexpr (MODE == SR_NND) {  // the tile's column norms, the same way
+            if (wm * 64 + lane < NF * 32) {
+                const int jl = wn * (NF * 32) + wm * 64 + lane;
+                ctab[jl] = p.cnorm[(size_t)b * p.cn_bs + min(ct * SR_TILE + jl, Nb - 1)];
             }
         }
 #pragma unroll
@@ -330,6 +338,21 @@ __global__ __launch_bounds__(512, 2) void simred_kernel(SimRedP p) {
         // second copy of the masking part and as a second copy of the whole epilogue -- and both made hipcc spill: the accumulators are
         // rewritten in place and two variants of that meeting in one control-flow join keep both register sets alive)
         const int jlim = Nb - jb;  // column c of the lane's list is live when c < jlim
+        if constexpr (MODE == SR_NND) {
+            // x = (2 a.b - |a|^2) - |b|^2 in place (2 a.b is exact, so a contracted and an uncontracted build round alike); from here on SR_NN
+#pragma unroll
+            for (int f = 0; f < RF; ++f)
+#pragma unroll
+                for (int n = 0; n < NF; ++n)
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        const float4 t0 = *reinterpret_cast<const float4*>(ctab + wn * (NF * 32) + 4 * ehi + n * 32 + 8 * q);
+                        acc[f][n][4 * q + 0] = (2.0f * acc[f][n][4 * q + 0] - rc0[f]) - t0.x;
+                        acc[f][n][4 * q + 1] = (2.0f * acc[f][n][4 * q + 1] - rc0[f]) - t0.y;
+                        acc[f][n][4 * q + 2] = (2.0f * acc[f][n][4 * q + 2] - rc0[f]) - t0.z;
+                        acc[f][n][4 * q + 3] = (2.0f * acc[f][n][4 * q + 3] - rc0[f]) - t0.w;
+                    }
+        }
         if constexpr (PREMASK) {
             // only the last column tile of a matrix has dead columns: they are set to -inf IN PLACE, in a block of its own, so the common
             // tile pays neither the compare nor the select per element (a second copy of the epilogue for it made hipcc spill: see above)
@@ -371,7 +394,7 @@ __global__ __launch_bounds__(512, 2) void simred_kernel(SimRedP p) {
                     (void)valid, (void)x;
                     if constexpr (ISNN) {
                         // (alpha is 1 for the nearest-neighbour modes: simred_launch refuses anything else; dead columns are -inf already)
-                        if constexpr (MODE == SR_NN) {
+                        if constexpr (NN2) {
                             q1[f] = __builtin_amdgcn_fmed3f(q0[f], q1[f], acc[f][n][r]);  // second best of {best, second, x} (second <= best)
                             q0[f] = fmaxf(q0[f], acc[f][n][r]);
                         }
@@ -477,7 +500,7 @@ __global__ __launch_bounds__(512, 2) void simred_kernel(SimRedP p) {
                     for (int u = 31; u >= 0; --u) ti = (v[u] == tm) ? 64 * (u >> 4) + (u & 15) : ti;
                     ti += rbase;
                     float b2 = -INFINITY;
-                    if constexpr (MODE == SR_NN) {
+                    if constexpr (NN2) {
                         // second best = the maximum of the list with ONE occurrence of the best removed: the running pair over the values
                         float b1 = -INFINITY;
 #pragma unroll
@@ -497,14 +520,14 @@ __global__ __launch_bounds__(512, 2) void simred_kernel(SimRedP p) {
                                                                           : __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, b2), 0x4E, 0xF, 0xF, true));
                         (void)ctrl;
                         const bool up = om > tm || (om == tm && oi < ti);
-                        if (MODE == SR_NN) b2 = up ? fmaxf(tm, o2) : fmaxf(b2, om);
+                        if (NN2) b2 = up ? fmaxf(tm, o2) : fmaxf(b2, om);
                         (void)o2;
                         ti = up ? oi : ti;
                         tm = up ? om : tm;
                     }
                     if (part == 0 && j < Nb) {
                         p.c0[o] = tm;
-                        if (MODE == SR_NN) p.c1[o] = b2;
+                        if (NN2) p.c1[o] = b2;
                         p.ci[o] = ti;
                     }
                 } else if constexpr (MODE == SR_LSE) {
@@ -598,7 +621,7 @@ __global__ __launch_bounds__(512, 2) void simred_kernel(SimRedP p) {
             if (rowl0 + 32 * f < rowsv) {
                 const size_t o = ((size_t)b * p.nchunk + chunk) * p.r_pitch + rowg0 + 32 * f;
                 p.r0[o] = q0[f];
-                if (MODE == SR_NN || MODE == SR_LSE) p.r1[o] = q1[f];
+                if (NN2 || MODE == SR_LSE) p.r1[o] = q1[f];
                 if (MODE != SR_LSE) p.ri[o] = qi[f];
             }
     }
@@ -645,6 +668,7 @@ static int sr_launch_m(imcui_hip_s* h, const SimRedP& p, hipStream_t stream) {
     switch (p.mode) {
         case SR_NN: return sr_launch_k<SR_NN, F32>(h, p, stream);
         case SR_NN1: return sr_launch_k<SR_NN1, F32>(h, p, stream);
+        case SR_NND: return sr_launch_k<SR_NND, F32>(h, p, stream);
         case SR_LSE: return sr_launch_k<SR_LSE, F32>(h, p, stream);
         case SR_DSBEST: return sr_launch_k<SR_DSBEST, F32>(h, p, stream);
         case SR_LGBEST: return sr_launch_k<SR_LGBEST, F32>(h, p, stream);
@@ -660,7 +684,8 @@ int simred_launch(imcui_hip_s* h, const SimRedP& p, hipStream_t stream) {
     if ((nct + p.nchunk - 1) / p.nchunk > SR_MAXLIST) return imcui_set_err(h, IMCUI_ERR_ARG, "simred: more than %d column tiles per chunk", SR_MAXLIST);
     if ((p.mode == SR_DSBEST || p.mode == SR_LGBEST) && (!p.rmax || !p.rsum || !p.cmax || !p.csum || (p.mode == SR_LGBEST && (!p.l0 || !p.l1))))
         return imcui_set_err(h, IMCUI_ERR_ARG, "simred: pass 2 needs the statistics of pass 1");
-    if ((p.mode == SR_NN || p.mode == SR_NN1) && p.alpha != 1.0f) return imcui_set_err(h, IMCUI_ERR_ARG, "simred: the nearest-neighbour modes take alpha = 1");
+    if (p.mode == SR_NND && (!p.rnorm || !p.cnorm)) return imcui_set_err(h, IMCUI_ERR_ARG, "simred: the distance mode needs both squared norms");
+    if ((p.mode == SR_NN || p.mode == SR_NN1 || p.mode == SR_NND) && p.alpha != 1.0f) return imcui_set_err(h, IMCUI_ERR_ARG, "simred: the nearest-neighbour modes take alpha = 1");
     if (!(p.alpha > 0.0f)) return imcui_set_err(h, IMCUI_ERR_ARG, "simred: alpha must be positive");
     static const int dbg = getenv("IMCUI_SR_DBG") ? atoi(getenv("IMCUI_SR_DBG")) : 0;  // (lab switch, read once per process)
     SimRedP q = p;

@@ -2879,6 +2879,99 @@ class IMPHIP:
         return {"matches0": m0, "matches1": m1, "matching_scores0": s0, "matching_scores1": s1, "u": u, "v": v}
 
 
+# ------------------------------------------------------------------ AdaLAM
+ADALAM_CONF_KEYS = ("area_ratio", "search_expansion", "ransac_iters", "min_inliers", "min_confidence", "orientation_difference_threshold",
+                    "scale_rate_threshold", "detected_scale_rate_threshold", "refit", "force_seed_mnn")  # the order of the C ABI's conf array
+ADALAM_MAX_KEYPOINTS = 4096  # AL_MAXN of csrc/adalam.hip
+ADALAM_WIDTHS = (64, 128, 256)
+
+
+def adalam_conf_array(conf: dict):
+    """The conf as the C ABI takes it: 10 doubles in ADALAM_CONF_KEYS order, None (a threshold that is off) as -1."""
+    vals = []
+    for k in ADALAM_CONF_KEYS:
+        v = conf[k]
+        if v is None:
+            if not k.endswith("_threshold"):
+                raise ImcuiHipError(f"AdaLAM: conf['{k}'] is None")
+            v = -1.0
+        elif k.endswith("_threshold") and float(v) < 0:
+            raise ImcuiHipError(f"AdaLAM: conf['{k}'] = {v} (a threshold is None or >= 0)")
+        vals.append(float(v))
+    return (C.c_double * len(vals))(*vals)
+
+
+def adalam_needs(conf: dict) -> tuple:
+    """(orientations needed, scales needed): whether the two relative tests are on (kornia: off at None, or at >= 180 / >= 10)."""
+    ot, st = conf["orientation_difference_threshold"], conf["scale_rate_threshold"]
+    return ot is not None and float(ot) < 180.0, st is not None and float(st) < 10.0
+
+
+class AdaLAMHIP:
+    def __init__(self):
+        self._ws = _Workspace()
+
+    def _run(self, desc, nn_in, kpts0, kpts1, n0, n1, size0, size1, conf, scales_oris, probe, members):
+        dev = kpts0.device
+        hd = get_handle(dev)
+        lib = hd.lib
+        B, ncap = kpts0.shape[0], max(kpts0.shape[1], kpts1.shape[1], 1)
+        if ncap > ADALAM_MAX_KEYPOINTS:
+            raise ImcuiHipError(f"AdaLAM: {ncap} key-points per image, the kernels take at most {ADALAM_MAX_KEYPOINTS}")
+        carr = adalam_conf_array(conf)
+        need_o, need_s = adalam_needs(conf)
+        s0, o0, s1, o1 = (None,) * 4 if scales_oris is None else scales_oris
+        if need_o and (o0 is None or o1 is None):
+            raise ImcuiHipError("AdaLAM: orientation_difference_threshold is active but oris0 / oris1 are missing")
+        if need_s and (s0 is None or s1 is None):
+            raise ImcuiHipError("AdaLAM: scale_rate_threshold is active but scales0 / scales1 are missing")
+        k0, k1 = _pad_rows(kpts0, ncap, dev), _pad_rows(kpts1, ncap, dev)
+        so = [None if t is None else _pad_rows(t, ncap, dev) for t in (s0, s1, o0, o1)]
+        n0 = n0.to(device=dev, dtype=torch.int32).contiguous()
+        n1 = n1.to(device=dev, dtype=torch.int32).contiguous()
+        (w0, h0), (w1, h1) = size0, size1
+        m0 = torch.empty((B, ncap), dtype=torch.int32, device=dev)
+        ms0 = torch.empty((B, ncap), dtype=torch.float32, device=dev)
+        out = {"matches0": m0, "matching_scores0": ms0}
+        opt = {}
+        if probe:
+            opt = {"seed": torch.empty((B, ncap), dtype=torch.int32, device=dev), "seed_info": torch.empty((B, ncap, 4), dtype=torch.int32, device=dev),
+                   "seed_conf": torch.empty((B, ncap), dtype=torch.float32, device=dev)}  # fmt: skip
+            if members:
+                opt["seed_members"] = torch.full((B, ncap, ncap), -1, dtype=torch.int32, device=dev)
+        tail = (_ptr(opt.get("seed")), _ptr(opt.get("seed_members")), _ptr(opt.get("seed_info")), _ptr(opt.get("seed_conf")))
+        geom = (_ptr(k0), _ptr(k1), _ptr(so[0]), _ptr(so[1]), _ptr(so[2]), _ptr(so[3]), _ptr(n0), _ptr(n1), int(h0), int(w0), int(h1), int(w1), carr)
+        if desc is not None:
+            d0, d1 = desc
+            D = d0.shape[2]
+            if D not in ADALAM_WIDTHS or d1.shape[2] != D:
+                raise ImcuiHipError(f"AdaLAM: descriptor width {D} / {d1.shape[2]}, the kernels take {ADALAM_WIDTHS}")
+            d0, d1 = _pad_rows(d0, ncap, dev), _pad_rows(d1, ncap, dev)
+            if probe:
+                opt.update(nn=torch.empty((B, ncap), dtype=torch.int32, device=dev), score=torch.empty((B, ncap), dtype=torch.float32, device=dev),
+                           mnn=torch.empty((B, ncap), dtype=torch.int32, device=dev))  # fmt: skip
+            with self._ws.use(max(256, lib.imcui_hip_adalam_workspace_bytes(hd.h, B, ncap, D)), dev) as ws:
+                hd.launch(lib.imcui_hip_adalam_forward, B, ncap, D, _ptr(d0), _ptr(d1), *geom, _ptr(m0), _ptr(ms0), _ptr(opt.get("nn")),
+                          _ptr(opt.get("score")), _ptr(opt.get("mnn")), *tail, _ptr(ws), ws.numel())  # fmt: skip
+        else:
+            nn, score, mnn = nn_in
+            nn, score, mnn = _pad_rows(nn, ncap, dev).to(torch.int32), _pad_rows(score, ncap, dev), _pad_rows(mnn, ncap, dev).to(torch.int32)
+            with self._ws.use(max(256, lib.imcui_hip_adalam_workspace_bytes(hd.h, B, ncap, 0)), dev) as ws:
+                hd.launch(lib.imcui_hip_adalam_filter, B, ncap, *geom, _ptr(nn), _ptr(score), _ptr(mnn), _ptr(m0), _ptr(ms0), *tail, _ptr(ws), ws.numel())
+        out.update(opt)
+        return out
+
+    def forward(self, kpts0, kpts1, desc0, desc1, n0, n1, size0, size1, conf, scales_oris=None, probe: bool = False, members: bool = False) -> dict:
+        """kptsX [B,ncap,2], descX [B,ncap,D] (row per point, D in ADALAM_WIDTHS), nX [B] int32 on the GPU; sizeX = (W, H); scales_oris =
+        (scales0, oris0, scales1, oris1) [B,ncap] or None; conf = the plugin's.  probe: also nn / score / mnn, seed, seed_info [B,ncap,4]
+        {members, best iteration, count, passed}, seed_conf; members: also seed_members [B,ncap,ncap].  No host synchronisation."""
+        return self._run((desc0, desc1), None, kpts0, kpts1, n0, n1, size0, size1, conf, scales_oris, probe, members)
+
+    def filter(self, kpts0, kpts1, nn, score, mnn, n0, n1, size0, size1, conf, scales_oris=None, probe: bool = True, members: bool = False) -> dict:
+        """Stages B .. G (imcui_hip_adalam_filter) from given nn [B,ncap] int, score [B,ncap] float32, mnn [B,ncap] 0 / 1."""
+        return self._run(None, (nn, score, mnn), kpts0, kpts1, n0, n1, size0, size1, conf, scales_oris, probe, members)
+
+
 # ------------------------------------------------------------------ LoFTR
 def _fold_bn(w: torch.Tensor, sd: dict, bn: str | None, eps: float = 1e-5):
     """conv (no bias) followed by eval-mode BatchNorm -> (w', b')."""

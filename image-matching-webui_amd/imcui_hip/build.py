@@ -12,7 +12,7 @@ CSRC = os.path.normpath(os.path.join(PKG_DIR, "..", "csrc"))
 INCLUDE = os.path.normpath(os.path.join(PKG_DIR, "..", "..", "include"))
 LIB_DIR = os.path.join(PKG_DIR, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libimcui_hip.so")
-SOURCES = ["api.hip", "preprocess.hip", "jpeg.hip", "png.hip", "geometry.hip", "gemm.hip", "gemm_wreg.hip", "ffn.hip", "simred.hip", "conv.hip", "attention.hip", "attention_mx.hip", "superpoint.hip", "disk.hip", "aliked.hip", "alike.hip", "r2d2.hip", "d2net.hip", "lanet.hip", "darkfeat.hip", "sfd2.hip", "dedode.hip", "netvlad.hip", "places.hip", "dog.hip", "sift.hip", "xfeat.hip", "liftfeat.hip", "lisrd.hip", "lightglue.hip", "superglue.hip", "imp.hip", "nn.hip", "dual_softmax.hip", "loftr.hip", "eloftr.hip", "dust3r.hip", "select_probe.hip"]
+SOURCES = ["api.hip", "preprocess.hip", "jpeg.hip", "png.hip", "geometry.hip", "gemm.hip", "gemm_wreg.hip", "ffn.hip", "simred.hip", "conv.hip", "attention.hip", "attention_mx.hip", "superpoint.hip", "disk.hip", "aliked.hip", "alike.hip", "r2d2.hip", "d2net.hip", "lanet.hip", "darkfeat.hip", "sfd2.hip", "dedode.hip", "netvlad.hip", "places.hip", "dog.hip", "sift.hip", "xfeat.hip", "liftfeat.hip", "lisrd.hip", "lightglue.hip", "superglue.hip", "imp.hip", "adalam.hip", "nn.hip", "dual_softmax.hip", "loftr.hip", "eloftr.hip", "dust3r.hip", "select_probe.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value", f"-I{INCLUDE}", f"-I{CSRC}"]
 # Per-source code-generation switches.  preprocess.hip restates host float32 arithmetic that rounds after every
@@ -23,7 +23,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-val
 # gemm.hip (round 4): the same switch for the round-2 GEMM, whose rotary epilogue (EPI_QKV, taken when gemm_wreg_ok says no) compiled to the
 # same class of in-place v_pk_fma_f32 with op_sel (16 per kernel, seen in the ISA); measured performance-neutral on one box (headline
 # 945.6 -> 950.2 pairs/s, LoFTR 100.98 -> 101.04, DUSt3R 89.98 -> 89.83), all kernel tests unchanged.
-EXTRA_FLAGS: dict = {"preprocess.hip": ["-ffp-contract=off"], "d2net.hip": ["-ffp-contract=off"], "lanet.hip": ["-ffp-contract=off"], "darkfeat.hip": ["-ffp-contract=off"], "sfd2.hip": ["-ffp-contract=off"], "dedode.hip": ["-ffp-contract=off"], "lisrd.hip": ["-ffp-contract=off"], "imp.hip": ["-ffp-contract=off"], "gemm_wreg.hip": ["-fno-slp-vectorize"], "gemm.hip": ["-fno-slp-vectorize"]}
+EXTRA_FLAGS: dict = {"preprocess.hip": ["-ffp-contract=off"], "d2net.hip": ["-ffp-contract=off"], "lanet.hip": ["-ffp-contract=off"], "darkfeat.hip": ["-ffp-contract=off"], "sfd2.hip": ["-ffp-contract=off"], "dedode.hip": ["-ffp-contract=off"], "lisrd.hip": ["-ffp-contract=off"], "imp.hip": ["-ffp-contract=off"], "adalam.hip": ["-ffp-contract=off"], "gemm_wreg.hip": ["-fno-slp-vectorize"], "gemm.hip": ["-fno-slp-vectorize"]}
 
 
 def _newest_source_mtime() -> float:
@@ -38,7 +38,7 @@ def needs_build() -> bool:
 # MFMA kernels whose register budget is part of the design: a build that spills them to scratch is rejected (two
 # experimental builds of the split GEMM that spilled -- 128-VGPR and 168-VGPR-with-20-B-scratch variants -- were
 # slower AND failed the parity / determinism tests on the GPU; hipcc is not to be trusted with spills around them).
-NO_SPILL_KERNELS = ("simred_kernel", "gemm_split_kernel", "gemm_wreg_kernel", "gemm_kernel", "attn_split_kernel", "attn_mx_kernel", "attn_kernel", "conv3x3_split_kernel", "conv3x3_tall_kernel", "conv3x3_kernel", "lg_ffn_kernel", "sfd2_", "lf_", "lisrd_match_kernel", "imp_", "glue_")
+NO_SPILL_KERNELS = ("simred_kernel", "gemm_split_kernel", "gemm_wreg_kernel", "gemm_kernel", "attn_split_kernel", "attn_mx_kernel", "attn_kernel", "conv3x3_split_kernel", "conv3x3_tall_kernel", "conv3x3_kernel", "lg_ffn_kernel", "sfd2_", "lf_", "lisrd_match_kernel", "imp_", "glue_", "adalam_")
 
 
 def _check_no_spills(src: str, remarks: str) -> None:

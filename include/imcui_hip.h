@@ -12,6 +12,7 @@
  *   imcui_hip_dual_softmax        <- imcui/hloc/matchers/dual_softmax.py:62-75  `dual_softmax_matcher(...)`
  *   imcui_hip_superglue_forward   <- imcui/hloc/matchers/superglue.py:42-43     `self.net(data)`
  *   imcui_hip_imp_forward         <- imcui/hloc/matchers/imp.py:51              `self.net.produce_matches(data, p=0.2)`
+ *   imcui_hip_adalam_forward      <- imcui/hloc/matchers/adalam.py:46-57        `self.adalam.match_and_filter(...)`
  *   *_pack_weights                <- the `_init` weight loading (superpoint.py:48-53, lightglue.py:39-51)
  *
  * Conventions
@@ -846,6 +847,36 @@ int imcui_hip_imp_forward(imcui_hip_t* h, const float* packed, int B, int ncap, 
 int imcui_hip_imp_ot_probe(imcui_hip_t* h, const float* scores, int B, int ncap, const int* n0, const int* n1, float bin_score,
                            int iterations, double p, int* matches0, int* matches1, float* matching_scores0, float* matching_scores1,
                            float* u, float* v, void* ws, size_t ws_bytes, void* stream);
+
+/* ---- AdaLAM (`adalam`; imcui/hloc/matchers/adalam.py:46-57 `self.adalam.match_and_filter(...)`, kornia.feature.adalam.AdalamFilter) ---- */
+/* No weights.  The rule (stages A .. G) is stated in INTEGRATION.md, "AdaLAM: what is pinned"; csrc/adalam.hip.
+ * conf [host, 10 doubles], the keys of adalam.py:10-21 in this order: area_ratio, search_expansion, ransac_iters, min_inliers,
+ * min_confidence, orientation_difference_threshold, scale_rate_threshold, detected_scale_rate_threshold, refit, force_seed_mnn;
+ * a threshold that is None in Python is passed as a negative number; the two flags as 0 / 1.  It is read during the call.
+ * D = 0: the workspace of imcui_hip_adalam_filter. */
+size_t imcui_hip_adalam_workspace_bytes(imcui_hip_t* h, int B, int ncap, int D);
+/* adalam.py:39-68 for B pairs.  descriptors0/1 [dev, B,ncap,D] (row per key-point, not assumed normalised; D = 64, 128 or 256,
+ * another width is IMCUI_HIP_ERR_UNSUPPORTED); keypoints0/1 [dev, B,ncap,2] pixel (x,y); scales0/1, oris0/1 [dev, B,ncap] (oris in
+ * degrees; a pair of them may be NULL while its threshold is off, otherwise IMCUI_HIP_ERR_ARG); n0/n1 [dev, B] int32 valid counts
+ * (<= ncap <= 4096); (h0,w0)/(h1,w1): image sizes (adalam.py:51-52).  Outputs [dev]: matches0 [B,ncap] int32 (-1 = unmatched;
+ * a pair with fewer than two key-points on a side is all -1, adalam.py:41-44), matching_scores0 [B,ncap] (zeros, adalam.py:67).
+ * Optional outputs (NULL allowed): nn / score / mnn [B,ncap] (nearest neighbour, ratio of the squared distances, mutual flag),
+ * seed [B,ncap] int32 (1 = key-point is a seed), and per seed slot (= the seed's key-point index) seed_members [B,ncap,ncap] int32
+ * (the first seed_info[.,.,0] entries of a slot: its members in (score, index) order), seed_info [B,ncap,4] int32 {members, best
+ * iteration or -1, accepted count, passed}, seed_conf [B,ncap].  No host synchronisation; graph-capturable; the same input gives
+ * the same bits alone, in a batch and under replay. */
+int imcui_hip_adalam_forward(imcui_hip_t* h, int B, int ncap, int D, const float* descriptors0, const float* descriptors1,
+                             const float* keypoints0, const float* keypoints1, const float* scales0, const float* scales1,
+                             const float* oris0, const float* oris1, const int* n0, const int* n1, int h0, int w0, int h1, int w1,
+                             const double* conf, int* matches0, float* matching_scores0, int* nn, float* score, int* mnn, int* seed,
+                             int* seed_members, int* seed_info, float* seed_conf, void* ws, size_t ws_bytes, void* stream);
+/* kornia's `AdalamFilter.filter_matches`: the same from given nn / score / mnn [dev, B,ncap] (an nn outside [0, n1) takes its
+ * key-point out of every stage).  Doubles as the probe of stages B .. G. */
+int imcui_hip_adalam_filter(imcui_hip_t* h, int B, int ncap, const float* keypoints0, const float* keypoints1, const float* scales0,
+                            const float* scales1, const float* oris0, const float* oris1, const int* n0, const int* n1, int h0, int w0,
+                            int h1, int w1, const double* conf, const int* nn, const float* score, const int* mnn, int* matches0,
+                            float* matching_scores0, int* seed, int* seed_members, int* seed_info, float* seed_conf, void* ws,
+                            size_t ws_bytes, void* stream);
 
 /* ---- LoFTR (kornia.feature.LoFTR behind imcui/hloc/matchers/loftr.py:54) ---- */
 /* Host-side packing.  Every convolution / Linear is one layer W[N][K] (+ bias[N], may be NULL) in GEMM
